@@ -18,15 +18,27 @@ One step = one full top-k pass of all M queries against the corpus:
          Total work is fixed: "scaling": "strong".
 
 Run: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c5|c1|c2]
+                    [--dump-outputs DIR] [--full]
   --gpus N > 1 without a torch.distributed launcher: this process starts N rank
   processes itself (before touching the GPU) and exits with their status;
   under torch.distributed.run, WORLD_SIZE must equal N.
 
-Prints ONE JSON line on rank 0 with the metric, the dominant kernel's roofline
-(achieved TFLOP/s from HIP events on its launch stream vs the 157.3 TFLOP/s
-f32 MFMA peak) and CPU baselines (the oracle -- a port of the reference's
-algorithm -- on a bounded query sample on this host's cores; the reference's
-own benchmark size configs[0] in full under extra.c1).
+Prints ONE JSON line on rank 0 with the metric and the dominant kernel's
+roofline (achieved TFLOP/s from HIP events on its launch stream, recorded in
+the timed steps themselves, vs the 157.3 TFLOP/s f32 MFMA peak).  A plain run
+does only that: set-up, W warm-up steps, K timed steps, the line.
+
+--dump-outputs DIR writes the last timed step's result (what a caller of the
+timed path receives) as DIR/indices.npy (float64) and DIR/scores.npy
+(float32); the inputs are seeded, so two builds can be compared entry by entry.
+
+--full adds everything that takes runs of its own: the f64 spot check, the
+host-boundary rates, the CPU baselines (the oracle -- a port of the
+reference's algorithm -- on a bounded query sample on this host's cores; the
+reference's own benchmark size configs[0] in full under extra.c1), the
+secondary configs under "extra" and, for N > 1, the in-process transport.
+--cpu-sample, --boundary, --extra, --check and --inproc select among these
+and have no effect without --full.
 """
 from __future__ import annotations
 
@@ -794,9 +806,35 @@ def spot_check(q, c, lo, k, metric, out_i, out_s, rows, dist, world, rank):
     }
 
 
-def measure(name, steps, warmup, rank, world, dist, dev, check_rows=8, stride=1):
+DUMP_BYTES = 48 * 10**6  # --dump-outputs: both arrays together stay below this (the limit is 64 MB)
+DUMP_SEED = 20_240_607
+
+
+def dump_outputs(path, out_i, out_s):
+    """--dump-outputs: the (M, k) index and score lists of the last timed step
+    as path/indices.npy (float64: exact for any int32) and path/scores.npy
+    (float32).  A result larger than DUMP_BYTES is written as a fixed sample
+    of its query rows: a seeded choice without replacement that depends on M
+    alone, in ascending row order."""
+    import torch
+
+    M, k = out_i.shape
+    keep = DUMP_BYTES // (k * (8 + 4))
+    if M > keep:
+        rows = np.sort(np.random.RandomState(DUMP_SEED).choice(M, keep, replace=False))
+        rows = torch.from_numpy(rows).to(out_i.device)
+        out_i, out_s = out_i[rows], out_s[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "indices.npy"), out_i.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), out_s.float().cpu().numpy())
+    log(f"outputs: {out_i.shape[0]} of {M} query rows x {k} written to {path}")
+
+
+def measure(name, steps, warmup, rank, world, dist, dev, check_rows=8, stride=1, dump_dir=None):
     """One config's timed line (inputs resident, K steps bracketed by barrier
-    + synchronize, max over ranks).  Returns (fields, q, corpus shard)."""
+    + synchronize, max over ranks).  Returns (fields, q, corpus shard, the
+    index lists on the host).  dump_dir: rank 0 writes the last step's lists
+    there (dump_outputs)."""
     import torch
     from polars_matmul import _native
     from polars_matmul.sharded import ShardedTopK
@@ -810,6 +848,8 @@ def measure(name, steps, warmup, rank, world, dist, dev, check_rows=8, stride=1)
     runner = ShardedTopK(q, c, lo, k, mid, workspace=ws)
     torch.cuda.synchronize()
     elapsed, (out_i, out_s) = timed_steps(runner, steps, warmup, dist, stride)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, out_i, out_s)
     ks = kernel_stats(bf16)
     merge_bytes = _native.merge_bytes(ws.data_ptr(), M, n_loc, D, k, mid, compute) if ks["merge"][1] else None
     check = None
@@ -1354,7 +1394,18 @@ def main():
                          "process driving all N GPUs through pmm_set_devices) under extra.inproc")
     ap.add_argument("--inproc-timeout", type=int, default=0, help=argparse.SUPPRESS)  # 0: by problem size
     ap.add_argument("--inproc-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's index and score lists to "
+                         "DIR/indices.npy (float64) and DIR/scores.npy (float32); a result over 48 MB as a "
+                         "fixed seeded sample of its query rows")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the spot check (--check), the "
+                         "host-boundary rates (--boundary), the CPU baselines (--cpu-sample), the secondary "
+                         "configs (--extra) and, for N > 1, the in-process transport (--inproc); without "
+                         "--full those options have no effect")
     args = ap.parse_args()
+    if not args.full:
+        args.check, args.boundary, args.cpu_sample, args.extra, args.inproc = 0, 0, 0, "none", 0
     if args.metric and args.metric != CONFIGS[args.config][4]:
         global METRIC_OVERRIDE
         METRIC_OVERRIDE = args.metric
@@ -1409,7 +1460,7 @@ def main():
 
     M, N, D, k, metric, cdt = CONFIGS[args.config]
     fields, q, c, lists = measure(args.config, args.steps, args.warmup, rank, world, dist, dev, args.check,
-                                  args.timing_stride)
+                                  args.timing_stride, dump_dir=args.dump_outputs)
     if fields["check"]:
         log(f"spot check: {fields['check']}")
     # f32 lists of this workload's (M, N, D, k, metric) for the bf16 recall check of an extra line

@@ -97,10 +97,39 @@ def test_summary_is_the_last_key_and_carries_every_extra():
     assert len(json.dumps(sm)) < 4000
 
 
+def test_dump_outputs_writes_a_fixed_sample_within_the_size_limit(tmp_path):
+    # --dump-outputs: float64 indices and float32 scores; a result over the
+    # limit is written as the same seeded sample of query rows every time
+    import numpy as np
+    import torch
+
+    b = _bench_module()
+    m, k = 3000, 8
+    idx = torch.arange(m * k, dtype=torch.int32).reshape(m, k)
+    sc = torch.linspace(-1.0, 1.0, m * k).reshape(m, k)
+    b.DUMP_BYTES = 1000 * k * 12  # room for 1000 of the 3000 rows
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), idx, sc)
+    ia, sa = np.load(tmp_path / "a" / "indices.npy"), np.load(tmp_path / "a" / "scores.npy")
+    assert ia.dtype == np.float64 and sa.dtype == np.float32 and ia.shape == sa.shape == (1000, k)
+    assert ia.nbytes + sa.nbytes <= b.DUMP_BYTES
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "indices.npy"))
+    assert np.array_equal(sa, np.load(tmp_path / "b" / "scores.npy"))
+    rows = (ia[:, 0] // k).astype(np.int64)  # the sampled rows: distinct, ascending, each written whole
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(ia, idx.numpy()[rows]) and np.array_equal(sa, sc.numpy()[rows])
+    b.DUMP_BYTES = m * k * 12  # the whole result fits: written in full
+    b.dump_outputs(str(tmp_path / "c"), idx, sc)
+    assert np.array_equal(np.load(tmp_path / "c" / "indices.npy"), idx.numpy())
+
+
 def test_descendants_names_a_live_child():
     b = _bench_module()
-    p = subprocess.Popen([sys.executable, "-c", "import time; time.sleep(30)"])
+    # (the child says when it runs: before its exec the fork has no command line yet)
+    p = subprocess.Popen([sys.executable, "-c", "import time; print('up', flush=True); time.sleep(30)"],
+                         stdout=subprocess.PIPE)
     try:
+        assert p.stdout.readline().strip() == b"up"
         kids = b.descendants(os.getpid())
         assert any(k == p.pid and "sleep" in c for k, _, c in kids), kids
     finally:

@@ -3,7 +3,7 @@
 #   tools/gpu_suite.sh <tag> [tests] [smoke] [bench] [prof:<cfg>[:<pmc 0|1>]]...
 #   tests        the whole GPU suite (pytest -m gpu), as the driver runs it
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (python bench.py)
+#   bench        the whole bench line, every extra included (python bench.py --full)
 #   prof:c3:1    tools/profile.sh on one config (kernel trace + stats; with
 #                :1 the PMC passes too) and the PMC digest of its kernels
 # Output under gpurun_out/<tag>/ (and gpurun_out/prof_<tag>_<cfg>/).  Each
@@ -22,7 +22,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit 4
       tail -1 "$out/smoke.log" ;;
     bench)
-      timeout -k 10 900 python -u bench.py > "$out/bench.json" 2> "$out/bench.log" || { tail -20 "$out/bench.log"; exit 5; }
+      timeout -k 10 900 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.log" || { tail -20 "$out/bench.log"; exit 5; }
       python3 -c "import json,sys; d=json.load(open('$out/bench.json')); print(json.dumps(d['summary']))" ;;
     prof:*)
       IFS=: read -r _ cfg pmc <<< "$step"
