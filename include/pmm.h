@@ -190,15 +190,19 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
  * ------------------------------------------------------------------------- */
 
 /* Scratch bytes pmm_topk_f32_device (compute F32) or pmm_topk_bf16_device
- * (compute BF16) needs for this problem. */
+ * (compute BF16) needs for this problem, for the path the call will take
+ * with the environment as it is now (the screened f32 cosine path,
+ * PMM_F32_SCREEN, adds the bf16 images of both operands). */
 size_t pmm_topk_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int metric,
                                 int compute);
 
 /* Algorithmic bytes of the last fused top-k's merge pass (merge_kernel) for
  * this problem and workspace, read after the call completed: the split
  * counts, the candidates the GEMM left, the shared thresholds and the m x k
- * output.  Measurement only (the HBM-roofline line of the reduction,
- * SURVEY 8d); synchronous. */
+ * output; after a screened f32 call also the exact finish's traffic (every
+ * kept candidate read and rewritten, its f32 corpus row gathered).
+ * Measurement only (the HBM-roofline line of the reduction);
+ * synchronous.  Call it with the environment the top-k call ran under. */
 int pmm_topk_merge_bytes(const void *workspace, int64_t m, int64_t n, int64_t d, int64_t k,
                          int metric, int compute, uint64_t *bytes);
 

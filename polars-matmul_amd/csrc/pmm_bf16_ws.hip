@@ -25,6 +25,13 @@ hipError_t launch_bf16_ws_ks4(const GemmF32Args &a, int grid, size_t lds, hipStr
 hipError_t launch_bf16_ws_ks5(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
 hipError_t launch_bf16_ws_ks6(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
 
+hipError_t launch_bf16_ws_screen_ks1(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_bf16_ws_screen_ks2(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_bf16_ws_screen_ks3(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_bf16_ws_screen_ks4(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_bf16_ws_screen_ks5(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_bf16_ws_screen_ks6(const GemmF32Args &a, int grid, size_t lds, hipStream_t s);
+
 hipError_t launch_seed_bf16_ws_ks1(const GemmF32Args &a, float *S, int ns, hipStream_t s);
 hipError_t launch_seed_bf16_ws_ks2(const GemmF32Args &a, float *S, int ns, hipStream_t s);
 hipError_t launch_seed_bf16_ws_ks3(const GemmF32Args &a, float *S, int ns, hipStream_t s);
@@ -46,13 +53,26 @@ hipError_t launch_seed_bf16_ws(const GemmF32Args &a, float *S, int ns, hipStream
   }
 }
 
-hipError_t launch_gemm_bf16_ws(const GemmF32Args &a, int grid, hipStream_t s) {
+hipError_t launch_gemm_bf16_ws(const GemmF32Args &a, int grid, hipStream_t s, bool screen) {
   const size_t lds = gemm_bf16_ws_lds_bytes(a.capg, a.D);
   // the kernel's grid and tile shapes assume: whole 128-wide K-steps, a
   // capacity the LDS carve holds, and every unit's tiles inside the corpus
   if (lds > 160 * 1024 || a.D % kBf16DAlign != 0 || a.capg > kBf16WsMaxCapg || a.tps < 1 ||
       (int64_t)a.ntiles * ws::BN < a.N || (int64_t)a.QB * ws::BM < a.M)
     return hipErrorInvalidValue;
+  if (screen) {
+    // the band kept above a compaction's k-th needs room: the caller's limits
+    if (!a.eps || !a.ovf || a.ctrig < a.k + 8 || a.ctrig > a.capg - 64) return hipErrorInvalidValue;
+    switch (a.D / 128) {
+      case 1: return launch_bf16_ws_screen_ks1(a, grid, lds, s);
+      case 2: return launch_bf16_ws_screen_ks2(a, grid, lds, s);
+      case 3: return launch_bf16_ws_screen_ks3(a, grid, lds, s);
+      case 4: return launch_bf16_ws_screen_ks4(a, grid, lds, s);
+      case 5: return launch_bf16_ws_screen_ks5(a, grid, lds, s);
+      case 6: return launch_bf16_ws_screen_ks6(a, grid, lds, s);
+      default: return hipErrorInvalidValue;
+    }
+  }
   switch (a.D / 128) {
     case 1: return launch_bf16_ws_ks1(a, grid, lds, s);
     case 2: return launch_bf16_ws_ks2(a, grid, lds, s);

@@ -298,9 +298,20 @@ __device__ __forceinline__ bool unit_at(const GemmF32Args &a, int round, UnitPos
 // ===========================================================================
 // KS = padded D / 128 (K-steps per tile).
 // ===========================================================================
-template <int KS, int METRIC>
+//
+// SCREEN (cosine only): the kernel as a conservative screen for the exact f32
+// top-k.  Its scores are approximations (bf16-rounded operands) of the f32
+// path's, within a.eps[row] of them (screen_eps, pmm_device.h).  gthr[row]
+// keeps its meaning -- a lower bound L of the row's final *exact* k-th -- and
+// the row's LDS threshold holds L - eps in the approximate scores' space, so
+// the pre-filter, the drain's compare and the candidate appends are the
+// unscreened kernel's.  Only the compaction differs (compact_row_screen): it
+// publishes a_k - eps and keeps the whole band above a_k - 2 eps.  Candidates
+// carry approximate keys; screen_rescore_kernel makes them exact.
+template <int KS, int METRIC, bool SCREEN = false>
 __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a) {
   using namespace ws;
+  static_assert(!SCREEN || METRIC == kMetricCosine, "the screen's slack is a cosine bound");
   using C = Carve<KS>;
   constexpr int NST = C::NST, NHB = C::NHB;
   static_assert(drain_tiles<KS>() + (KS == 1 ? 4 : 3) < CVT, "queued survivors' column norms must stay in the ring");
@@ -491,6 +502,7 @@ __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a)
       barrier();
     }
   } else {
+  float eps_l = 0.0f;  // SCREEN: the slack of row `lane` (lanes 0..31), kept across a run's units
   for (int round = 0;; round++) {
     UnitPos u;
     if (!unit_at(a, round, u)) break;
@@ -510,9 +522,13 @@ __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a)
         const int grow = wrow0 + lane;
         const float qv = (XFORM && grow < a.M) ? a.qn[grow] : 0.0f;
         qex_w[lane] = qv;
-        const u64 t = (grow < a.M)
-                          ? __hip_atomic_load(a.gthr + grow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                          : ~0ull;
+        u64 t = (grow < a.M)
+                    ? __hip_atomic_load(a.gthr + grow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                    : ~0ull;
+        if (SCREEN) {
+          eps_l = (grow < a.M) ? a.eps[grow] : 0.0f;
+          t = screen_lower(t, eps_l);
+        }
         thr_w[lane] = t;
         lo_w[lane] = prefilter_bound<METRIC>(t, qv);
         cnt_w[lane] = 0u;
@@ -585,6 +601,7 @@ __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a)
         u64 gt = 0ull;
         if (split_unit && lane < 32 && wrow0 + lane < a.M)
           gt = __hip_atomic_load(a.gthr + wrow0 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (SCREEN) gt = screen_lower(gt, eps_l);
         for (int base = 0; base < qlen; base += 64) {
           const int i = base + lane;
           if (i < qlen) {
@@ -614,7 +631,8 @@ __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a)
               const int r = __builtin_ctzll(need);
               need &= need - 1;
               // (capg <= 512: compact_row's selection path, no LDS scratch)
-              compact_row(a, s, wrow0 + r, thr_w + r, cnt_w + r, nullptr, lane);
+              if (SCREEN) compact_row_screen(a, s, wrow0 + r, thr_w + r, cnt_w + r, __shfl(eps_l, r, 64), lane);
+              else compact_row(a, s, wrow0 + r, thr_w + r, cnt_w + r, nullptr, lane);
             }
             if (lane < 32) lo_w[lane] = prefilter_bound<METRIC>(thr_w[lane], qex_w[lane]);
             wave_sync();
@@ -1026,16 +1044,16 @@ static hipError_t launch_seed_bf16_ws_t(const GemmF32Args &a, float *S, int ns, 
   return hipGetLastError();
 }
 
-template <int KS, int METRIC>
+template <int KS, int METRIC, bool SCREEN = false>
 static hipError_t launch_bf16_ws_t(const GemmF32Args &a, int grid, size_t lds, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)gemm_bf16_ws_kernel<KS, METRIC>,
+    hipError_t e = hipFuncSetAttribute((const void *)gemm_bf16_ws_kernel<KS, METRIC, SCREEN>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  gemm_bf16_ws_kernel<KS, METRIC><<<dim3(grid), dim3(ws::NTH), lds, s>>>(a);
+  gemm_bf16_ws_kernel<KS, METRIC, SCREEN><<<dim3(grid), dim3(ws::NTH), lds, s>>>(a);
   return hipGetLastError();
 }
 

@@ -17,6 +17,13 @@ hipError_t PMM_CAT(launch_bf16_ws_ks, PMM_BF16_KS)(const GemmF32Args &a, int gri
   return launch_bf16_ws_t<PMM_BF16_KS, kMetricEuclidean>(a, grid, lds, s);
 }
 
+// the screen form for the exact f32 path (cosine only)
+hipError_t PMM_CAT(launch_bf16_ws_screen_ks, PMM_BF16_KS)(const GemmF32Args &a, int grid, size_t lds,
+                                                         hipStream_t s) {
+  if (a.metric != kMetricCosine) return hipErrorInvalidValue;
+  return launch_bf16_ws_t<PMM_BF16_KS, kMetricCosine, true>(a, grid, lds, s);
+}
+
 hipError_t PMM_CAT(launch_seed_bf16_ws_ks, PMM_BF16_KS)(const GemmF32Args &a, float *S, int ns,
                                                        hipStream_t s) {
   if (a.metric == kMetricCosine) return launch_seed_bf16_ws_t<PMM_BF16_KS, kMetricCosine>(a, S, ns, s);

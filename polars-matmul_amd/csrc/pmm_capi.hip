@@ -670,6 +670,295 @@ hipError_t run_fused_f32(const FusedF32 &f, const Plan &p, char *w, uint32_t ind
   return launch_merge(ma, 0, s);
 }
 
+// ---------------------------------------------------------------------------
+// Screened f32 top-k (cosine).  The wave-specialised bf16
+// kernel runs over bf16 images of Q and C as a conservative screen -- it keeps
+// every column whose exact score could reach the row's k-th, by a proven
+// slack -- and the few hundred kept candidates per row are re-scored with the
+// f32 path's arithmetic, so indices, scores and tie order are the f32
+// kernel's bit for bit at about 1/16 of its matrix-pipe time.
+// ---------------------------------------------------------------------------
+// set while a call re-runs rows (or a whole call) the screen could not finish
+thread_local bool t_no_screen = false;
+// (scope of a caller that never screens -- cached corpus norms, chunked
+// uploads: its workspace is sized for the unscreened layout)
+struct NoScreenScope {
+  bool prev;
+  NoScreenScope() : prev(t_no_screen) { t_no_screen = true; }
+  ~NoScreenScope() { t_no_screen = prev; }
+};
+bool bf16_native(int64_t d, int64_t k, int64_t n);
+size_t f32_topk_ws_bytes(int64_t m, int64_t n, int64_t dp, int64_t k, int metric, int cus);
+constexpr int64_t kScreenMaxK = 192;       // k + its 2 eps band + a drain round fit capg = 512
+constexpr int64_t kScreenRerunRows = 1024;  // rows per f32 re-run launch
+// m * n * d from which the screen is chosen without the knob.  Below it the
+// f32 kernel's launch is short against the screen's fixed passes (rounding the
+// corpus, seed, re-score, the count read-back).  Measured at D = 768, k = 100
+// (profiles/screen_c3/crossover.json): at 7.7e12 the screen wins 2.1-2.9x in
+// both shapes; at 7.7e11 it wins only with a long corpus and few rows (1000 x
+// 1M: 9.6 vs 13.3 ms) and loses at 10k x 100k and 100k x 10k; at 7.7e10 and
+// below it loses.
+constexpr double kScreenMinWork = 4e12, kScreenMinWorkLongCorpus = 5e11;
+
+struct ScreenPlan {
+  Plan b;  // the bf16 kernel's plan (counter, thresholds, counts, candidates, norms)
+  int64_t dpb = 0, dp = 0, rr = 0;
+  size_t off_qb = 0, off_cb = 0, off_rel = 0, off_eps = 0, off_bad = 0, off_ovf = 0, off_scal = 0, off_rows = 0,
+         off_crel = 0, off_gq = 0, off_gi = 0, off_gs = 0, off_f32 = 0, f32_bytes = 0, total = 0;
+};
+// PMM_F32_SCREEN (read per call): 0 = never, 1 = wherever the limits allow,
+// unset = from kScreenMinWork
+bool screen_enabled(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus) {
+  if (t_no_screen || metric != kMetricCosine || k > kScreenMaxK || !bf16_native(d, k, n)) return false;
+  const char *e = getenv("PMM_F32_SCREEN");
+  if (e && atoi(e) == 0) return false;
+  // (the padded dimension: callers name either d or roundup(d, 32))
+  const double work = (double)m * (double)n * (double)(cdiv(d, 32) * 32);
+  if (!e && !(work >= kScreenMinWork || (work >= kScreenMinWorkLongCorpus && n >= 100 * m))) return false;
+  Plan p;
+  plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, p, PMM_COMPUTE_BF16);
+  // the wave-specialised kernel, with room above k for the kept band before
+  // a drain round could pass the segment's end
+  return p.variant == -2 && p.capg <= kBf16WsMaxCapg && p.ctrig >= k + k / 2 + 32 && p.ctrig <= p.capg - 64;
+}
+void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, ScreenPlan &sp) {
+  sp.dpb = cdiv(d, kBf16DAlign) * kBf16DAlign;
+  sp.dp = cdiv(d, 32) * 32;
+  plan_topk(m, n, sp.dpb, k, metric, cus, sp.b, PMM_COMPUTE_BF16);
+  size_t off = sp.b.total;
+  sp.off_qb = off;
+  off = al256(off + (size_t)m * sp.dpb * 2);
+  sp.off_cb = off;
+  off = al256(off + (size_t)n * sp.dpb * 2);
+  sp.off_rel = off;
+  off = al256(off + (size_t)m * 4);
+  sp.off_eps = off;
+  off = al256(off + (size_t)m * 4);
+  sp.off_bad = off;  // [bad m | ovf m | scal 64 words]: one fill
+  off = al256(off + (size_t)m * 4);
+  sp.off_ovf = off;
+  off = al256(off + (size_t)m * 4);
+  sp.off_scal = off;  // [0] max corpus residual, [1] corpus unsafe, [2] re-run rows
+  off += 256;
+  sp.off_rows = off;
+  off = al256(off + (size_t)m * 4);
+  sp.off_crel = off;  // per corpus row: [residual n | unsafe flag n]
+  off = al256(off + (size_t)n * 8);
+  // re-run: gathered query rows, their lists, and the f32 path's own workspace
+  // (sized for the whole call, which an unsafe corpus sends there)
+  sp.rr = std::min<int64_t>(m, kScreenRerunRows);
+  sp.off_gq = off;
+  off = al256(off + (size_t)sp.rr * sp.dp * 4);
+  sp.off_gi = off;
+  off = al256(off + (size_t)sp.rr * k * 4);
+  sp.off_gs = off;
+  off = al256(off + (size_t)sp.rr * k * 4);
+  sp.off_f32 = off;
+  {
+    Plan f;
+    plan_topk(m, n, sp.dp, k, metric, cus, f);
+    sp.f32_bytes = f.total;
+    if (sp.rr < m) {
+      plan_topk(sp.rr, n, sp.dp, k, metric, cus, f);
+      sp.f32_bytes = std::max(sp.f32_bytes, f.total);
+    }
+  }
+  sp.total = off + sp.f32_bytes;
+}
+
+int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
+                         int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
+                         uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes,
+                         hipStream_t s, int dev, const float *c_norms, bool keep_gthr, bool allow_screen);
+
+int topk_f32_screened(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc, int64_t n, int64_t d,
+                      int64_t k, uint32_t index_base, uint32_t *out_idx, float *out_score, void *ws,
+                      size_t ws_bytes, hipStream_t s, int dev) {
+  const int cus = g_dev[dev].cus;
+  const int metric = kMetricCosine;
+  ScreenPlan sp;
+  plan_screen(m, n, d, k, metric, cus, sp);
+  const Plan &p = sp.b;
+  const bool own = !ws;
+  if (!ws) {
+    int rc = arena(dev, s, sp.total, &ws);
+    if (rc) return rc;
+  } else if (ws_bytes < sp.total) {
+    return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, sp.total);
+  }
+  char *w = (char *)ws;
+  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
+  uint16_t *qb = (uint16_t *)(w + sp.off_qb), *cb = (uint16_t *)(w + sp.off_cb);
+  float *rel = (float *)(w + sp.off_rel), *eps = (float *)(w + sp.off_eps);
+  unsigned *bad = (unsigned *)(w + sp.off_bad), *ovf = (unsigned *)(w + sp.off_ovf);
+  unsigned *scal = (unsigned *)(w + sp.off_scal);
+  int *rows = (int *)(w + sp.off_rows);
+  float *crel = (float *)(w + sp.off_crel);
+  HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
+  if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
+  HIP_TRY(hipMemsetAsync(w + sp.off_ovf, 0, sp.off_rows - sp.off_ovf, s));
+  {
+    // the exact norms and factors (norms_rows, as the unscreened path's), then
+    // the bf16 images with the rounding residuals and the unsafe flags
+    Timed t("norms_f32/round", s);
+    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, 0, s));
+    HIP_TRY(launch_screen_round(q, m, d, ldq, qn, qb, sp.dpb, rel, bad, nullptr, s));
+    HIP_TRY(launch_screen_round(c, n, d, ldc, cn, cb, sp.dpb, crel, (unsigned *)(crel + n), scal, s));
+  }
+  GemmF32Args a{};
+  a.qb = qb;
+  a.cb = cb;
+  a.qn = qn;
+  a.cn = cn;
+  a.cpre = cn + n;
+  a.ldq = sp.dpb;
+  a.ldc = sp.dpb;
+  a.M = (int)m;
+  a.N = (int)n;
+  a.D = (int)sp.dpb;
+  a.k = (int)k;
+  a.capg = p.capg;
+  a.ctrig = p.ctrig;
+  a.metric = metric;
+  a.QB = p.QB;
+  a.S = p.S;
+  a.tps = p.tps;
+  a.ntiles = p.T;
+  a.units = p.units;
+  a.counter = (unsigned *)(w + p.off_counter);
+  a.cand = (unsigned long long *)(w + p.off_cand);
+  a.wq = (unsigned long long *)(w + p.off_wq);
+  a.cnt = (unsigned *)(w + p.off_cnt);
+  a.gthr = (unsigned long long *)(w + p.off_gthr);
+  a.nst = 3;
+  a.pf = 1;
+  // (the bf16 path's knobs hold for its kernel here too)
+  static const int defer_env = getenv("PMM_BF16_DEFER") ? atoi(getenv("PMM_BF16_DEFER")) : 1;
+  a.defer = defer_env;
+  a.qb_full = p.qb_full;
+  static const int sync_env = getenv("PMM_BF16_SYNC") ? atoi(getenv("PMM_BF16_SYNC")) : 1;
+  a.round_sync = sync_env;
+  static const int tmo_env = getenv("PMM_BF16_SYNC_TIMEOUT_US") ? atoi(getenv("PMM_BF16_SYNC_TIMEOUT_US")) : 20000;
+  a.sync_timeout = tmo_env * 100;
+  const bool debug = getenv("PMM_SCREEN_DEBUG") != nullptr;
+  a.eps = eps;
+  a.ovf = ovf;
+  {
+    // the bf16 kernel's seed over the images (k-th approximate score of the
+    // first ns columns), lowered by eps into a bound of the exact k-th
+    const int64_t ns = kSeedMaxNs;
+    const int seed_env = getenv("PMM_BF16_SEED") ? atoi(getenv("PMM_BF16_SEED")) : 1;  // (per call)
+    const bool seeded = seed_env && 4 * k <= ns && n >= 8 * ns && (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
+    Timed t("seed_bf16/screen", s);
+    if (seeded) {
+      float *sample = (float *)(w + p.off_cand);
+      HIP_TRY(launch_seed_bf16_ws(a, sample, (int)ns, s));
+      HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
+    }
+    HIP_TRY(launch_screen_prep(rel, scal, (int)m, (int)sp.dpb, eps, a.gthr, seeded ? 1 : 0, s));
+  }
+  {
+    Timed t("gemm_f32_topk/screen", s);
+    HIP_TRY(launch_gemm_bf16_ws(a, p.grid, s, true));
+  }
+  {
+    Timed t("merge_topk/rescore", s);
+    ScreenFinishArgs fa{};
+    fa.q = q;
+    fa.c = c;
+    fa.ldq = ldq;
+    fa.ldc = ldc;
+    fa.qn = qn;
+    fa.cn = cn;
+    fa.eps = eps;
+    fa.M = (int)m;
+    fa.N = (int)n;
+    fa.dp = (int)sp.dp;
+    fa.S = p.S;
+    fa.capg = p.capg;
+    fa.cand = a.cand;
+    fa.cnt = a.cnt;
+    fa.gthr = a.gthr;
+    fa.stat = debug ? scal + 4 : nullptr;
+    HIP_TRY(launch_screen_rescore(fa, s));
+  }
+  {
+    MergeArgs ma{};
+    ma.cand = a.cand;
+    ma.cnt = a.cnt;
+    ma.gthr = a.gthr;
+    ma.capg = p.capg;
+    ma.M = (int)m;
+    ma.S = p.S;
+    ma.k_out = (int)k;
+    ma.P = p.P;
+    ma.metric = metric;
+    ma.index_base = index_base;
+    ma.out_idx = out_idx;
+    ma.out_score = out_score;
+    Timed t("merge_topk", s);
+    HIP_TRY(launch_merge(ma, 0, s));
+  }
+  HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
+                                  out_score, s));
+  // Rows the screen could not finish (unsafe, or a band that outgrew its
+  // segment) and an unsafe corpus: one read-back, then the f32 kernel.
+  HIP_TRY(launch_screen_collect(ovf, bad, (int)m, scal + 2, rows, s));
+  unsigned h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h, scal, 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // Many rows to re-run (a crowded corpus: clustered embeddings can fill the
+  // 2 eps band of most rows): one f32 launch over the whole call is cheaper
+  // than serial launches of kScreenRerunRows rows, each of which streams the
+  // corpus for a few query blocks.
+  const bool whole = h[1] != 0 || (int64_t)h[2] * 8 > m + 8 * kScreenRerunRows;
+  if (debug) {
+    float rc;
+    memcpy(&rc, &h[0], 4);
+    fprintf(stderr,
+            "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
+            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld\n",
+            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m);
+  }
+  int rc = PMM_OK;
+  NoScreenScope no_screen;
+  if (whole) {
+    rc = topk_f32_device_impl(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w + sp.off_f32,
+                              sp.f32_bytes, s, dev, nullptr, false, false);
+  } else {
+    float *gq = (float *)(w + sp.off_gq);
+    uint32_t *gi = (uint32_t *)(w + sp.off_gi);
+    float *gs = (float *)(w + sp.off_gs);
+    for (int64_t r0 = 0; r0 < (int64_t)h[2] && rc == PMM_OK; r0 += sp.rr) {
+      const int64_t r = std::min<int64_t>(sp.rr, (int64_t)h[2] - r0);
+      // (a smaller launch may plan more corpus splits: outside the reserved
+      // bytes it takes a buffer of its own)
+      const size_t need = f32_topk_ws_bytes(r, n, sp.dp, k, metric, cus);
+      char *fw = w + sp.off_f32;
+      char *tmp = nullptr;
+      if (need > sp.f32_bytes) {
+        HIP_TRY(hipMalloc(&tmp, need));
+        fw = tmp;
+      }
+      hipError_t e = launch_gather_rows_f32(q, ldq, rows + r0, (int)r, (int)sp.dp, gq, s);
+      if (e == hipSuccess)
+        rc = topk_f32_device_impl(gq, sp.dp, r, c, ldc, n, d, k, metric, index_base, gi, gs, fw, need, s, dev,
+                                  nullptr, false, false);
+      if (e == hipSuccess && rc == PMM_OK) e = launch_scatter_lists(gi, gs, rows + r0, (int)r, (int)k, out_idx, out_score, s);
+      if (tmp) {
+        const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffer is freed)
+        (void)hipFree(tmp);
+        if (e == hipSuccess) e = e2;
+      }
+      if (e != hipSuccess) {
+        return fail(PMM_ERR_HIP, "screen re-run: %s", hipGetErrorString(e));
+      }
+    }
+  }
+  if (rc) return rc;
+  return own ? arena_record(dev, s) : PMM_OK;
+}
+
 // c_norms: optional precomputed corpus norms for `metric` laid out as
 // [n norms | n pre-filter factors] (a pmm_corpus handle's cache); NULL =
 // compute them in this call.
@@ -682,12 +971,16 @@ int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c,
                          int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
                          uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes,
                          hipStream_t s, int dev, const float *c_norms = nullptr,
-                         bool keep_gthr = false) {
+                         bool keep_gthr = false, bool allow_screen = false) {
   // d is the logical dimension (norms follow ndarray's order over exactly d
   // elements); the GEMM runs over dp = roundup(d, 32), the rows being
   // zero-padded up to dp.
   const int cus = g_dev[dev].cus;
   const int64_t dp = cdiv(d, 32) * 32;
+  // allow_screen: the caller sized the workspace with pmm_topk_workspace_bytes
+  if (allow_screen && !c_norms && !keep_gthr && ldq % 4 == 0 && ldc % 4 == 0 && ldq >= dp && ldc >= dp &&
+      !(((uintptr_t)q | (uintptr_t)c) & 15) && screen_enabled(m, n, d, k, metric, cus))
+    return topk_f32_screened(q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, ws, ws_bytes, s, dev);
   if (k <= kFusedMaxK) {
     Plan p;
     plan_topk(m, n, dp, k, metric, cus, p);
@@ -770,6 +1063,10 @@ int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c,
       }
     }
     HIP_TRY(run_fused_f32(f, p, w, index_base, out_idx, out_score, "gemm_f32_topk", "merge_topk", s));
+    // (not under a keep_gthr chunk merge: its loader re-keys the scores)
+    if (metric == kMetricCosine && !keep_gthr)
+      HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
+                                      out_score, s));
     return own ? arena_record(dev, s) : PMM_OK;
   }
   // k beyond the fused path: materialise score chunks, row-select them.
@@ -1157,6 +1454,7 @@ constexpr int kChunks = 4;
 int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
                           int metric, uint32_t *out_idx, float *out_score, int dev, hipStream_t s) {
   const int64_t dp = cdiv(d, 32) * 32;
+  NoScreenScope no_screen;  // (chunks carry thresholds over: unscreened)
   int64_t bnd[kChunks + 1];
   bnd[0] = 0;
   bnd[1] = std::max<int64_t>(k, n / 16);
@@ -2087,6 +2385,11 @@ size_t pmm_topk_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int 
     return p.total;
   }
   if (k <= kFusedMaxK) {
+    if (screen_enabled(m, n, d, k, metric, cus)) {
+      ScreenPlan sp;
+      plan_screen(m, n, d, k, metric, cus, sp);
+      return sp.total;
+    }
     Plan p;
     plan_topk(m, n, d, k, metric, cus, p);
     return p.total;
@@ -2111,16 +2414,37 @@ int pmm_topk_merge_bytes(const void *workspace, int64_t m, int64_t n, int64_t d,
     std::lock_guard<std::mutex> lk(g_dev_mu);
     if (dev >= 0 && dev < kMaxDevices && g_dev[dev].probed) cus = g_dev[dev].cus;
   }
+  // the counts sit at the offsets of the layout the call used: the bf16 plan
+  // (a bf16 call, or the screened f32 path), the f32 plan behind the widened
+  // rows (a bf16 call past the bf16 kernels' limits), or the f32 plan
   Plan p;
-  plan_topk(m, n, d, k, metric, cus, p, compute);
+  size_t base = 0;
+  uint64_t row_bytes = 0;  // screened path: f32 bytes gathered per re-scored candidate
+  if (compute == PMM_COMPUTE_BF16 && !bf16_native(d, k, n)) {
+    if (k > kFusedMaxK)
+      return fail(PMM_ERR_UNSUPPORTED, "no merge pass on the materialised path (k > %d)", kFusedMaxK);
+    const int64_t dp32 = cdiv(d, 32) * 32;
+    base = al256((size_t)m * dp32 * 4) + al256((size_t)n * dp32 * 4);
+    plan_topk(m, n, dp32, k, metric, cus, p, PMM_COMPUTE_F32);
+  } else if (compute != PMM_COMPUTE_BF16 && screen_enabled(m, n, d, k, metric, cus)) {
+    ScreenPlan sp;
+    plan_screen(m, n, d, k, metric, cus, sp);
+    p = sp.b;
+    row_bytes = (uint64_t)sp.dp * 4;
+  } else {
+    plan_topk(m, n, d, k, metric, cus, p, compute);
+  }
   // the merge reads every row's split counts and shared threshold, the
-  // candidates the GEMM left, and writes the m x k (index, score) lists
+  // candidates the GEMM left, and writes the m x k (index, score) lists; the
+  // screened path's exact finish also reads and rewrites every candidate the
+  // screen kept and gathers its corpus row (and each query row once)
   std::vector<unsigned> cnt((size_t)m * p.segs);
-  HIP_TRY(hipMemcpy(cnt.data(), (const char *)workspace + p.off_cnt, cnt.size() * 4,
+  HIP_TRY(hipMemcpy(cnt.data(), (const char *)workspace + base + p.off_cnt, cnt.size() * 4,
                     hipMemcpyDeviceToHost));
   uint64_t cands = 0;
   for (unsigned c : cnt) cands += std::min<unsigned>(c, (unsigned)p.capg);
   *bytes = (uint64_t)m * p.segs * 4 + cands * 8 + (uint64_t)m * 8 + (uint64_t)m * k * 8;
+  if (row_bytes) *bytes += cands * (16 + row_bytes) + (uint64_t)m * (row_bytes + 8 + p.segs * 4);
   return PMM_OK;
 }
 
@@ -2152,7 +2476,7 @@ int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, 
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
   return topk_f32_device_impl(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
-                              workspace, workspace_bytes, s, dev);
+                              workspace, workspace_bytes, s, dev, nullptr, false, true);
 }
 
 int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
@@ -2228,7 +2552,7 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
   if ((rc = upload_padded(b + off_c, c, n, d, dp, 4, s))) return rc;
   rc = topk_f32_device_impl((const float *)(b + off_q), dp, m, (const float *)(b + off_c), dp, n,
                             d, k, metric, 0u, (uint32_t *)(b + off_i), (float *)(b + off_s),
-                            b + off_w, ws_need, s, dev);
+                            b + off_w, ws_need, s, dev, nullptr, false, true);
   if (rc) return rc;
   {
     Timed t("d2h", s);
@@ -2733,6 +3057,7 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = h->dp;
+  NoScreenScope no_screen;  // (cached corpus norms: unscreened)
   size_t ws_need = pmm_topk_workspace_bytes(m, h->n, dp, k, metric, PMM_COMPUTE_F32);
   size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
   size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);

@@ -491,4 +491,73 @@ __device__ inline void compact_row(const GemmF32Args &a, int s, int grow, u64 *t
   wave_sync();
 }
 
+// ===========================================================================
+// Screened f32 top-k (cosine): the bf16 kernel's score a_ij of (row i, column
+// j) against the f32 path's exact score s_ij.  With rq = ||q - bf16(q)|| / ||q||
+// for the row and rc >= ||c - bf16(c)|| / ||c|| for every column,
+//   |s_ij - a_ij| <= eps_i = rq (1 + rc) + rc        bf16 rounding of both operands
+//                                                    (Cauchy-Schwarz on dq.c + q^.dc)
+//                          + 8 D 2^-24 (1 + 2^-7)    f32 accumulation of the bf16 MFMA: any
+//                                                    summation order, every partial sum within
+//                                                    8 units of 2^-24 relative (its internal
+//                                                    order and rounding are not documented)
+//                          + 2 D 2^-24               the exact path's D-step fmaf chain
+//                          + 2^-20                   both epilogue divisions and the computed
+//                                                    norms in the shared denominator
+// (DESIGN.md §4a derives each term), inflated by 2^-9 relative for the f32
+// arithmetic of this function and of the measured rq, rc.
+// ===========================================================================
+__device__ __forceinline__ float screen_eps(float rq, float rc, int dp) {
+  const float round = rq * (1.0f + rc) + rc;
+  const float accum = (float)dp * (8.0f * (1.0f + 0x1p-7f) + 2.0f) * 0x1p-24f;
+  return (round + accum) * (1.0f + 0x1p-9f) + 0x1p-20f;
+}
+// A composite no higher than (the score of thr's key) - e, index part 0: every
+// composite whose score is at least that score - e compares above it.  0
+// (accept all) and ~0 (padding row) pass through; a NaN difference accepts all.
+__device__ __forceinline__ u64 screen_lower(u64 thr, float e) {
+  if (thr == ~0ull) return thr;
+  const uint32_t tk = (uint32_t)(thr >> 32);
+  if (tk == 0u) return 0ull;
+  float r = dekey32(tk) - e;
+  r = r - (fabsf(r) * 0x1p-22f + 0x1p-100f);  // (covers the subtraction's rounding)
+  return (u64)okey32(r) << 32;
+}
+// Compaction of a screened row's candidate buffer (approximate keys): with
+// a_k the k-th approximate composite, k columns have exact scores >= a_k -
+// eps, which is published as the row's bound; a column of the final top-k has
+// an approximate score >= (final exact k-th) - eps >= a_k - 2 eps, so that
+// band is kept, not just the best k.  A band that leaves no room for a drain
+// round (more than ctrig entries) marks the row overflowed -- it is finished
+// by the f32 kernel -- and keeps the best k, so the buffer stays in bounds.
+__device__ inline void compact_row_screen(const GemmF32Args &a, int s, int grow, u64 *thr_slot,
+                                          unsigned *cnt_slot, float eps, int lane) {
+  u64 *base = a.cand + ((int64_t)grow * a.S + s) * a.capg;
+  const int n = min((int)*cnt_slot, a.capg);  // (> k: the trigger is above k)
+  u64 x[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const int i = lane + 64 * e;
+    x[e] = (i < n) ? __hip_atomic_load(base + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+  }
+  const u64 ak = wave_kth_u64<8>(x, a.k);
+  const u64 keep = screen_lower(ak, 2.0f * eps);
+  const u64 keep1 = keep ? keep : 1ull;
+  int nk = 0;
+#pragma unroll
+  for (int e = 0; e < 8; e++) nk += __popcll(__ballot(x[e] >= keep1));
+  const bool over = nk > a.ctrig;
+  const u64 t = over ? ak : keep;
+  const int kept =
+      wave_keep_ge<8>(x, t, [&](int pos, u64 v) __attribute__((always_inline)) { base[pos] = v; }, lane);
+  wave_sync();
+  if (lane == 0) {
+    *cnt_slot = (unsigned)kept;
+    if (t > *thr_slot) *thr_slot = t;
+    atomicMax(a.gthr + grow, screen_lower(ak, eps));
+    if (over) a.ovf[grow] = 1u;
+  }
+  wave_sync();
+}
+
 }  // namespace pmm

@@ -70,6 +70,11 @@ struct GemmF32Args {
   unsigned long long *ffreg;
   unsigned *ffcnt;
   int ffcap;
+  // screened f32 path (gemm_bf16_ws_kernel<KS, cosine, true>): per-row slack
+  // of the bf16 scores against the exact f32 chain (score units), and per-row
+  // flags set when a row's kept band outgrew its candidate segment
+  const float *eps;
+  unsigned *ovf;
 };
 
 struct MergeArgs {
@@ -158,7 +163,8 @@ size_t gemm_bf16_lds_bytes(int capg, int nst);
 constexpr int kBf16WsBN = 64;
 constexpr int kBf16WsMaxCapg = 512;
 size_t gemm_bf16_ws_lds_bytes(int capg, int D);  // D = padded dimension
-hipError_t launch_gemm_bf16_ws(const GemmF32Args &a, int grid, hipStream_t s);
+// screen: the conservative-screen form of the kernel (cosine only; a.eps, a.ovf)
+hipError_t launch_gemm_bf16_ws(const GemmF32Args &a, int grid, hipStream_t s, bool screen = false);
 // bf16 threshold seed (pmm_bf16_ws_kernel.h): S[row][0..ns) = the scores of
 // corpus rows 0..ns-1 exactly as the wave-specialised kernel computes them
 hipError_t launch_seed_bf16_ws(const GemmF32Args &a, float *S, int ns, hipStream_t s);
@@ -188,6 +194,45 @@ hipError_t launch_bf16_to_f32(const uint16_t *src, int64_t rows, int64_t d, int6
 hipError_t launch_norms_bf16(const uint16_t *a, int64_t rows, int64_t d, int64_t ld, int squared,
                              float *out, float *inv, hipStream_t s);
 size_t merge_lds_bytes_per_wave(int P);
+// ---- screened f32 top-k (cosine): bf16 screen + exact f32 re-score ----
+// One pass over f32 rows: the bf16 image (RNE, row stride ldd, columns d..ldd-1
+// zero), per row an upper bound of ||x - bf16(x)|| / ||x|| in rel[] and an
+// "unsafe" flag in bad[] (non-finite or out-of-window element, or norm[row]
+// at or below the reference's 1e-6 rule).  With `scal`: scal[0] takes the
+// maximum rel over the safe rows (float bits), scal[1] is set when any row is
+// unsafe (the corpus form); both zeroed by the caller.
+hipError_t launch_screen_round(const float *src, int64_t rows, int64_t d, int64_t lds, const float *norm,
+                               uint16_t *dst, int64_t ldd, float *rel, unsigned *bad, unsigned *scal,
+                               hipStream_t s);
+// eps[row] from rel[row] and the corpus scalar; with `seeded` the rows' bf16
+// seed thresholds in gthr are lowered by eps into bounds of the exact k-th
+hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int dp, float *eps,
+                              unsigned long long *gthr, int seeded, hipStream_t s);
+struct ScreenFinishArgs {
+  const float *q, *c;
+  int64_t ldq, ldc;
+  const float *qn, *cn, *eps;
+  int M, N, dp, S, capg;
+  unsigned long long *cand;
+  const unsigned *cnt;
+  const unsigned long long *gthr;
+  unsigned *stat;  // optional: [0] += candidates re-scored, [1] = max per row
+};
+// every kept candidate's approximate key replaced by its exact composite (the
+// f32 path's fmaf chain and epilogue); entries below the final bound dropped
+hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s);
+// rows[0 .. *count) = the rows with ovf[row] | bad[row] set; count[1] += the overflowed ones
+hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,
+                                 hipStream_t s);
+// f32 cosine lists: +0.0 scores whose reference value is -0.0 get their sign
+// back (the selection keys fold the two zeros)
+hipError_t launch_zero_sign_cosine(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
+                                   const float *cn, int m, int64_t n, int d, int k, uint32_t index_base,
+                                   const uint32_t *out_idx, float *out_score, hipStream_t s);
+hipError_t launch_gather_rows_f32(const float *q, int64_t ldq, const int *rows, int r, int dp, float *dst,
+                                  hipStream_t s);
+hipError_t launch_scatter_lists(const uint32_t *oi, const float *os, const int *rows, int r, int k,
+                                uint32_t *out_idx, float *out_score, hipStream_t s);
 hipError_t launch_gemm_f64_store(const double *q, int64_t ldq, const double *c, int64_t ldc,
                                  const double *qn, const double *cn, int M, int N, int D,
                                  int metric, int store_metric, double *out, int64_t ldo,

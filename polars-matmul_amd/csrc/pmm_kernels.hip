@@ -2432,4 +2432,257 @@ hipError_t launch_rowsort_global(const void *scores, int64_t lds, int rows, int 
   return hipGetLastError();
 }
 
+// ===========================================================================
+// Screened f32 top-k (cosine), the passes around the bf16 screen kernel
+// (pmm_bf16_ws_kernel.h, SCREEN; the bound is screen_eps in pmm_device.h).
+// ===========================================================================
+// The element window of a "safe" row: inside it squares, products and sums of
+// up to 2^16 of them stay normal f32 numbers (no overflow, no subnormal the
+// MFMA might flush), and the bf16 rounding (same exponent range) keeps its
+// 2^-8 relative bound.  Zero is safe (exact in bf16).
+constexpr float kScreenMinAbs = 0x1p-48f, kScreenMaxAbs = 0x1p48f;
+
+// One wave per row, four elements per lane and step (16-byte loads, 8-byte
+// stores: rows 16-byte aligned, strides multiples of 4).
+__global__ __launch_bounds__(256) void screen_round_kernel(const float *__restrict__ src, int64_t rows, int64_t d,
+                                                           int64_t lds, const float *__restrict__ norm,
+                                                           uint16_t *__restrict__ dst, int64_t ldd,
+                                                           float *__restrict__ rel, unsigned *__restrict__ bad,
+                                                           unsigned *scal) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;  // whole wave
+  const float *p = src + row * lds;
+  uint16_t *o = dst + row * ldd;
+  const int64_t d4 = (d + 3) & ~(int64_t)3;  // (<= lds: readable)
+  float n2 = 0.0f, r2 = 0.0f;
+  bool ok = true;
+  for (int64_t i = 4 * lane; i < ldd; i += 256) {
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (i < d4) v = *(const f32x4 *)(p + i);
+    uint32_t b[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float x = (i + j < d) ? v[j] : 0.0f;
+      const uint32_t u = __float_as_uint(x);
+      // round to nearest even; NaN stays NaN
+      b[j] = (x != x) ? ((u >> 16) | 0x40u) : ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+      const float r = x - __uint_as_float(b[j] << 16);  // (exact for a safe element)
+      n2 = fmaf(x, x, n2);
+      r2 = fmaf(r, r, r2);
+      const float ax = fabsf(x);
+      ok = ok && (ax == 0.0f || (ax >= kScreenMinAbs && ax <= kScreenMaxAbs));
+    }
+    *(uint2 *)(o + i) = make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    n2 += __shfl_xor(n2, off);
+    r2 += __shfl_xor(r2, off);
+  }
+  const bool all_ok = __ballot(!ok) == 0ull;
+  if (lane == 0) {
+    const bool unsafe = !all_ok || !(norm[row] > 1e-6f) || !(n2 > 0.0f);
+    // (the sums' and the square root's rounding: far inside the 2^-9 inflation;
+    // a safe row's true ratio is below 2^-8, bf16's half ulp)
+    const float rl = unsafe ? 0x1p-8f : fminf(__builtin_sqrtf(r2 / n2) * (1.0f + 0x1p-9f), 0x1p-8f);
+    rel[row] = rl;
+    bad[row] = unsafe ? 1u : 0u;
+    if (scal) {
+      if (unsafe) {
+        atomicOr(scal + 1, 1u);
+      } else if (__float_as_uint(rl) > __hip_atomic_load(scal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        atomicMax(scal, __float_as_uint(rl));  // (non-negative floats order as their bits)
+      }
+    }
+  }
+}
+hipError_t launch_screen_round(const float *src, int64_t rows, int64_t d, int64_t lds, const float *norm,
+                               uint16_t *dst, int64_t ldd, float *rel, unsigned *bad, unsigned *scal,
+                               hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (lds % 4 != 0 || ldd % 4 != 0 || ldd < d || lds < ((d + 3) & ~(int64_t)3) || ((uintptr_t)src & 15) ||
+      ((uintptr_t)dst & 7))
+    return hipErrorInvalidValue;
+  screen_round_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(src, rows, d, lds, norm, dst, ldd, rel, bad, scal);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void screen_prep_kernel(const float *__restrict__ rel,
+                                                          const unsigned *__restrict__ scal, int m, int dp,
+                                                          float *__restrict__ eps, u64 *gthr, int seeded) {
+  const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (row >= m) return;
+  const float e = screen_eps(rel[row], __uint_as_float(scal[0]), dp);
+  eps[row] = e;
+  // the bf16 seed's k-th approximate composite (- 1) -> a bound of the exact k-th
+  if (seeded) gthr[row] = screen_lower(gthr[row], e);
+}
+hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int dp, float *eps,
+                              unsigned long long *gthr, int seeded, hipStream_t s) {
+  if (m <= 0) return hipSuccess;
+  screen_prep_kernel<<<(unsigned)((m + 255) / 256), 256, 0, s>>>(rel, scal, m, dp, eps, gthr, seeded);
+  return hipGetLastError();
+}
+
+// Exact finish, first half: one workgroup per query row (staged in LDS, read
+// as broadcasts), one thread per kept candidate.  An entry whose approximate
+// key is below (the row's final bound) - eps cannot be in the top-k and is
+// emptied; every other entry's corpus row is gathered (16-byte loads, 128
+// bytes in flight per lane) and scored by the f32 path's arithmetic -- the
+// fmaf chain over the padded K in natural order from 0, exact_score on the
+// reference-order norms: seed_lds_block's, bit for bit the fused kernel's --
+// and its composite replaces the approximate one in place.  merge_kernel then
+// selects and orders the exact top-k as for the unscreened kernels.
+__global__ __launch_bounds__(256) void screen_rescore_kernel(ScreenFinishArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *qs = (float *)smem;
+  const int tid = threadIdx.x;
+  const int row = (int)blockIdx.x;
+  const float *qr = a.q + (int64_t)row * a.ldq;
+  for (int i = 4 * tid; i < a.dp; i += 1024) *(f32x4 *)(qs + i) = *(const f32x4 *)(qr + i);
+  __syncthreads();
+  const float qv = a.qn[row];
+  const u64 T = screen_lower(a.gthr[row], a.eps[row]);
+  const u64 T1 = T ? T : 1ull;
+  int mine = 0;
+  for (int s = 0; s < a.S; s++) {
+    const int n_s = min((int)a.cnt[(int64_t)row * a.S + s], a.capg);
+    u64 *seg = a.cand + ((int64_t)row * a.S + s) * a.capg;
+    for (int i = tid; i < n_s; i += 256) {
+      const u64 x = seg[i];
+      const uint32_t col = ~(uint32_t)x;
+      if (x < T1 || col >= (uint32_t)a.N) {
+        seg[i] = 0ull;
+        continue;
+      }
+      const float *cr = a.c + (int64_t)col * a.ldc;
+      mine++;
+      float acc = 0.0f;
+      for (int k0 = 0; k0 < a.dp; k0 += 32) {
+        f32x4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = *(const f32x4 *)(cr + k0 + 4 * j);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const f32x4 q4 = *(const f32x4 *)(qs + k0 + 4 * j);
+          acc = fmaf(q4[0], v[j][0], acc);
+          acc = fmaf(q4[1], v[j][1], acc);
+          acc = fmaf(q4[2], v[j][2], acc);
+          acc = fmaf(q4[3], v[j][3], acc);
+        }
+      }
+      const float sc = exact_score<kMetricCosine>(acc, qv, a.cn[col]);
+      seg[i] = ((u64)okey32(sc) << 32) | (u64)(~col);
+    }
+  }
+  if (a.stat) {  // (diagnostics: PMM_SCREEN_DEBUG)
+    __shared__ unsigned kept;
+    __syncthreads();  // (every thread is past its reads of qs)
+    if (tid == 0) kept = 0u;
+    __syncthreads();
+    atomicAdd(&kept, (unsigned)mine);
+    __syncthreads();
+    if (tid == 0) {
+      atomicAdd(a.stat, kept);
+      atomicMax(a.stat + 1, kept);
+    }
+  }
+}
+hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s) {
+  if (a.M <= 0) return hipSuccess;
+  if (a.dp % 32 != 0 || a.dp > 4096 || a.ldq % 4 != 0 || a.ldc % 4 != 0 || a.ldq < a.dp || a.ldc < a.dp ||
+      (((uintptr_t)a.q | (uintptr_t)a.c) & 15))
+    return hipErrorInvalidValue;
+  screen_rescore_kernel<<<(unsigned)a.M, 256, (size_t)a.dp * 4, s>>>(a);
+  return hipGetLastError();
+}
+
+// The selection keys fold -0 onto +0 (equal scores go to the lower index), so
+// a list's zero scores all come out as +0.0.  The reference keeps the sign: a
+// cosine of -0.0 where a negative dot is divided by an overflowed norm product
+// or underflows.  One thread per returned entry: a +0.0 score is recomputed
+// by the reference's arithmetic -- the fmaf chain over exactly d elements in
+// natural order, exact_score on the reference-order norms -- and rewritten
+// when that is a zero, with its sign.  Zero scores are rare; every other
+// entry costs its 4-byte read.
+__global__ __launch_bounds__(256) void zero_sign_kernel(const float *__restrict__ q, int64_t ldq,
+                                                        const float *__restrict__ c, int64_t ldc,
+                                                        const float *__restrict__ qn,
+                                                        const float *__restrict__ cn, int m, int64_t n, int d,
+                                                        int k, uint32_t index_base,
+                                                        const uint32_t *__restrict__ out_idx,
+                                                        float *__restrict__ out_score) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)m * k) return;
+  if (__float_as_uint(out_score[t]) != 0u) return;
+  const uint32_t id = out_idx[t];
+  if (id == 0xFFFFFFFFu) return;
+  const int64_t col = (int64_t)(uint32_t)(id - index_base);
+  if (col >= n) return;
+  const int row = (int)(t / k);
+  const float *qr = q + (int64_t)row * ldq, *cr = c + col * ldc;
+  float acc = 0.0f;
+  for (int i = 0; i < d; i++) acc = fmaf(qr[i], cr[i], acc);
+  const float sc = exact_score<kMetricCosine>(acc, qn[row], cn[col]);
+  if (sc == 0.0f) out_score[t] = sc;
+}
+hipError_t launch_zero_sign_cosine(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
+                                   const float *cn, int m, int64_t n, int d, int k, uint32_t index_base,
+                                   const uint32_t *out_idx, float *out_score, hipStream_t s) {
+  if (m <= 0 || k <= 0) return hipSuccess;
+  zero_sign_kernel<<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(q, ldq, c, ldc, qn, cn, m, n, d, k,
+                                                                           index_base, out_idx, out_score);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void screen_collect_kernel(const unsigned *__restrict__ ovf,
+                                                             const unsigned *__restrict__ bad, int m,
+                                                             unsigned *count, int *__restrict__ rows) {
+  const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (row < m && (ovf[row] | bad[row])) {
+    rows[atomicAdd(count, 1u)] = row;
+    if (ovf[row]) atomicAdd(count + 1, 1u);
+  }
+}
+hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,
+                                 hipStream_t s) {
+  if (m <= 0) return hipSuccess;
+  screen_collect_kernel<<<(unsigned)((m + 255) / 256), 256, 0, s>>>(ovf, bad, m, count, rows);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float *__restrict__ q, int64_t ldq,
+                                                              const int *__restrict__ rows, int r, int dp,
+                                                              float *__restrict__ dst) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)r * dp) return;
+  const int i = (int)(t / dp), c = (int)(t - (int64_t)i * dp);
+  dst[t] = q[(int64_t)rows[i] * ldq + c];
+}
+hipError_t launch_gather_rows_f32(const float *q, int64_t ldq, const int *rows, int r, int dp, float *dst,
+                                  hipStream_t s) {
+  if (r <= 0) return hipSuccess;
+  gather_rows_f32_kernel<<<(unsigned)(((int64_t)r * dp + 255) / 256), 256, 0, s>>>(q, ldq, rows, r, dp, dst);
+  return hipGetLastError();
+}
+__global__ __launch_bounds__(256) void scatter_lists_kernel(const uint32_t *__restrict__ oi,
+                                                            const float *__restrict__ os,
+                                                            const int *__restrict__ rows, int r, int k,
+                                                            uint32_t *__restrict__ out_idx,
+                                                            float *__restrict__ out_score) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)r * k) return;
+  const int i = (int)(t / k), j = (int)(t - (int64_t)i * k);
+  out_idx[(int64_t)rows[i] * k + j] = oi[t];
+  out_score[(int64_t)rows[i] * k + j] = os[t];
+}
+hipError_t launch_scatter_lists(const uint32_t *oi, const float *os, const int *rows, int r, int k,
+                                uint32_t *out_idx, float *out_score, hipStream_t s) {
+  if (r <= 0) return hipSuccess;
+  scatter_lists_kernel<<<(unsigned)(((int64_t)r * k + 255) / 256), 256, 0, s>>>(oi, os, rows, r, k, out_idx,
+                                                                               out_score);
+  return hipGetLastError();
+}
+
 }  // namespace pmm
