@@ -138,6 +138,13 @@ int probe_device(int dev) {
   return PMM_OK;
 }
 
+// CUs to plan for: the probed device's, 256 before any probe (no GPU: the
+// planners still run, see pmm_shard_plan).
+int device_cus(int dev) {
+  std::lock_guard<std::mutex> lk(g_dev_mu);
+  return (dev >= 0 && dev < kMaxDevices && g_dev[dev].probed) ? g_dev[dev].cus : 256;
+}
+
 // Device-pointer entry points (scope == NULL) run on the caller's current
 // device and leave it alone.  Host entry points pass a scope: they run on
 // `want` (a corpus handle's device), else on pmm_set_device's choice for this
@@ -245,9 +252,6 @@ struct Plan {
   size_t off_ffcnt = 0, off_ffreg = 0, off_fb = 0;
   size_t total = 0;
 };
-// set while a call re-runs the rows the fire-and-forget kernel could not
-// prove exact (they go to the wave-specialised kernel)
-thread_local bool t_no_ff = false;
 
 void plan_units(int64_t m, int64_t n, int bm, int bn, int cus, double unit_overhead, int64_t max_S,
                 Plan &p, bool whole_blocks = false) {
@@ -360,8 +364,10 @@ bool bf16_ff_enabled(int64_t k, int64_t n, int64_t d) {
 #endif
 }
 
+// allow_ff = false: the re-run of the rows the fire-and-forget kernel could not
+// prove exact (they go to the wave-specialised kernel).
 int plan_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, Plan &p,
-              int compute = PMM_COMPUTE_F32) {
+              int compute = PMM_COMPUTE_F32, bool allow_ff = true) {
   // testing knob: plan for fewer workgroups (small problems then take the
   // whole-query-block schedule that only full-size runs reach otherwise);
   // read per call so a test can set and clear it
@@ -382,7 +388,7 @@ int plan_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, P
     if (cap_env > 0 && k + 64 <= 512) p.capg = std::max<int>(((int)k + 64 + 7) / 8 * 8, std::min(cap_env, 512) / 8 * 8);
   }
   const bool bf16 = compute == PMM_COMPUTE_BF16;
-  const bool ffk = bf16 && !t_no_ff && bf16_ff_enabled(k, n, d);
+  const bool ffk = bf16 && allow_ff && bf16_ff_enabled(k, n, d);
   const bool ws = bf16 && !ffk && bf16_ws_enabled(p.capg, d);
   // the wave-specialised kernel on 16x16x32: twice the power of two (512 at
   // k = 100) compacts less often; c4 alternated twice on one box: 131.0 /
@@ -564,55 +570,132 @@ int gemm_store_f32(const float *q, int64_t ldq, int64_t rows, const float *c, in
   return PMM_OK;
 }
 
-// One fused top-k pass (gemm_f32_kernel + merge_kernel) over a planned
-// workspace whose work counter and shared thresholds are already set.
-struct FusedF32 {
-  const float *q;
-  int64_t ldq, m;
-  const float *c;
-  int64_t ldc, n, dp, k;
-  int metric;
-  const float *qn, *cn, *cpre;
-};
-hipError_t run_fused_f32(const FusedF32 &f, const Plan &p, char *w, uint32_t index_base,
-                         uint32_t *out_idx, float *out_score, const char *gemm_label,
-                         const char *merge_label, hipStream_t s) {
-  // whole query blocks first (see gemm_f32_kernel's unit decode)
-  const int64_t units = p.qb_full ? p.qb_full + (int64_t)(p.QB - p.qb_full) * p.S : p.units;
-  // the caller has zeroed [w, w + p.off_cand): counter, thresholds, counts
+// ---------------------------------------------------------------------------
+// Argument builders: every fused launch (the f32 kernel, the bf16 kernels, the
+// screen) and every merge fills its arguments here, so a workspace offset or a
+// knob is read in one place.
+// ---------------------------------------------------------------------------
+// The fields every fused launch shares: shape, work decomposition and the
+// plan's workspace regions at base w.  The caller adds its operands (rows,
+// norms, strides).
+GemmF32Args fused_args(int64_t m, int64_t n, int64_t dp, int64_t k, int metric, const Plan &p, char *w) {
   GemmF32Args a{};
-  a.q = f.q;
-  a.c = f.c;
-  a.qn = f.qn;
-  a.cn = f.cn;
-  a.cpre = f.cpre;
-  a.ldq = f.ldq;
-  a.ldc = f.ldc;
-  a.M = (int)f.m;
-  a.N = (int)f.n;
-  a.D = (int)f.dp;
-  a.k = (int)f.k;
+  a.M = (int)m;
+  a.N = (int)n;
+  a.D = (int)dp;
+  a.k = (int)k;
   a.capg = p.capg;
   a.ctrig = p.ctrig;
-  a.metric = f.metric;
+  a.metric = metric;
   a.QB = p.QB;
+  // The kernels index a row's candidate segments with S.  The f32 kernel's
+  // column-split variant keeps two segments per corpus split (segs = 2 S);
+  // every other kernel has segs == S.
+  a.S = p.segs;
   a.tps = p.tps;
   a.ntiles = p.T;
-  a.units = (int)units;
+  a.units = p.units;
   a.qb_full = p.qb_full;
-  a.S = p.segs;  // (the kernel indexes candidate segments with it)
   a.counter = (unsigned *)(w + p.off_counter);
+  a.cand = (unsigned long long *)(w + p.off_cand);
+  a.wq = (unsigned long long *)(w + p.off_wq);
+  a.cnt = (unsigned *)(w + p.off_cnt);
+  a.gthr = (unsigned long long *)(w + p.off_gthr);
+  return a;
+}
+
+// The bf16 kernels' launch knobs (the screen runs the same kernel: they hold
+// there too).  Read once per process.
+void set_bf16_knobs(GemmF32Args &a) {
+  a.nst = 3;  // LDS ring slots of the bf16 kernel
+  a.pf = 1;
+  static const int defer_env = getenv("PMM_BF16_DEFER") ? atoi(getenv("PMM_BF16_DEFER")) : 1;
+  a.defer = defer_env;
+  static const int sync_env = getenv("PMM_BF16_SYNC") ? atoi(getenv("PMM_BF16_SYNC")) : 1;
+  a.round_sync = sync_env;
+  // round-barrier spin limit: workgroups of one round finish up to a few ms
+  // apart (uneven epilogues); a workgroup that times out stops syncing
+  static const int tmo_env = getenv("PMM_BF16_SYNC_TIMEOUT_US") ? atoi(getenv("PMM_BF16_SYNC_TIMEOUT_US")) : 20000;
+  a.sync_timeout = tmo_env * 100;
+}
+
+// merge_kernel's loader 0: the candidate segments a fused launch with
+// arguments `a` left, into m x k lists.
+MergeArgs merge_cand_args(const GemmF32Args &a, const Plan &p, uint32_t index_base, uint32_t *out_idx,
+                          float *out_score) {
+  MergeArgs ma{};
+  ma.cand = a.cand;
+  ma.cnt = a.cnt;
+  ma.gthr = a.gthr;
+  ma.capg = p.capg;
+  ma.M = a.M;
+  ma.S = p.segs;
+  ma.k_out = a.k;
+  ma.P = p.P;
+  ma.metric = a.metric;
+  ma.index_base = index_base;
+  ma.out_idx = out_idx;
+  ma.out_score = out_score;
+  return ma;
+}
+
+// merge_kernel's loader 1: `lists` (idx, score) lists of k_in entries per row
+// (chunks of one corpus, device shards, the strided merge API; see MergeArgs
+// for the strides).  sorted: every list is best-first, e.g. a top-k output.
+MergeArgs merge_lists_args(const uint32_t *idx, const float *score, int64_t m, int64_t lists, int64_t k_in,
+                           int64_t row_stride, int64_t list_stride, int64_t k_out, int metric, bool sorted,
+                           uint32_t *out_idx, float *out_score) {
+  MergeArgs ma{};
+  ma.in_idx = idx;
+  ma.in_score = score;
+  ma.k_in = (int)k_in;
+  ma.row_stride = row_stride;
+  ma.list_stride = list_stride;
+  ma.M = (int)m;
+  ma.S = (int)lists;
+  ma.sorted = sorted ? 1 : 0;
+  ma.k_out = (int)k_out;
+  ma.P = std::min(8192, next_pow2(2 * (int)k_out + 64, 128));
+  ma.metric = metric;
+  ma.out_idx = out_idx;
+  ma.out_score = out_score;
+  return ma;
+}
+
+// The call's workspace: the caller's when one is given (and large enough),
+// else the thread's arena, whose use done() marks at the end of the call.
+struct Workspace {
+  char *w = nullptr;
+  bool own = false;
+  int dev = 0;
+  hipStream_t s = nullptr;
+  int done() const { return own ? arena_record(dev, s) : PMM_OK; }
+};
+int acquire_workspace(void *ws, size_t ws_bytes, size_t need, int dev, hipStream_t s, Workspace &out) {
+  out.own = !ws;
+  out.dev = dev;
+  out.s = s;
+  if (!ws) {
+    if (int rc = arena(dev, s, need, &ws)) return rc;
+  } else if (ws_bytes < need) {
+    return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  }
+  out.w = (char *)ws;
+  return PMM_OK;
+}
+
+// One fused f32 pass (gemm_f32_kernel + merge_kernel) with arguments `a` over
+// a planned workspace whose work counter and shared thresholds are already
+// set (the caller has zeroed [w, w + p.off_cand): counter, thresholds, counts).
+hipError_t run_fused_f32(GemmF32Args a, const Plan &p, uint32_t index_base, uint32_t *out_idx, float *out_score,
+                         hipStream_t s) {
+  // whole query blocks first (see gemm_f32_kernel's unit decode)
+  if (p.qb_full) a.units = (int)(p.qb_full + (int64_t)(p.QB - p.qb_full) * p.S);
 #ifdef PMM_LAB
   {
     static const int ablate = getenv("PMM_ABLATE") ? atoi(getenv("PMM_ABLATE")) : 0;
     a.ablate = ablate;
   }
-#endif
-  a.cand = (unsigned long long *)(w + p.off_cand);
-  a.wq = (unsigned long long *)(w + p.off_wq);
-  a.cnt = (unsigned *)(w + p.off_cnt);
-  a.gthr = (unsigned long long *)(w + p.off_gthr);
-#ifdef PMM_LAB
   // per-phase cycle counters of the f32 kernel (make lab LAB=-DPMM_F32_STATS,
   // PMM_STATS=1): summed over waves, printed per call
   static const bool f32_stats = getenv("PMM_STATS") != nullptr;
@@ -628,7 +711,7 @@ hipError_t run_fused_f32(const FusedF32 &f, const Plan &p, char *w, uint32_t ind
   }
 #endif
   {
-    Timed t(gemm_label, s);
+    Timed t("gemm_f32_topk", s);
     hipError_t e = launch_gemm_f32(a, p.variant, 0, p.grid, s);
     if (e != hipSuccess) return e;
   }
@@ -647,26 +730,14 @@ hipError_t run_fused_f32(const FusedF32 &f, const Plan &p, char *w, uint32_t ind
     a.stats = nullptr;
   }
 #endif
-  MergeArgs ma{};
-  ma.cand = a.cand;
-  ma.cnt = a.cnt;
-  ma.gthr = a.gthr;
-  ma.capg = p.capg;
-  ma.M = (int)f.m;
-  ma.S = p.segs;
-  ma.k_out = (int)f.k;
-  ma.P = p.P;
-  ma.metric = f.metric;
-  ma.index_base = index_base;
-  ma.out_idx = out_idx;
-  ma.out_score = out_score;
+  MergeArgs ma = merge_cand_args(a, p, index_base, out_idx, out_score);
 #ifdef PMM_LAB
   {
     static const int ablate = getenv("PMM_MERGE_ABLATE") ? atoi(getenv("PMM_MERGE_ABLATE")) : 0;
     ma.ablate = ablate;
   }
 #endif
-  Timed t(merge_label, s);
+  Timed t("merge_topk", s);
   return launch_merge(ma, 0, s);
 }
 
@@ -678,18 +749,13 @@ hipError_t run_fused_f32(const FusedF32 &f, const Plan &p, char *w, uint32_t ind
 // f32 path's arithmetic, so indices, scores and tie order are the f32
 // kernel's bit for bit at about 1/16 of its matrix-pipe time.
 // ---------------------------------------------------------------------------
-// set while a call re-runs rows (or a whole call) the screen could not finish
-thread_local bool t_no_screen = false;
-// (scope of a caller that never screens -- cached corpus norms, chunked
-// uploads: its workspace is sized for the unscreened layout)
-struct NoScreenScope {
-  bool prev;
-  NoScreenScope() : prev(t_no_screen) { t_no_screen = true; }
-  ~NoScreenScope() { t_no_screen = prev; }
-};
-bool bf16_native(int64_t d, int64_t k, int64_t n);
-size_t f32_topk_ws_bytes(int64_t m, int64_t n, int64_t dp, int64_t k, int metric, int cus);
-constexpr int64_t kScreenMaxK = 192;       // k + its 2 eps band + a drain round fit capg = 512
+// Whether the bf16 MFMA kernels take the shape themselves (see the bf16
+// compute path below for their limits).
+bool bf16_native(int64_t d, int64_t k, int64_t n) {
+  return cdiv(d, kBf16DAlign) * kBf16DAlign <= kBf16MaxD && n < (int64_t(1) << 27) &&
+         next_pow2((int)std::min<int64_t>(k, 1 << 20) + 64, 128) <= kBf16MaxCapg;
+}
+constexpr int64_t kScreenMaxK = 192;      // k + its 2 eps band + a drain round fit capg = 512
 constexpr int64_t kScreenRerunRows = 1024;  // rows per f32 re-run launch
 // m * n * d from which the screen is chosen without the knob.  Below it the
 // f32 kernel's launch is short against the screen's fixed passes (rounding the
@@ -700,32 +766,27 @@ constexpr int64_t kScreenRerunRows = 1024;  // rows per f32 re-run launch
 // below it loses.
 constexpr double kScreenMinWork = 4e12, kScreenMinWorkLongCorpus = 5e11;
 
+// The screened path's workspace behind the bf16 kernel's own plan (counter,
+// thresholds, counts, candidates, norms), which starts it.
 struct ScreenPlan {
-  Plan b;  // the bf16 kernel's plan (counter, thresholds, counts, candidates, norms)
   int64_t dpb = 0, dp = 0, rr = 0;
   size_t off_qb = 0, off_cb = 0, off_rel = 0, off_eps = 0, off_bad = 0, off_ovf = 0, off_scal = 0, off_rows = 0,
-         off_crel = 0, off_gq = 0, off_gi = 0, off_gs = 0, off_f32 = 0, f32_bytes = 0, total = 0;
+         off_crel = 0, off_gq = 0, off_f32 = 0, f32_bytes = 0, total = 0;
 };
-// PMM_F32_SCREEN (read per call): 0 = never, 1 = wherever the limits allow,
-// unset = from kScreenMinWork
-bool screen_enabled(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus) {
-  if (t_no_screen || metric != kMetricCosine || k > kScreenMaxK || !bf16_native(d, k, n)) return false;
+// Whether a call's shape asks for the screen.  PMM_F32_SCREEN (read per call):
+// 0 = never, 1 = wherever the limits allow, unset = from kScreenMinWork.
+bool screen_wanted(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
+  if (metric != kMetricCosine || k > kScreenMaxK || !bf16_native(d, k, n)) return false;
   const char *e = getenv("PMM_F32_SCREEN");
-  if (e && atoi(e) == 0) return false;
-  // (the padded dimension: callers name either d or roundup(d, 32))
+  if (e) return atoi(e) != 0;
   const double work = (double)m * (double)n * (double)(cdiv(d, 32) * 32);
-  if (!e && !(work >= kScreenMinWork || (work >= kScreenMinWorkLongCorpus && n >= 100 * m))) return false;
-  Plan p;
-  plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, p, PMM_COMPUTE_BF16);
-  // the wave-specialised kernel, with room above k for the kept band before
-  // a drain round could pass the segment's end
-  return p.variant == -2 && p.capg <= kBf16WsMaxCapg && p.ctrig >= k + k / 2 + 32 && p.ctrig <= p.capg - 64;
+  return work >= kScreenMinWork || (work >= kScreenMinWorkLongCorpus && n >= 100 * m);
 }
-void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, ScreenPlan &sp) {
+// b: the bf16 kernel's plan of the call (padded D = roundup(d, 128))
+void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, const Plan &b, ScreenPlan &sp) {
   sp.dpb = cdiv(d, kBf16DAlign) * kBf16DAlign;
   sp.dp = cdiv(d, 32) * 32;
-  plan_topk(m, n, sp.dpb, k, metric, cus, sp.b, PMM_COMPUTE_BF16);
-  size_t off = sp.b.total;
+  size_t off = b.total;
   sp.off_qb = off;
   off = al256(off + (size_t)m * sp.dpb * 2);
   sp.off_cb = off;
@@ -747,11 +808,9 @@ void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus
   // re-run: gathered query rows, their lists, and the f32 path's own workspace
   // (sized for the whole call, which an unsafe corpus sends there)
   sp.rr = std::min<int64_t>(m, kScreenRerunRows);
-  sp.off_gq = off;
+  sp.off_gq = off;  // [rows rr x dp | their indices rr x k | their scores rr x k] (rerun_rows' layout)
   off = al256(off + (size_t)sp.rr * sp.dp * 4);
-  sp.off_gi = off;
   off = al256(off + (size_t)sp.rr * k * 4);
-  sp.off_gs = off;
   off = al256(off + (size_t)sp.rr * k * 4);
   sp.off_f32 = off;
   {
@@ -766,199 +825,128 @@ void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus
   sp.total = off + sp.f32_bytes;
 }
 
-int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
-                         int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
-                         uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes,
-                         hipStream_t s, int dev, const float *c_norms, bool keep_gthr, bool allow_screen);
+// ---------------------------------------------------------------------------
+// The route of one fused top-k call, decided once by route_topk.  Sizing
+// (pmm_topk_workspace_bytes), accounting (pmm_topk_merge_bytes) and the
+// executors (topk_f32_device_impl, topk_bf16_device_impl) all read it; none
+// of them decides again.
+// ---------------------------------------------------------------------------
+enum class Route {
+  kF32Fused,         // gemm_f32_kernel + merge
+  kF32Screened,      // bf16 screen + exact f32 re-score (cosine, large)
+  kF32Materialised,  // k > kFusedMaxK: score chunks + row select
+  kBf16Native,       // the bf16 MFMA kernels (wave-specialised or one-wave, by p.variant)
+  kBf16Widened,      // bf16 rows past the bf16 kernels' limits: widened to f32, searched by the f32 path
+};
+struct TopkRoute {
+  Route kind = Route::kF32Fused;
+  // A fused kernel leaves candidates to merge_kernel: every route but the
+  // materialised one and the widened path's inner search at k > kFusedMaxK.
+  bool fused = true;
+  // fused: the plan whose candidate counts the merge reads -- the f32
+  // kernel's, the bf16 kernel's (native, screened) or the widened path's inner
+  // f32 search's
+  Plan p;
+  ScreenPlan sp;  // screened: the workspace behind p
+  MatPlan mp;     // !fused
+  // widened: the f32 images of Q at 0 and of C at off_wc, rows of dpw floats,
+  // and the inner f32 search's workspace at base
+  int64_t dpw = 0;
+  size_t off_wc = 0, base = 0;
+  size_t total = 0;
+};
 
-int topk_f32_screened(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc, int64_t n, int64_t d,
-                      int64_t k, uint32_t index_base, uint32_t *out_idx, float *out_score, void *ws,
-                      size_t ws_bytes, hipStream_t s, int dev) {
-  const int cus = g_dev[dev].cus;
-  const int metric = kMetricCosine;
-  ScreenPlan sp;
-  plan_screen(m, n, d, k, metric, cus, sp);
-  const Plan &p = sp.b;
-  const bool own = !ws;
-  if (!ws) {
-    int rc = arena(dev, s, sp.total, &ws);
-    if (rc) return rc;
-  } else if (ws_bytes < sp.total) {
-    return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, sp.total);
-  }
-  char *w = (char *)ws;
-  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
-  uint16_t *qb = (uint16_t *)(w + sp.off_qb), *cb = (uint16_t *)(w + sp.off_cb);
-  float *rel = (float *)(w + sp.off_rel), *eps = (float *)(w + sp.off_eps);
-  unsigned *bad = (unsigned *)(w + sp.off_bad), *ovf = (unsigned *)(w + sp.off_ovf);
-  unsigned *scal = (unsigned *)(w + sp.off_scal);
-  int *rows = (int *)(w + sp.off_rows);
-  float *crel = (float *)(w + sp.off_crel);
-  HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
-  if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
-  HIP_TRY(hipMemsetAsync(w + sp.off_ovf, 0, sp.off_rows - sp.off_ovf, s));
-  {
-    // the exact norms and factors (norms_rows, as the unscreened path's), then
-    // the bf16 images with the rounding residuals and the unsafe flags
-    Timed t("norms_f32/round", s);
-    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, 0, s));
-    HIP_TRY(launch_screen_round(q, m, d, ldq, qn, qb, sp.dpb, rel, bad, nullptr, s));
-    HIP_TRY(launch_screen_round(c, n, d, ldc, cn, cb, sp.dpb, crel, (unsigned *)(crel + n), scal, s));
-  }
-  GemmF32Args a{};
-  a.qb = qb;
-  a.cb = cb;
-  a.qn = qn;
-  a.cn = cn;
-  a.cpre = cn + n;
-  a.ldq = sp.dpb;
-  a.ldc = sp.dpb;
-  a.M = (int)m;
-  a.N = (int)n;
-  a.D = (int)sp.dpb;
-  a.k = (int)k;
-  a.capg = p.capg;
-  a.ctrig = p.ctrig;
-  a.metric = metric;
-  a.QB = p.QB;
-  a.S = p.S;
-  a.tps = p.tps;
-  a.ntiles = p.T;
-  a.units = p.units;
-  a.counter = (unsigned *)(w + p.off_counter);
-  a.cand = (unsigned long long *)(w + p.off_cand);
-  a.wq = (unsigned long long *)(w + p.off_wq);
-  a.cnt = (unsigned *)(w + p.off_cnt);
-  a.gthr = (unsigned long long *)(w + p.off_gthr);
-  a.nst = 3;
-  a.pf = 1;
-  // (the bf16 path's knobs hold for its kernel here too)
-  static const int defer_env = getenv("PMM_BF16_DEFER") ? atoi(getenv("PMM_BF16_DEFER")) : 1;
-  a.defer = defer_env;
-  a.qb_full = p.qb_full;
-  static const int sync_env = getenv("PMM_BF16_SYNC") ? atoi(getenv("PMM_BF16_SYNC")) : 1;
-  a.round_sync = sync_env;
-  static const int tmo_env = getenv("PMM_BF16_SYNC_TIMEOUT_US") ? atoi(getenv("PMM_BF16_SYNC_TIMEOUT_US")) : 20000;
-  a.sync_timeout = tmo_env * 100;
-  const bool debug = getenv("PMM_SCREEN_DEBUG") != nullptr;
-  a.eps = eps;
-  a.ovf = ovf;
-  {
-    // the bf16 kernel's seed over the images (k-th approximate score of the
-    // first ns columns), lowered by eps into a bound of the exact k-th
-    const int64_t ns = kSeedMaxNs;
-    const int seed_env = getenv("PMM_BF16_SEED") ? atoi(getenv("PMM_BF16_SEED")) : 1;  // (per call)
-    const bool seeded = seed_env && 4 * k <= ns && n >= 8 * ns && (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
-    Timed t("seed_bf16/screen", s);
-    if (seeded) {
-      float *sample = (float *)(w + p.off_cand);
-      HIP_TRY(launch_seed_bf16_ws(a, sample, (int)ns, s));
-      HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
+// allow_screen = false: a caller whose call cannot screen (thresholds carried
+// between corpus chunks, cached corpus norms, per-device shards, the widened
+// bf16 path, the screen's own re-runs); allow_ff = false: the fire-and-forget
+// kernel's re-run.
+// d may arrive already padded (callers name d, roundup(d, 32) or, for bf16,
+// roundup(d, 128)): every decision and size below reads d through one of those
+// roundings, so the route is the same.  The one exception is the widened bf16
+// path, whose f32 rows are roundup(d, 32) wide: a d padded to 128 sizes more.
+TopkRoute route_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int compute, int cus,
+                     bool allow_screen, bool allow_ff) {
+  TopkRoute r;
+  const int64_t dp = cdiv(d, 32) * 32;
+  if (compute == PMM_COMPUTE_BF16) {
+    if (bf16_native(d, k, n)) {
+      r.kind = Route::kBf16Native;
+      plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
+      r.total = r.p.total;
+      return r;
     }
-    HIP_TRY(launch_screen_prep(rel, scal, (int)m, (int)sp.dpb, eps, a.gthr, seeded ? 1 : 0, s));
+    r = route_topk(m, n, dp, k, metric, PMM_COMPUTE_F32, cus, false, false);
+    r.kind = Route::kBf16Widened;
+    r.dpw = dp;
+    r.off_wc = al256((size_t)m * dp * 4);
+    r.base = r.off_wc + al256((size_t)n * dp * 4);
+    r.total += r.base;
+    return r;
   }
-  {
-    Timed t("gemm_f32_topk/screen", s);
-    HIP_TRY(launch_gemm_bf16_ws(a, p.grid, s, true));
+  if (k > kFusedMaxK) {
+    r.kind = Route::kF32Materialised;
+    r.fused = false;
+    plan_materialise(m, n, k, 4, r.mp);
+    r.total = r.mp.total;
+    return r;
   }
-  {
-    Timed t("merge_topk/rescore", s);
-    ScreenFinishArgs fa{};
-    fa.q = q;
-    fa.c = c;
-    fa.ldq = ldq;
-    fa.ldc = ldc;
-    fa.qn = qn;
-    fa.cn = cn;
-    fa.eps = eps;
-    fa.M = (int)m;
-    fa.N = (int)n;
-    fa.dp = (int)sp.dp;
-    fa.S = p.S;
-    fa.capg = p.capg;
-    fa.cand = a.cand;
-    fa.cnt = a.cnt;
-    fa.gthr = a.gthr;
-    fa.stat = debug ? scal + 4 : nullptr;
-    HIP_TRY(launch_screen_rescore(fa, s));
-  }
-  {
-    MergeArgs ma{};
-    ma.cand = a.cand;
-    ma.cnt = a.cnt;
-    ma.gthr = a.gthr;
-    ma.capg = p.capg;
-    ma.M = (int)m;
-    ma.S = p.S;
-    ma.k_out = (int)k;
-    ma.P = p.P;
-    ma.metric = metric;
-    ma.index_base = index_base;
-    ma.out_idx = out_idx;
-    ma.out_score = out_score;
-    Timed t("merge_topk", s);
-    HIP_TRY(launch_merge(ma, 0, s));
-  }
-  HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
-                                  out_score, s));
-  // Rows the screen could not finish (unsafe, or a band that outgrew its
-  // segment) and an unsafe corpus: one read-back, then the f32 kernel.
-  HIP_TRY(launch_screen_collect(ovf, bad, (int)m, scal + 2, rows, s));
-  unsigned h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h, scal, 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  // Many rows to re-run (a crowded corpus: clustered embeddings can fill the
-  // 2 eps band of most rows): one f32 launch over the whole call is cheaper
-  // than serial launches of kScreenRerunRows rows, each of which streams the
-  // corpus for a few query blocks.
-  const bool whole = h[1] != 0 || (int64_t)h[2] * 8 > m + 8 * kScreenRerunRows;
-  if (debug) {
-    float rc;
-    memcpy(&rc, &h[0], 4);
-    fprintf(stderr,
-            "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
-            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld\n",
-            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m);
-  }
-  int rc = PMM_OK;
-  NoScreenScope no_screen;
-  if (whole) {
-    rc = topk_f32_device_impl(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w + sp.off_f32,
-                              sp.f32_bytes, s, dev, nullptr, false, false);
-  } else {
-    float *gq = (float *)(w + sp.off_gq);
-    uint32_t *gi = (uint32_t *)(w + sp.off_gi);
-    float *gs = (float *)(w + sp.off_gs);
-    for (int64_t r0 = 0; r0 < (int64_t)h[2] && rc == PMM_OK; r0 += sp.rr) {
-      const int64_t r = std::min<int64_t>(sp.rr, (int64_t)h[2] - r0);
-      // (a smaller launch may plan more corpus splits: outside the reserved
-      // bytes it takes a buffer of its own)
-      const size_t need = f32_topk_ws_bytes(r, n, sp.dp, k, metric, cus);
-      char *fw = w + sp.off_f32;
-      char *tmp = nullptr;
-      if (need > sp.f32_bytes) {
-        HIP_TRY(hipMalloc(&tmp, need));
-        fw = tmp;
-      }
-      hipError_t e = launch_gather_rows_f32(q, ldq, rows + r0, (int)r, (int)sp.dp, gq, s);
-      if (e == hipSuccess)
-        rc = topk_f32_device_impl(gq, sp.dp, r, c, ldc, n, d, k, metric, index_base, gi, gs, fw, need, s, dev,
-                                  nullptr, false, false);
-      if (e == hipSuccess && rc == PMM_OK) e = launch_scatter_lists(gi, gs, rows + r0, (int)r, (int)k, out_idx, out_score, s);
-      if (tmp) {
-        const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffer is freed)
-        (void)hipFree(tmp);
-        if (e == hipSuccess) e = e2;
-      }
-      if (e != hipSuccess) {
-        return fail(PMM_ERR_HIP, "screen re-run: %s", hipGetErrorString(e));
-      }
+  if (allow_screen && screen_wanted(m, n, d, k, metric)) {
+    // the wave-specialised kernel, with room above k for the kept band before
+    // a drain round could pass the segment's end
+    plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
+    if (r.p.variant == -2 && r.p.capg <= kBf16WsMaxCapg && r.p.ctrig >= k + k / 2 + 32 &&
+        r.p.ctrig <= r.p.capg - 64) {
+      r.kind = Route::kF32Screened;
+      plan_screen(m, n, d, k, metric, cus, r.p, r.sp);
+      r.total = r.sp.total;
+      return r;
     }
+    r.p = Plan();
   }
-  if (rc) return rc;
-  return own ? arena_record(dev, s) : PMM_OK;
+  r.kind = Route::kF32Fused;
+  plan_topk(m, n, dp, k, metric, cus, r.p);
+  r.total = r.p.total;
+  return r;
 }
 
+// Re-runs the query rows listed on the device in rows[0 .. r): gathers them
+// (row_bytes of each, at row stride ld_bytes, both multiples of 16) into a
+// dense block, has run(block, idx, score, ws) search the block into dense
+// r x k lists with a workspace of ws_need bytes, and scatters the lists to the
+// rows' places in out_idx / out_score.  Block, lists and workspace lie in
+// [buf, buf + buf_bytes) when they fit, else in an allocation of the call's
+// own, freed after a stream synchronisation.
+template <typename Run>
+int rerun_rows(const void *q, int64_t ld_bytes, int64_t row_bytes, const int *rows, int64_t r, int64_t k,
+               size_t ws_need, char *buf, size_t buf_bytes, uint32_t *out_idx, float *out_score, hipStream_t s,
+               const char *what, Run run) {
+  const size_t o_i = al256((size_t)r * row_bytes), o_s = o_i + al256((size_t)r * k * 4),
+               o_w = o_s + al256((size_t)r * k * 4);
+  char *tmp = nullptr;
+  hipError_t e = hipSuccess;
+  if (o_w + ws_need > buf_bytes) {
+    e = hipMalloc(&tmp, o_w + ws_need);
+    buf = tmp;
+  }
+  uint32_t *gi = (uint32_t *)(buf + o_i);
+  float *gs = (float *)(buf + o_s);
+  int rc = PMM_OK;
+  if (e == hipSuccess) e = launch_gather_rows(q, ld_bytes / 16, rows, (int)r, (int)(row_bytes / 16), buf, s);
+  if (e == hipSuccess) rc = run(buf, gi, gs, buf + o_w);
+  if (e == hipSuccess && rc == PMM_OK) e = launch_scatter_lists(gi, gs, rows, (int)r, (int)k, out_idx, out_score, s);
+  if (tmp) {
+    const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffer is freed)
+    (void)hipFree(tmp);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return fail(PMM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  return rc;
+}
+
+// The fused route's executor over its acquired workspace w (p.total bytes).
+// d is the logical dimension (norms follow ndarray's order over exactly d
+// elements); the GEMM runs over dp = roundup(d, 32), the rows being
+// zero-padded up to dp.
 // c_norms: optional precomputed corpus norms for `metric` laid out as
 // [n norms | n pre-filter factors] (a pmm_corpus handle's cache); NULL =
 // compute them in this call.
@@ -967,119 +955,99 @@ int topk_f32_screened(const float *q, int64_t ldq, int64_t m, const float *c, in
 // topk_f32_host_chunked); they are kept instead of zeroed, so this chunk
 // only returns what can still enter the top-k (possibly fewer than k per row:
 // the rest are empty slots, which the chunk merge skips).
-int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
-                         int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
-                         uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes,
-                         hipStream_t s, int dev, const float *c_norms = nullptr,
-                         bool keep_gthr = false, bool allow_screen = false) {
-  // d is the logical dimension (norms follow ndarray's order over exactly d
-  // elements); the GEMM runs over dp = roundup(d, 32), the rows being
-  // zero-padded up to dp.
-  const int cus = g_dev[dev].cus;
+int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc, int64_t n,
+                   int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, float *out_score,
+                   char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr) {
   const int64_t dp = cdiv(d, 32) * 32;
-  // allow_screen: the caller sized the workspace with pmm_topk_workspace_bytes
-  if (allow_screen && !c_norms && !keep_gthr && ldq % 4 == 0 && ldc % 4 == 0 && ldq >= dp && ldc >= dp &&
-      !(((uintptr_t)q | (uintptr_t)c) & 15) && screen_enabled(m, n, d, k, metric, cus))
-    return topk_f32_screened(q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, ws, ws_bytes, s, dev);
-  if (k <= kFusedMaxK) {
-    Plan p;
-    plan_topk(m, n, dp, k, metric, cus, p);
-    const bool own = !ws;
-    if (!ws) {
-      int rc = arena(dev, s, p.total, &ws);
+  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
+  if (c_norms) cn = const_cast<float *>(c_norms);
+  // Threshold seeding.  When every unit spans few corpus tiles (small
+  // problems: the reference's own benchmark size), a unit starts cold: its
+  // first tile's scores nearly all survive the pre-filter and are re-scored
+  // exactly, appended and compacted, which took most of the kernel's time.
+  // Instead, the scores of the first ns corpus rows are computed first --
+  // by seed_dots_kernel as fmaf chains in natural K order (bit-identical to
+  // the main pass's MFMA chain and epilogue arithmetic), or, past its
+  // limits or with PMM_SEED_GEMM=1, by the MFMA main loop in store mode into
+  // the still unused candidate buffers -- and one wave per row selects the
+  // k-th best composite of that sample: (that key - 1) is an exact lower
+  // bound of the row's final k-th best and seeds the shared threshold.
+  // Sample size max(256, 8k): at c1 128 / 256 / 512 / 1024 rows measured
+  // 0.170 / 0.163 / 0.174 / 0.192 ms per call (tools/experiments/gpu_seedns.sh).
+  int64_t ns = std::min<int64_t>(n, next_pow2((int)std::max<int64_t>(256, 8 * k), 256));
+  if (const char *ne = getenv("PMM_SEED_NS")) ns = std::min<int64_t>(n, std::max<int64_t>(atoll(ne), k));
+  const char *se = getenv("PMM_SEED");
+  // (only when most query blocks run as split units: a block run whole
+  // carries its threshold across the corpus and gains nothing from the
+  // seed, which costs m * ns * d fmaf on the vector units -- at a c3 shard
+  // of 8, 100k x 125k x 768 with 256 of 391 blocks whole, 9.3 ms for no
+  // GEMM time saved; tools/experiments/shard_shapes.py, profiles/r4_shards/)
+  const bool mostly_split = 2 * (int64_t)p.qb_full < (int64_t)p.QB;
+  bool seed = (se ? atoi(se) != 0
+                  : ((int64_t)p.tps * gemm_f32_bn(p.variant) < 8192 && n >= 4 * ns && mostly_split)) &&
+              ns >= k && ns < n && ns <= kSeedMaxNs && !keep_gthr &&
+              (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
+  GemmF32Args a = fused_args(m, n, dp, k, metric, p, w);
+  a.q = q;
+  a.c = c;
+  a.qn = qn;
+  a.cn = cn;
+  a.cpre = cn + n;
+  a.ldq = ldq;
+  a.ldc = ldc;
+  // Seeded small problems: one prologue launch (seed + norms + fills).
+  const bool one_prologue = seed && dp <= kSeedDotsMaxD && ldq % 4 == 0 && ldc % 4 == 0 &&
+                            !(((uintptr_t)q | (uintptr_t)c | (uintptr_t)w) & 15) && p.off_gthr % 16 == 0 &&
+                            p.off_cnt % 16 == 0 && p.off_cand % 16 == 0 && !getenv("PMM_SEED_GEMM");
+  if (one_prologue) {
+    Timed t("gemm_f32_seed", s);
+    HIP_TRY(launch_seeded_prologue(q, ldq, (int)m, c, ldc, n, (int)d, (int)dp, (int)ns, (int)k, metric, qn, cn,
+                                   !c_norms, a.gthr, w, p.off_gthr, w + p.off_cnt, p.off_cand - p.off_cnt, s));
+  } else {
+    // one fill zeroes the work counters (the main pass's and the seed store
+    // pass's), thresholds and buffer counts [0, off_cand); with the norms
+    // pair kernel the fill rides in the same launch
+    const bool fill_in_norms =
+        metric != kMetricDot && !c_norms && !keep_gthr && p.off_cand % 16 == 0 && ((uintptr_t)w & 15) == 0;
+    if (keep_gthr) {
+      HIP_TRY(hipMemsetAsync(w + p.off_counter, 0, p.off_gthr - p.off_counter, s));
+      HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, p.off_cand - p.off_cnt, s));
+    } else if (!fill_in_norms) {
+      HIP_TRY(hipMemsetAsync(w, 0, p.off_cand, s));
+    }
+    if (metric != kMetricDot) {
+      const int sq = metric == kMetricEuclidean;
+      Timed t("norms_f32", s);
+      if (c_norms) HIP_TRY(launch_norms_f32(q, m, d, ldq, sq, qn, nullptr, s));
+      else HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, sq, s,
+                                         fill_in_norms ? w : nullptr, fill_in_norms ? p.off_cand : 0));
+    }
+    if (seed) {
+      // PMM_SEED_GEMM=1 or outside the one-launch limits: the sample's
+      // scores from the fused kernel's main loop in store mode, then a
+      // select launch
+      float *sample = (float *)a.cand;
+      int rc = gemm_store_f32(q, ldq, m, c, ldc, ns, dp, metric, 1, qn, cn, sample, ns, a.counter + 16, cus, s,
+                              "gemm_f32_seed", true);
       if (rc) return rc;
-    } else if (ws_bytes < p.total) {
-      return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
+      Timed t("seed_select", s);
+      HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
     }
-    char *w = (char *)ws;
-    float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
-    if (c_norms) cn = const_cast<float *>(c_norms);
-    // Threshold seeding.  When every unit spans few corpus tiles (small
-    // problems: the reference's own benchmark size), a unit starts cold: its
-    // first tile's scores nearly all survive the pre-filter and are re-scored
-    // exactly, appended and compacted, which took most of the kernel's time.
-    // Instead, the scores of the first ns corpus rows are computed first --
-    // by seed_dots_kernel as fmaf chains in natural K order (bit-identical to
-    // the main pass's MFMA chain and epilogue arithmetic), or, past its
-    // limits or with PMM_SEED_GEMM=1, by the MFMA main loop in store mode into
-    // the still unused candidate buffers -- and one wave per row selects the
-    // k-th best composite of that sample: (that key - 1) is an exact lower
-    // bound of the row's final k-th best and seeds the shared threshold.
-    // Sample size max(256, 8k): at c1 128 / 256 / 512 / 1024 rows measured
-    // 0.170 / 0.163 / 0.174 / 0.192 ms per call (tools/experiments/gpu_seedns.sh).
-    int64_t ns = std::min<int64_t>(n, next_pow2((int)std::max<int64_t>(256, 8 * k), 256));
-    if (const char *ne = getenv("PMM_SEED_NS")) ns = std::min<int64_t>(n, std::max<int64_t>(atoll(ne), k));
-    const char *se = getenv("PMM_SEED");
-    // (only when most query blocks run as split units: a block run whole
-    // carries its threshold across the corpus and gains nothing from the
-    // seed, which costs m * ns * d fmaf on the vector units -- at a c3 shard
-    // of 8, 100k x 125k x 768 with 256 of 391 blocks whole, 9.3 ms for no
-    // GEMM time saved; tools/experiments/shard_shapes.py, profiles/r4_shards/)
-    const bool mostly_split = 2 * (int64_t)p.qb_full < (int64_t)p.QB;
-    bool seed = (se ? atoi(se) != 0
-                    : ((int64_t)p.tps * gemm_f32_bn(p.variant) < 8192 && n >= 4 * ns && mostly_split)) &&
-                ns >= k && ns < n && ns <= kSeedMaxNs && !keep_gthr &&
-                (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
-    FusedF32 f{q, ldq, m, c, ldc, n, dp, k, metric, qn, cn, cn + n};
-    // Seeded small problems: one prologue launch (seed + norms + fills).
-    const bool one_prologue = seed && dp <= kSeedDotsMaxD && ldq % 4 == 0 && ldc % 4 == 0 &&
-                              !(((uintptr_t)q | (uintptr_t)c | (uintptr_t)w) & 15) && p.off_gthr % 16 == 0 &&
-                              p.off_cnt % 16 == 0 && p.off_cand % 16 == 0 && !getenv("PMM_SEED_GEMM");
-    if (one_prologue) {
-      Timed t("gemm_f32_seed", s);
-      HIP_TRY(launch_seeded_prologue(q, ldq, (int)m, c, ldc, n, (int)d, (int)dp, (int)ns, (int)k, metric, qn, cn,
-                                     !c_norms, (unsigned long long *)(w + p.off_gthr), w, p.off_gthr,
-                                     w + p.off_cnt, p.off_cand - p.off_cnt, s));
-    } else {
-      // one fill zeroes the work counters (the main pass's and the seed store
-      // pass's), thresholds and buffer counts [0, off_cand); with the norms
-      // pair kernel the fill rides in the same launch
-      const bool fill_in_norms =
-          metric != kMetricDot && !c_norms && !keep_gthr && p.off_cand % 16 == 0 && ((uintptr_t)w & 15) == 0;
-      if (keep_gthr) {
-        HIP_TRY(hipMemsetAsync(w + p.off_counter, 0, p.off_gthr - p.off_counter, s));
-        HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, p.off_cand - p.off_cnt, s));
-      } else if (!fill_in_norms) {
-        HIP_TRY(hipMemsetAsync(w, 0, p.off_cand, s));
-      }
-      if (metric != kMetricDot) {
-        const int sq = metric == kMetricEuclidean;
-        Timed t("norms_f32", s);
-        if (c_norms) HIP_TRY(launch_norms_f32(q, m, d, ldq, sq, qn, nullptr, s));
-        else HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, sq, s,
-                                           fill_in_norms ? w : nullptr, fill_in_norms ? p.off_cand : 0));
-      }
-      if (seed) {
-        // PMM_SEED_GEMM=1 or outside the one-launch limits: the sample's
-        // scores from the fused kernel's main loop in store mode, then a
-        // select launch
-        float *sample = (float *)(w + p.off_cand);
-        int rc = gemm_store_f32(q, ldq, m, c, ldc, ns, dp, metric, 1, qn, cn, sample, ns,
-                                (unsigned *)(w + p.off_counter) + 16, cus, s, "gemm_f32_seed", true);
-        if (rc) return rc;
-        Timed t("seed_select", s);
-        HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric,
-                                   (unsigned long long *)(w + p.off_gthr), s));
-      }
-    }
-    HIP_TRY(run_fused_f32(f, p, w, index_base, out_idx, out_score, "gemm_f32_topk", "merge_topk", s));
-    // (not under a keep_gthr chunk merge: its loader re-keys the scores)
-    if (metric == kMetricCosine && !keep_gthr)
-      HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
-                                      out_score, s));
-    return own ? arena_record(dev, s) : PMM_OK;
   }
-  // k beyond the fused path: materialise score chunks, row-select them.
-  MatPlan p;
-  plan_materialise(m, n, k, 4, p);
-  const bool own = !ws;
-  if (!ws) {
-    int rc = arena(dev, s, p.total, &ws);
-    if (rc) return rc;
-  } else if (ws_bytes < p.total) {
-    return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
-  }
-  char *w = (char *)ws;
+  HIP_TRY(run_fused_f32(a, p, index_base, out_idx, out_score, s));
+  // (not under a keep_gthr chunk merge: its loader re-keys the scores)
+  if (metric == kMetricCosine && !keep_gthr)
+    HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
+                                    out_score, s));
+  return PMM_OK;
+}
+
+// The materialised route's executor (k beyond the fused path: score chunks,
+// row-selected) over its acquired workspace w (p.total bytes).
+int topk_f32_materialised(const MatPlan &p, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
+                          int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
+                          float *out_score, char *w, hipStream_t s, int cus, const float *c_norms) {
+  const int64_t dp = cdiv(d, 32) * 32;
   float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
   float *sc = (float *)(w + p.off_scores);
   if (c_norms) cn = const_cast<float *>(c_norms);
@@ -1112,7 +1080,171 @@ int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c,
                                     (int)k, index_base, out_idx + r0 * k, out_score + r0 * k, s));
     }
   }
-  return own ? arena_record(dev, s) : PMM_OK;
+  return PMM_OK;
+}
+
+// The screened route's executor over its acquired workspace w (r.total bytes).
+int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
+                      int64_t n, int64_t d, int64_t k, uint32_t index_base, uint32_t *out_idx, float *out_score,
+                      char *w, hipStream_t s, int cus) {
+  const int metric = kMetricCosine;
+  const ScreenPlan &sp = r.sp;
+  const Plan &p = r.p;
+  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
+  uint16_t *qb = (uint16_t *)(w + sp.off_qb), *cb = (uint16_t *)(w + sp.off_cb);
+  float *rel = (float *)(w + sp.off_rel), *eps = (float *)(w + sp.off_eps);
+  unsigned *bad = (unsigned *)(w + sp.off_bad), *ovf = (unsigned *)(w + sp.off_ovf);
+  unsigned *scal = (unsigned *)(w + sp.off_scal);
+  int *rows = (int *)(w + sp.off_rows);
+  float *crel = (float *)(w + sp.off_crel);
+  HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
+  if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
+  HIP_TRY(hipMemsetAsync(w + sp.off_ovf, 0, sp.off_rows - sp.off_ovf, s));
+  {
+    // the exact norms and factors (norms_rows, as the unscreened path's), then
+    // the bf16 images with the rounding residuals and the unsafe flags
+    Timed t("norms_f32/round", s);
+    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, 0, s));
+    HIP_TRY(launch_screen_round(q, m, d, ldq, qn, qb, sp.dpb, rel, bad, nullptr, s));
+    HIP_TRY(launch_screen_round(c, n, d, ldc, cn, cb, sp.dpb, crel, (unsigned *)(crel + n), scal, s));
+  }
+  GemmF32Args a = fused_args(m, n, sp.dpb, k, metric, p, w);
+  a.qb = qb;
+  a.cb = cb;
+  a.qn = qn;
+  a.cn = cn;
+  a.cpre = cn + n;
+  a.ldq = sp.dpb;
+  a.ldc = sp.dpb;
+  set_bf16_knobs(a);
+  const bool debug = getenv("PMM_SCREEN_DEBUG") != nullptr;
+  a.eps = eps;
+  a.ovf = ovf;
+  {
+    // the bf16 kernel's seed over the images (k-th approximate score of the
+    // first ns columns), lowered by eps into a bound of the exact k-th
+    const int64_t ns = kSeedMaxNs;
+    const int seed_env = getenv("PMM_BF16_SEED") ? atoi(getenv("PMM_BF16_SEED")) : 1;  // (per call)
+    const bool seeded = seed_env && 4 * k <= ns && n >= 8 * ns && (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
+    Timed t("seed_bf16/screen", s);
+    if (seeded) {
+      float *sample = (float *)a.cand;
+      HIP_TRY(launch_seed_bf16_ws(a, sample, (int)ns, s));
+      HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
+    }
+    HIP_TRY(launch_screen_prep(rel, scal, (int)m, (int)sp.dpb, eps, a.gthr, seeded ? 1 : 0, s));
+  }
+  {
+    Timed t("gemm_f32_topk/screen", s);
+    HIP_TRY(launch_gemm_bf16_ws(a, p.grid, s, true));
+  }
+  {
+    Timed t("merge_topk/rescore", s);
+    ScreenFinishArgs fa{};
+    fa.q = q;
+    fa.c = c;
+    fa.ldq = ldq;
+    fa.ldc = ldc;
+    fa.qn = qn;
+    fa.cn = cn;
+    fa.eps = eps;
+    fa.M = (int)m;
+    fa.N = (int)n;
+    fa.dp = (int)sp.dp;
+    fa.S = p.S;
+    fa.capg = p.capg;
+    fa.cand = a.cand;
+    fa.cnt = a.cnt;
+    fa.gthr = a.gthr;
+    fa.stat = debug ? scal + 4 : nullptr;
+    HIP_TRY(launch_screen_rescore(fa, s));
+  }
+  {
+    Timed t("merge_topk", s);
+    HIP_TRY(launch_merge(merge_cand_args(a, p, index_base, out_idx, out_score), 0, s));
+  }
+  HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
+                                  out_score, s));
+  // Rows the screen could not finish (unsafe, or a band that outgrew its
+  // segment) and an unsafe corpus: one read-back, then the f32 kernel.
+  HIP_TRY(launch_screen_collect(ovf, bad, (int)m, scal + 2, rows, s));
+  unsigned h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h, scal, 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // Many rows to re-run (a crowded corpus: clustered embeddings can fill the
+  // 2 eps band of most rows): one f32 launch over the whole call is cheaper
+  // than serial launches of kScreenRerunRows rows, each of which streams the
+  // corpus for a few query blocks.
+  const bool whole = h[1] != 0 || (int64_t)h[2] * 8 > m + 8 * kScreenRerunRows;
+  if (debug) {
+    float rc;
+    memcpy(&rc, &h[0], 4);
+    fprintf(stderr,
+            "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
+            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld\n",
+            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m);
+  }
+  // The f32 kernel's runs never screen (k <= kScreenMaxK: always its fused
+  // route); plan_screen reserved their workspace at off_f32.
+  if (whole) {
+    const TopkRoute f = route_topk(m, n, d, k, metric, PMM_COMPUTE_F32, cus, false, false);
+    return topk_f32_fused(f.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w + sp.off_f32,
+                          s, cus, nullptr, false);
+  }
+  for (int64_t r0 = 0; r0 < (int64_t)h[2]; r0 += sp.rr) {
+    const int64_t nr = std::min<int64_t>(sp.rr, (int64_t)h[2] - r0);
+    // (a smaller launch may plan more corpus splits: outside the reserved
+    // bytes rerun_rows takes a buffer of its own)
+    const TopkRoute f = route_topk(nr, n, d, k, metric, PMM_COMPUTE_F32, cus, false, false);
+    const int rc = rerun_rows(q, ldq * 4, sp.dp * 4, rows + r0, nr, k, f.total, w + sp.off_gq, sp.total - sp.off_gq,
+                              out_idx, out_score, s, "screen re-run",
+                              [&](const char *gq, uint32_t *gi, float *gs, char *fw) {
+                                return topk_f32_fused(f.p, (const float *)gq, sp.dp, nr, c, ldc, n, d, k, metric,
+                                                      index_base, gi, gs, fw, s, cus, nullptr, false);
+                              });
+    if (rc) return rc;
+  }
+  return PMM_OK;
+}
+
+// The f32 kernel's search of a route that does not screen (fused,
+// materialised, or the widened bf16 path's inner search) over workspace w.
+int topk_f32_unscreened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
+                        int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
+                        float *out_score, char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr) {
+  return r.fused ? topk_f32_fused(r.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w, s, cus,
+                                  c_norms, keep_gthr)
+                 : topk_f32_materialised(r.mp, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w,
+                                         s, cus, c_norms);
+}
+
+// Executes an f32 route (route_topk's, for this m, n, d, k, metric) in the
+// caller's workspace, or the arena when ws is NULL.
+int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
+                         int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
+                         float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev,
+                         const float *c_norms = nullptr, bool keep_gthr = false) {
+  const int cus = g_dev[dev].cus;
+  const int64_t dp = cdiv(d, 32) * 32;
+  // What the screen asks of a call and route_topk cannot see (row strides and
+  // alignment of the rows it rounds, norms it computes itself, thresholds it
+  // starts from zero): without it the call takes the unscreened route, whose
+  // workspace the screened one contains (plan_screen reserves it).
+  TopkRoute plain;
+  const TopkRoute *r = &route;
+  if (route.kind == Route::kF32Screened &&
+      (c_norms || keep_gthr || ldq % 4 != 0 || ldc % 4 != 0 || ldq < dp || ldc < dp ||
+       (((uintptr_t)q | (uintptr_t)c) & 15))) {
+    plain = route_topk(m, n, d, k, metric, PMM_COMPUTE_F32, cus, false, false);
+    r = &plain;
+  }
+  Workspace W;
+  if (int rc = acquire_workspace(ws, ws_bytes, r->total, dev, s, W)) return rc;
+  const int rc = r->kind == Route::kF32Screened
+                     ? topk_f32_screened(*r, q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, W.w, s, cus)
+                     : topk_f32_unscreened(*r, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
+                                           W.w, s, cus, c_norms, keep_gthr);
+  return rc ? rc : W.done();
 }
 
 // bf16 compute path over device bf16 rows (row strides ldq / ldc >=
@@ -1127,71 +1259,13 @@ int topk_f32_device_impl(const float *q, int64_t ldq, int64_t m, const float *c,
 // sum (the f32 path's bit-exact chain), so it meets the bf16 bar; the f32
 // MFMA runs at 1/16 of the bf16 rate, which the bench line of such a shape
 // states.
-bool bf16_native(int64_t d, int64_t k, int64_t n) {
-  return cdiv(d, kBf16DAlign) * kBf16DAlign <= kBf16MaxD && n < (int64_t(1) << 27) &&
-         next_pow2((int)std::min<int64_t>(k, 1 << 20) + 64, 128) <= kBf16MaxCapg;
-}
-
-size_t f32_topk_ws_bytes(int64_t m, int64_t n, int64_t dp, int64_t k, int metric, int cus) {
-  if (k <= kFusedMaxK) {
-    Plan p;
-    plan_topk(m, n, dp, k, metric, cus, p);
-    return p.total;
-  }
-  MatPlan p;
-  plan_materialise(m, n, k, 4, p);
-  return p.total;
-}
-
-// workspace of the widened path: the f32 rows, then the f32 search's own
-size_t bf16_widened_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus) {
-  const int64_t dp = cdiv(d, 32) * 32;
-  return al256((size_t)m * dp * 4) + al256((size_t)n * dp * 4) + f32_topk_ws_bytes(m, n, dp, k, metric, cus);
-}
-
-int ff_rerun(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c, int64_t ldc, int64_t n, int64_t d,
-             int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, float *out_score, const unsigned *fb,
-             hipStream_t s, int dev);
-
-int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
-                          int64_t ldc, int64_t n, int64_t d, int64_t k, int metric,
-                          uint32_t index_base, uint32_t *out_idx, float *out_score, void *ws,
-                          size_t ws_bytes, hipStream_t s, int dev) {
-  const int cus = g_dev[dev].cus;
-  if (!bf16_native(d, k, n)) {
-    // widened to f32 and searched by the f32 path (see bf16_native)
-    const int64_t dp32 = cdiv(d, 32) * 32;
-    const size_t oc = al256((size_t)m * dp32 * 4), ow = oc + al256((size_t)n * dp32 * 4);
-    const size_t wsf = f32_topk_ws_bytes(m, n, dp32, k, metric, cus);
-    const bool own = !ws;
-    if (!ws) {
-      int rc = arena(dev, s, ow + wsf, &ws);
-      if (rc) return rc;
-    } else if (ws_bytes < ow + wsf) {
-      return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, ow + wsf);
-    }
-    char *w = (char *)ws;
-    {
-      Timed t("bf16_widen", s);
-      HIP_TRY(launch_bf16_to_f32(q, m, d, ldq, (float *)w, dp32, s));
-      HIP_TRY(launch_bf16_to_f32(c, n, d, ldc, (float *)(w + oc), dp32, s));
-    }
-    int rc = topk_f32_device_impl((const float *)w, dp32, m, (const float *)(w + oc), dp32, n, d, k, metric,
-                                  index_base, out_idx, out_score, w + ow, wsf, s, dev);
-    if (rc) return rc;
-    return own ? arena_record(dev, s) : PMM_OK;
-  }
+//
+// The native route's executor (the bf16 kernel of p.variant + merge) over its
+// acquired workspace w (p.total bytes).
+int topk_bf16_native(const Plan &p, const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c, int64_t ldc,
+                     int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
+                     float *out_score, char *w, hipStream_t s) {
   const int64_t dp = cdiv(d, kBf16DAlign) * kBf16DAlign;
-  Plan p;
-  plan_topk(m, n, dp, k, metric, cus, p, PMM_COMPUTE_BF16);
-  const bool own = !ws;
-  if (!ws) {
-    int rc = arena(dev, s, p.total, &ws);
-    if (rc) return rc;
-  } else if (ws_bytes < p.total) {
-    return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, p.total);
-  }
-  char *w = (char *)ws;
   float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
   HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
   if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
@@ -1201,7 +1275,7 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
     HIP_TRY(launch_norms_bf16(q, m, d, ldq, sq, qn, nullptr, s));
     HIP_TRY(launch_norms_bf16(c, n, d, ldc, sq, cn, cn + n, s));
   }
-  GemmF32Args a{};
+  GemmF32Args a = fused_args(m, n, dp, k, metric, p, w);
   a.qb = q;
   a.cb = c;
   a.qn = qn;
@@ -1209,42 +1283,14 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
   a.cpre = cn + n;
   a.ldq = ldq;
   a.ldc = ldc;
-  a.M = (int)m;
-  a.N = (int)n;
-  a.D = (int)dp;
-  a.k = (int)k;
-  a.capg = p.capg;
-  a.ctrig = p.ctrig;
-  a.metric = metric;
-  a.QB = p.QB;
-  a.S = p.S;
-  a.tps = p.tps;
-  a.ntiles = p.T;
-  a.units = p.units;
-  a.counter = (unsigned *)(w + p.off_counter);
+  set_bf16_knobs(a);
 #ifdef PMM_LAB
   {
     static const int ablate = getenv("PMM_ABLATE") ? atoi(getenv("PMM_ABLATE")) : 0;
     a.ablate = ablate;
   }
 #endif
-  a.cand = (unsigned long long *)(w + p.off_cand);
-  a.wq = (unsigned long long *)(w + p.off_wq);
-  a.cnt = (unsigned *)(w + p.off_cnt);
-  a.gthr = (unsigned long long *)(w + p.off_gthr);
   {
-    a.nst = 3;  // LDS ring slots of the bf16 kernel
-    a.pf = 1;
-    static const int defer_env = getenv("PMM_BF16_DEFER") ? atoi(getenv("PMM_BF16_DEFER")) : 1;
-    a.defer = defer_env;
-    a.qb_full = p.qb_full;
-    static const int sync_env = getenv("PMM_BF16_SYNC") ? atoi(getenv("PMM_BF16_SYNC")) : 1;
-    a.round_sync = sync_env;
-    // round-barrier spin limit: workgroups of one round finish up to a few ms
-    // apart (uneven epilogues); a workgroup that times out stops syncing
-    static const int tmo_env =
-        getenv("PMM_BF16_SYNC_TIMEOUT_US") ? atoi(getenv("PMM_BF16_SYNC_TIMEOUT_US")) : 20000;
-    a.sync_timeout = tmo_env * 100;
 #ifdef PMM_LAB
     static const bool stats = getenv("PMM_STATS") != nullptr;
 #else
@@ -1268,7 +1314,7 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
       if (const char *ne = getenv("PMM_SEED_NS")) ns = std::max<int64_t>(32, std::min<int64_t>(atoll(ne), 4096) / 32 * 32);
       if (seed_env && p.variant == -2 && 4 * k <= ns && n >= 8 * ns &&
           (size_t)m * ns * 4 <= p.off_qn - p.off_cand) {
-        float *sample = (float *)(w + p.off_cand);
+        float *sample = (float *)a.cand;
         Timed t("seed_bf16", s);
         HIP_TRY(launch_seed_bf16_ws(a, sample, (int)ns, s));
         HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
@@ -1280,7 +1326,7 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
       // of an exact ns-row sample, minus 1), the pass, the exact re-score and
       // bucketing into the candidate lists; rows it cannot prove exact are
       // re-run below
-      float *sample = (float *)(w + p.off_cand);
+      float *sample = (float *)a.cand;
       {
         Timed t("seed_bf16", s);
         HIP_TRY(launch_seed_bf16_ws(a, sample, p.ff_ns, s));
@@ -1326,31 +1372,9 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
               h[0], h[1], h[2], h[3], p.units, p.S, p.tps, (double)h[4], (double)h[5], (double)h[6]);
     }
   }
-  MergeArgs ma{};
-  ma.cand = a.cand;
-  ma.cnt = a.cnt;
-  ma.gthr = a.gthr;
-  ma.capg = p.capg;
-  ma.M = (int)m;
-  ma.S = p.S;
-  ma.k_out = (int)k;
-  ma.P = p.P;
-  ma.metric = metric;
-  ma.index_base = index_base;
-  ma.out_idx = out_idx;
-  ma.out_score = out_score;
-  {
-    Timed t("merge_topk", s);
-    HIP_TRY(launch_merge(ma, 0, s));
-  }
-#ifdef PMM_WITH_FF
-  if (p.variant == -6) {
-    int rc = ff_rerun(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
-                      (const unsigned *)(w + p.off_fb), s, dev);
-    if (rc) return rc;
-  }
-#endif
-  return own ? arena_record(dev, s) : PMM_OK;
+  Timed t("merge_topk", s);
+  HIP_TRY(launch_merge(merge_cand_args(a, p, index_base, out_idx, out_score), 0, s));
+  return PMM_OK;
 }
 
 #ifdef PMM_WITH_FF
@@ -1359,47 +1383,59 @@ int topk_bf16_device_impl(const uint16_t *q, int64_t ldq, int64_t m, const uint1
 // their query rows are gathered and re-run on the wave-specialised kernel
 // against the whole corpus, and their lists replace the merge's.  Reads the
 // row count back (a stream synchronisation) and allocates the re-run's
-// buffers itself (hipMalloc, outside the caller's workspace): test-library
-// behaviour only (libpmm_ff.so), never in libpmm.so.  Rare: the guess leaves
-// about n j / ns scores per row against the k needed.
+// buffers itself (rerun_rows without a buffer: hipMalloc, outside the caller's
+// workspace): test-library behaviour only (libpmm_ff.so), never in libpmm.so.
+// Rare: the guess leaves about n j / ns scores per row against the k needed.
 int ff_rerun(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c, int64_t ldc, int64_t n, int64_t d,
              int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, float *out_score, const unsigned *fb,
-             hipStream_t s, int dev) {
+             hipStream_t s, int cus) {
   unsigned nfb = 0;
   HIP_TRY(hipMemcpyAsync(&nfb, fb, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (getenv("PMM_FF_DEBUG")) fprintf(stderr, "[pmm ff] re-run rows %u of %lld\n", nfb, (long long)m);
   if (nfb == 0) return PMM_OK;
-  // one allocation: the gathered rows, their lists, the re-run's workspace;
-  // the row list stays on the device (gather and scatter kernels read it)
-  const int64_t r = nfb;
-  const int *rows = (const int *)(fb + 4);
-  const bool prev = t_no_ff;
-  t_no_ff = true;
-  const int64_t dp = cdiv(d, kBf16DAlign) * kBf16DAlign;
-  const size_t wb = pmm_topk_workspace_bytes(r, n, dp, k, metric, PMM_COMPUTE_BF16);
-  const size_t o_i = al256((size_t)r * ldq * 2), o_s = o_i + al256((size_t)r * k * 4),
-               o_w = o_s + al256((size_t)r * k * 4);
-  char *buf = nullptr;
-  hipError_t e = hipMalloc(&buf, o_w + wb);
-  int rc = PMM_OK;
-  if (e == hipSuccess) e = launch_ff_gather_rows(q, ldq, rows, (int)r, (uint16_t *)buf, s);
-  if (e == hipSuccess)
-    rc = topk_bf16_device_impl((const uint16_t *)buf, ldq, r, c, ldc, n, d, k, metric, index_base,
-                               (uint32_t *)(buf + o_i), (float *)(buf + o_s), buf + o_w, wb, s, dev);
-  if (e == hipSuccess && rc == PMM_OK)
-    e = launch_ff_scatter_lists((const uint32_t *)(buf + o_i), (const float *)(buf + o_s), rows, (int)r, (int)k,
-                                out_idx, out_score, s);
-  t_no_ff = prev;
-  if (buf) {
-    const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffer is freed)
-    (void)hipFree(buf);
-    if (e == hipSuccess) e = e2;
-  }
-  if (e != hipSuccess) return fail(PMM_ERR_HIP, "ff re-run: %s", hipGetErrorString(e));
-  return rc;
+  // the row list stays on the device (gather and scatter kernels read it);
+  // whole rows of ldq elements are gathered, so the block keeps the stride
+  const int64_t nr = nfb;
+  const TopkRoute f = route_topk(nr, n, d, k, metric, PMM_COMPUTE_BF16, cus, false, false);
+  return rerun_rows(q, ldq * 2, ldq * 2, (const int *)(fb + 4), nr, k, f.total, nullptr, 0, out_idx, out_score, s,
+                    "ff re-run", [&](const char *gq, uint32_t *gi, float *gs, char *fw) {
+                      return topk_bf16_native(f.p, (const uint16_t *)gq, ldq, nr, c, ldc, n, d, k, metric, index_base,
+                                              gi, gs, fw, s);
+                    });
 }
 #endif  // PMM_WITH_FF
+
+// Executes a bf16 route (route_topk's, for this m, n, d, k, metric) in the
+// caller's workspace, or the arena when ws is NULL.
+int topk_bf16_device_impl(const TopkRoute &r, const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
+                          int64_t ldc, int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
+                          uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev) {
+  const int cus = g_dev[dev].cus;
+  Workspace W;
+  if (int rc = acquire_workspace(ws, ws_bytes, r.total, dev, s, W)) return rc;
+  char *w = W.w;
+  int rc;
+  if (r.kind == Route::kBf16Widened) {
+    // widened to f32 and searched by the f32 path, which never screens here
+    float *wq = (float *)w, *wc = (float *)(w + r.off_wc);
+    {
+      Timed t("bf16_widen", s);
+      HIP_TRY(launch_bf16_to_f32(q, m, d, ldq, wq, r.dpw, s));
+      HIP_TRY(launch_bf16_to_f32(c, n, d, ldc, wc, r.dpw, s));
+    }
+    rc = topk_f32_unscreened(r, wq, r.dpw, m, wc, r.dpw, n, d, k, metric, index_base, out_idx, out_score, w + r.base,
+                             s, cus, nullptr, false);
+  } else {
+    rc = topk_bf16_native(r.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w, s);
+#ifdef PMM_WITH_FF
+    if (rc == PMM_OK && r.p.variant == -6)
+      rc = ff_rerun(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
+                    (const unsigned *)(w + r.p.off_fb), s, cus);
+#endif
+  }
+  return rc ? rc : W.done();
+}
 
 // Upload a host matrix rows x d into a device buffer with row stride dp,
 // zero-padding columns d..dp-1.
@@ -1414,6 +1450,19 @@ int upload_padded(void *dst, const void *src, int64_t rows, int64_t d, int64_t d
     HIP_TRY(hipMemcpy2DAsync(dst, (size_t)dp * elem, src, (size_t)d * elem, (size_t)d * elem,
                              (size_t)rows, hipMemcpyHostToDevice, s));
   }
+  return PMM_OK;
+}
+
+// The end of a host f32 top-k call: both m x k result lists to the host, and
+// the call's one synchronisation.
+int download_lists(uint32_t *out_idx, float *out_score, const void *idx, const void *score, int64_t m, int64_t k,
+                   hipStream_t s) {
+  {
+    Timed t("d2h", s);
+    HIP_TRY(hipMemcpyAsync(out_idx, idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_score, score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
   return PMM_OK;
 }
 
@@ -1454,14 +1503,17 @@ constexpr int kChunks = 4;
 int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
                           int metric, uint32_t *out_idx, float *out_score, int dev, hipStream_t s) {
   const int64_t dp = cdiv(d, 32) * 32;
-  NoScreenScope no_screen;  // (chunks carry thresholds over: unscreened)
   int64_t bnd[kChunks + 1];
   bnd[0] = 0;
   bnd[1] = std::max<int64_t>(k, n / 16);
   for (int i = 2; i <= kChunks; i++) bnd[i] = bnd[1] + (n - bnd[1]) * (i - 1) / (kChunks - 1);
+  // (chunks carry thresholds over: unscreened)
+  TopkRoute route[kChunks];
   size_t ws_need = 0;
-  for (int i = 0; i < kChunks; i++)
-    ws_need = std::max(ws_need, pmm_topk_workspace_bytes(m, bnd[i + 1] - bnd[i], dp, k, metric, PMM_COMPUTE_F32));
+  for (int i = 0; i < kChunks; i++) {
+    route[i] = route_topk(m, bnd[i + 1] - bnd[i], d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
+    ws_need = std::max(ws_need, route[i].total);
+  }
   const size_t lists = (size_t)kChunks * 2 * m * k * 4;
   size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_l = off_c + al256((size_t)n * dp * 4);
   size_t off_i = off_l + al256(lists), off_s = off_i + al256((size_t)m * k * 4);
@@ -1507,26 +1559,15 @@ int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, 
     if ((rc = upload_padded(b + off_c + (size_t)lo * dp * 4, c + lo * d, rows, d, dp, 4, cs))) return finish(rc);
     CHUNK_TRY(hipEventRecord(ev[i], cs));
     CHUNK_TRY(hipStreamWaitEvent(s, ev[i], 0));
-    rc = topk_f32_device_impl((const float *)(b + off_q), dp, m, (const float *)(b + off_c) + lo * dp, dp,
+    rc = topk_f32_device_impl(route[i], (const float *)(b + off_q), dp, m, (const float *)(b + off_c) + lo * dp, dp,
                               rows, d, k, metric, (uint32_t)lo, li + (size_t)i * 2 * m * k,
                               (float *)(li + (size_t)i * 2 * m * k + (size_t)m * k), b + off_w, ws_need, s,
                               dev, nullptr, i > 0);
     if (rc) return finish(rc);
   }
-  MergeArgs ma{};
-  ma.in_idx = li;
-  ma.in_score = (const float *)(li + (size_t)m * k);
-  ma.k_in = (int)k;
-  ma.row_stride = k;
-  ma.list_stride = 2 * m * k;
-  ma.M = (int)m;
-  ma.S = kChunks;
-  ma.sorted = 1;  // each chunk's lists are a top-k output: best first
-  ma.k_out = (int)k;
-  ma.P = std::min(8192, next_pow2(2 * (int)k + 64, 128));
-  ma.metric = metric;
-  ma.out_idx = (uint32_t *)(b + off_i);
-  ma.out_score = (float *)(b + off_s);
+  // (each chunk's lists are a top-k output: best first)
+  const MergeArgs ma = merge_lists_args(li, (const float *)(li + (size_t)m * k), m, kChunks, k, k, 2 * m * k, k, metric,
+                                        true, (uint32_t *)(b + off_i), (float *)(b + off_s));
   {
     Timed t("merge_chunks", s);
     CHUNK_TRY(launch_merge(ma, 1, s));
@@ -1594,13 +1635,9 @@ struct ShardLayout {
   std::vector<DevPlan> dps;
   std::vector<int> plan_of;  // shard -> index into dps
   std::vector<size_t> off_c, off_cb, off_list;
+  std::vector<TopkRoute> route;        // per shard (never screened)
   size_t off_gather = 0, off_out = 0;  // in the root plan
 };
-
-int device_cus(int dev) {
-  std::lock_guard<std::mutex> lk(g_dev_mu);
-  return (dev >= 0 && dev < kMaxDevices && g_dev[dev].probed) ? g_dev[dev].cus : 256;
-}
 
 void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t k, int metric, int compute,
                   ShardLayout &L) {
@@ -1613,6 +1650,7 @@ void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t
   L.off_c.assign(G, 0);
   L.off_cb.assign(G, 0);
   L.off_list.assign(G, 0);
+  L.route.assign(G, TopkRoute());
   for (int g = 0; g < G; g++) {
     int j = 0;
     while (j < (int)L.dps.size() && L.dps[j].dev != sh[g].dev) j++;
@@ -1631,15 +1669,8 @@ void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t
     off = al256(off + (bf16 ? (size_t)m * dp * 2 : 0));
     for (int g = 0; g < G; g++) {
       if (sh[g].dev != p.dev) continue;
-      size_t need;
-      if (bf16 && !bf16_native(d, k, sh[g].rows)) {
-        need = bf16_widened_bytes(m, sh[g].rows, d, k, metric, device_cus(p.dev));
-      } else {
-        Plan tp;
-        plan_topk(m, sh[g].rows, dp, k, metric, device_cus(p.dev), tp, compute);
-        need = tp.total;
-      }
-      p.ws_bytes = std::max(p.ws_bytes, need);
+      L.route[g] = route_topk(m, sh[g].rows, d, k, metric, compute, device_cus(p.dev), false, true);
+      p.ws_bytes = std::max(p.ws_bytes, L.route[g].total);
       L.off_c[g] = off;
       if (sh[g].host) off = al256(off + (size_t)sh[g].rows * (bf16 ? d : dp) * 4);
       L.off_cb[g] = off;
@@ -1735,7 +1766,7 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
       SH_TRY(hipMemcpyAsync(p.base + off_c[g], x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
       SH_TRY(launch_f32_to_bf16((const float *)(p.base + off_c[g]), x.rows, d, d,
                                 (uint16_t *)(p.base + off_cb[g]), dp, p.s));
-      SH_RC(topk_bf16_device_impl((const uint16_t *)(p.base + p.off_qb), dp, m,
+      SH_RC(topk_bf16_device_impl(L.route[g], (const uint16_t *)(p.base + p.off_qb), dp, m,
                                   (const uint16_t *)(p.base + off_cb[g]), dp, x.rows, d, k, metric,
                                   (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev));
     } else {
@@ -1744,7 +1775,7 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
         SH_RC(upload_padded(p.base + off_c[g], x.host, x.rows, d, dp, 4, p.s));
         c = (const float *)(p.base + off_c[g]);
       }
-      SH_RC(topk_f32_device_impl((const float *)(p.base + p.off_q), dp, m, c, dp, x.rows, d, k, metric,
+      SH_RC(topk_f32_device_impl(L.route[g], (const float *)(p.base + p.off_q), dp, m, c, dp, x.rows, d, k, metric,
                                  (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev,
                                  x.host ? nullptr : x.dev_norms));
     }
@@ -1759,20 +1790,10 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
     SH_TRY(hipMemcpyPeerAsync(gb + (size_t)g * list_bytes, root, dps[plan_of[g]].base + off_list[g], sh[g].dev,
                               list_bytes, rp.s));
   }
-  MergeArgs ma{};
-  ma.in_idx = (const uint32_t *)gb;
-  ma.in_score = (const float *)((const uint32_t *)gb + (size_t)m * k);
-  ma.k_in = (int)k;
-  ma.row_stride = k;
-  ma.list_stride = 2 * m * k;
-  ma.M = (int)m;
-  ma.S = G;
-  ma.sorted = 1;  // each shard's lists are a top-k output: best first
-  ma.k_out = (int)k;
-  ma.P = std::min(8192, next_pow2(2 * (int)k + 64, 128));
-  ma.metric = metric;
-  ma.out_idx = (uint32_t *)(rp.base + off_out);
-  ma.out_score = (float *)(ma.out_idx + (size_t)m * k);
+  // (each shard's lists are a top-k output: best first)
+  uint32_t *oi = (uint32_t *)(rp.base + off_out);
+  const MergeArgs ma = merge_lists_args((const uint32_t *)gb, (const float *)((const uint32_t *)gb + (size_t)m * k), m,
+                                        G, k, k, 2 * m * k, k, metric, true, oi, (float *)(oi + (size_t)m * k));
   {
     Timed t("merge_devices", rp.s);
     SH_TRY(launch_merge(ma, 1, rp.s));
@@ -2372,31 +2393,9 @@ int pmm_get_devices(int *ids, int cap, int *n) {
 
 size_t pmm_topk_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int metric,
                                 int compute) {
-  int cus = 256;
   int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    if (dev >= 0 && dev < kMaxDevices && g_dev[dev].probed) cus = g_dev[dev].cus;
-  }
-  if (compute == PMM_COMPUTE_BF16) {
-    if (!bf16_native(d, k, n)) return bf16_widened_bytes(m, n, d, k, metric, cus);
-    Plan p;
-    plan_topk(m, n, d, k, metric, cus, p, PMM_COMPUTE_BF16);
-    return p.total;
-  }
-  if (k <= kFusedMaxK) {
-    if (screen_enabled(m, n, d, k, metric, cus)) {
-      ScreenPlan sp;
-      plan_screen(m, n, d, k, metric, cus, sp);
-      return sp.total;
-    }
-    Plan p;
-    plan_topk(m, n, d, k, metric, cus, p);
-    return p.total;
-  }
-  MatPlan p;
-  plan_materialise(m, n, k, 4, p);
-  return p.total;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? device_cus(dev) : 256;
+  return route_topk(m, n, d, k, metric, compute, cus, true, true).total;
 }
 
 int pmm_topk_merge_bytes(const void *workspace, int64_t m, int64_t n, int64_t d, int64_t k,
@@ -2404,36 +2403,19 @@ int pmm_topk_merge_bytes(const void *workspace, int64_t m, int64_t n, int64_t d,
   if (!bytes) return fail(PMM_ERR_ARG, "null output");
   *bytes = 0;
   if (m <= 0 || k <= 0) return PMM_OK;
-  if (compute != PMM_COMPUTE_BF16 && k > kFusedMaxK)
+  if (k > kFusedMaxK)
     return fail(PMM_ERR_UNSUPPORTED, "no merge pass on the materialised path (k > %d)", kFusedMaxK);
   int dev;
   int rc = ensure_device(&dev);
   if (rc) return rc;
-  int cus = 256;
-  {
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    if (dev >= 0 && dev < kMaxDevices && g_dev[dev].probed) cus = g_dev[dev].cus;
-  }
-  // the counts sit at the offsets of the layout the call used: the bf16 plan
-  // (a bf16 call, or the screened f32 path), the f32 plan behind the widened
-  // rows (a bf16 call past the bf16 kernels' limits), or the f32 plan
-  Plan p;
-  size_t base = 0;
-  uint64_t row_bytes = 0;  // screened path: f32 bytes gathered per re-scored candidate
-  if (compute == PMM_COMPUTE_BF16 && !bf16_native(d, k, n)) {
-    if (k > kFusedMaxK)
-      return fail(PMM_ERR_UNSUPPORTED, "no merge pass on the materialised path (k > %d)", kFusedMaxK);
-    const int64_t dp32 = cdiv(d, 32) * 32;
-    base = al256((size_t)m * dp32 * 4) + al256((size_t)n * dp32 * 4);
-    plan_topk(m, n, dp32, k, metric, cus, p, PMM_COMPUTE_F32);
-  } else if (compute != PMM_COMPUTE_BF16 && screen_enabled(m, n, d, k, metric, cus)) {
-    ScreenPlan sp;
-    plan_screen(m, n, d, k, metric, cus, sp);
-    p = sp.b;
-    row_bytes = (uint64_t)sp.dp * 4;
-  } else {
-    plan_topk(m, n, d, k, metric, cus, p, compute);
-  }
+  // the counts sit at the offsets of the layout the call used: the route's
+  // plan (at `base` behind the widened rows of a bf16 call past the bf16
+  // kernels' limits)
+  const TopkRoute r = route_topk(m, n, d, k, metric, compute, device_cus(dev), true, true);
+  const Plan &p = r.p;
+  const size_t base = r.base;
+  // screened path: f32 bytes gathered per re-scored candidate
+  const uint64_t row_bytes = r.kind == Route::kF32Screened ? (uint64_t)r.sp.dp * 4 : 0;
   // the merge reads every row's split counts and shared threshold, the
   // candidates the GEMM left, and writes the m x k (index, score) lists; the
   // screened path's exact finish also reads and rewrites every candidate the
@@ -2475,8 +2457,8 @@ int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, 
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
-  return topk_f32_device_impl(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
-                              workspace, workspace_bytes, s, dev, nullptr, false, true);
+  return topk_f32_device_impl(route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true), q, ldq, m, c, ldc,
+                              n, d, k, metric, index_base, out_idx, out_score, workspace, workspace_bytes, s, dev);
 }
 
 int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
@@ -2512,7 +2494,8 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
   if (compute == PMM_COMPUTE_BF16) {
     // f32 rows uploaded as they are, rounded to zero-padded bf16 rows on device
     const int64_t db = cdiv(d, kBf16DAlign) * kBf16DAlign;
-    size_t ws_need = pmm_topk_workspace_bytes(m, n, db, k, metric, compute);
+    const TopkRoute route = route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true);
+    const size_t ws_need = route.total;
     size_t off_qf = 0, off_cf = al256((size_t)m * d * 4);
     size_t off_qb = off_cf + al256((size_t)n * d * 4), off_cb = off_qb + al256((size_t)m * db * 2);
     size_t off_i = off_cb + al256((size_t)n * db * 2), off_s = off_i + al256((size_t)m * k * 4);
@@ -2524,17 +2507,11 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     HIP_TRY(hipMemcpyAsync(b + off_cf, c, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_f32_to_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db, s));
     HIP_TRY(launch_f32_to_bf16((const float *)(b + off_cf), n, d, d, (uint16_t *)(b + off_cb), db, s));
-    rc = topk_bf16_device_impl((const uint16_t *)(b + off_qb), db, m, (const uint16_t *)(b + off_cb),
+    rc = topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, (const uint16_t *)(b + off_cb),
                                db, n, d, k, metric, 0u, (uint32_t *)(b + off_i),
                                (float *)(b + off_s), b + off_w, ws_need, s, dev);
     if (rc) return rc;
-    {
-      Timed t("d2h", s);
-      HIP_TRY(hipMemcpyAsync(out_idx, b + off_i, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(out_score, b + off_s, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return PMM_OK;
+    return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
   }
   const int64_t dp = cdiv(d, 32) * 32;
   {
@@ -2542,7 +2519,8 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     if (k <= kFusedMaxK && (size_t)n * dp * 4 >= kChunkedMinBytes && n >= 64 * k && !(ce && atoi(ce) == 0))
       return topk_f32_host_chunked(q, m, c, n, d, k, metric, out_idx, out_score, dev, s);
   }
-  size_t ws_need = pmm_topk_workspace_bytes(m, n, dp, k, metric, compute);
+  const TopkRoute route = route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true);
+  const size_t ws_need = route.total;
   size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_i = off_c + al256((size_t)n * dp * 4);
   size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
   void *base;
@@ -2550,17 +2528,11 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
   char *b = (char *)base;
   if ((rc = upload_padded(b + off_q, q, m, d, dp, 4, s))) return rc;
   if ((rc = upload_padded(b + off_c, c, n, d, dp, 4, s))) return rc;
-  rc = topk_f32_device_impl((const float *)(b + off_q), dp, m, (const float *)(b + off_c), dp, n,
+  rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, (const float *)(b + off_c), dp, n,
                             d, k, metric, 0u, (uint32_t *)(b + off_i), (float *)(b + off_s),
-                            b + off_w, ws_need, s, dev, nullptr, false, true);
+                            b + off_w, ws_need, s, dev);
   if (rc) return rc;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, b + off_i, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, b + off_s, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return PMM_OK;
+  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
 }
 
 int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
@@ -2585,8 +2557,9 @@ int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
-  return topk_bf16_device_impl(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
-                               workspace, workspace_bytes, s, dev);
+  return topk_bf16_device_impl(route_topk(m, n, d, k, metric, PMM_COMPUTE_BF16, g_dev[dev].cus, true, true), q, ldq, m,
+                               c, ldc, n, d, k, metric, index_base, out_idx, out_score, workspace, workspace_bytes,
+                               s, dev);
 }
 
 int pmm_topk_f32(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
@@ -2803,20 +2776,8 @@ static int merge_strided(const uint32_t *idx, const float *score, int64_t m, int
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
-  MergeArgs ma{};
-  ma.in_idx = idx;
-  ma.in_score = score;
-  ma.k_in = (int)k_in;
-  ma.row_stride = row_stride;
-  ma.list_stride = list_stride;
-  ma.M = (int)m;
-  ma.S = (int)lists;
-  ma.sorted = sorted ? 1 : 0;
-  ma.k_out = (int)k_out;
-  ma.P = std::min(8192, next_pow2(2 * (int)k_out + 64, 128));
-  ma.metric = metric;
-  ma.out_idx = out_idx;
-  ma.out_score = out_score;
+  const MergeArgs ma = merge_lists_args(idx, score, m, lists, k_in, row_stride, list_stride, k_out, metric, sorted,
+                                        out_idx, out_score);
   Timed t("merge_shards", s);
   HIP_TRY(launch_merge(ma, 1, s));
   return PMM_OK;
@@ -3057,25 +3018,20 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = h->dp;
-  NoScreenScope no_screen;  // (cached corpus norms: unscreened)
-  size_t ws_need = pmm_topk_workspace_bytes(m, h->n, dp, k, metric, PMM_COMPUTE_F32);
+  // (cached corpus norms: unscreened)
+  const TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
+  const size_t ws_need = route.total;
   size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
   size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
   void *base;
   if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
   char *b = (char *)base;
   if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 4, s))) return rc;
-  rc = topk_f32_device_impl((const float *)(b + off_q), dp, m, x.data, dp, h->n, h->d, k, metric,
+  rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.data, dp, h->n, h->d, k, metric,
                             0u, (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need,
                             s, dev, shard_norms(x));
   if (rc) return rc;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, b + off_i, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, b + off_s, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return PMM_OK;
+  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
 }
 
 int pmm_timing_enable(int enable) {

@@ -179,10 +179,6 @@ hipError_t launch_gemm_bf16_ff(const GemmF32Args &a, int grid, hipStream_t s);
 // block, wave); rows whose lists overflowed, whose region overflowed or that
 // kept fewer than k candidates at or above their threshold go to fb_rows
 // (*fb_count of them) for a re-run.
-hipError_t launch_ff_gather_rows(const uint16_t *q, int64_t ldq, const int *rows, int r, uint16_t *dst,
-                                 hipStream_t s);
-hipError_t launch_ff_scatter_lists(const uint32_t *oi, const float *os, const int *rows, int r, int k,
-                                   uint32_t *out_idx, float *out_score, hipStream_t s);
 hipError_t launch_ff_bucket(const GemmF32Args &a, unsigned *fb_count, int *fb_rows, hipStream_t s);
 // f32 rows -> bf16 (round to nearest even) with row stride ldd, columns
 // d..ldd-1 zero-filled.
@@ -229,8 +225,12 @@ hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m
 hipError_t launch_zero_sign_cosine(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
                                    const float *cn, int m, int64_t n, int d, int k, uint32_t index_base,
                                    const uint32_t *out_idx, float *out_score, hipStream_t s);
-hipError_t launch_gather_rows_f32(const float *q, int64_t ldq, const int *rows, int r, int dp, float *dst,
-                                  hipStream_t s);
+// ---- re-runs of listed rows (the screen's, the ff kernel's) ----
+// dst row i (units 16-byte units, dense) = src row rows[i] (row stride
+// ld_units 16-byte units); both 16-byte aligned
+hipError_t launch_gather_rows(const void *src, int64_t ld_units, const int *rows, int r, int units, void *dst,
+                              hipStream_t s);
+// out_idx / out_score row rows[i] = the dense lists' row i (k entries each)
 hipError_t launch_scatter_lists(const uint32_t *oi, const float *os, const int *rows, int r, int k,
                                 uint32_t *out_idx, float *out_score, hipStream_t s);
 hipError_t launch_gemm_f64_store(const double *q, int64_t ldq, const double *c, int64_t ldc,

@@ -2652,18 +2652,22 @@ hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float *__restrict__ q, int64_t ldq,
-                                                              const int *__restrict__ rows, int r, int dp,
-                                                              float *__restrict__ dst) {
+// A re-run's row gather (the rows listed in rows[0..r) into a dense block, in
+// 16-byte units: f32 and bf16 rows alike) and list scatter (the re-run's lists
+// back to those rows).
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4 *__restrict__ src, int64_t ld,
+                                                          const int *__restrict__ rows, int r, int units,
+                                                          uint4 *__restrict__ dst) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)r * dp) return;
-  const int i = (int)(t / dp), c = (int)(t - (int64_t)i * dp);
-  dst[t] = q[(int64_t)rows[i] * ldq + c];
+  if (t >= (int64_t)r * units) return;
+  const int i = (int)(t / units), c = (int)(t - (int64_t)i * units);
+  dst[t] = src[(int64_t)rows[i] * ld + c];
 }
-hipError_t launch_gather_rows_f32(const float *q, int64_t ldq, const int *rows, int r, int dp, float *dst,
-                                  hipStream_t s) {
-  if (r <= 0) return hipSuccess;
-  gather_rows_f32_kernel<<<(unsigned)(((int64_t)r * dp + 255) / 256), 256, 0, s>>>(q, ldq, rows, r, dp, dst);
+hipError_t launch_gather_rows(const void *src, int64_t ld_units, const int *rows, int r, int units, void *dst,
+                              hipStream_t s) {
+  if (r <= 0 || units <= 0) return hipSuccess;
+  gather_rows_kernel<<<(unsigned)(((int64_t)r * units + 255) / 256), 256, 0, s>>>((const uint4 *)src, ld_units, rows,
+                                                                                  r, units, (uint4 *)dst);
   return hipGetLastError();
 }
 __global__ __launch_bounds__(256) void scatter_lists_kernel(const uint32_t *__restrict__ oi,
