@@ -243,6 +243,26 @@ int pmm_norms_f32_device(const float *a, int64_t ld, int64_t rows, int64_t d, in
 int pmm_norms_f64_device(const double *a, int64_t ld, int64_t rows, int64_t d, int squared,
                          double *out, void *stream);
 
+/* f32 device rows rounded to bf16 and, in the same pass, their norms: what a
+ * caller holding f32 rows needs before pmm_topk_bf16_device (and what
+ * pmm_corpus_create_bf16 / pmm_topk_bf16_corpus run).  a has `rows` rows of
+ * stride ld >= d floats (any alignment; 16-byte loads when a is 16-byte
+ * aligned and ld a multiple of 4).  out takes the bf16 bit patterns at row
+ * stride ldo >= d, a multiple of 8 (roundup(d, 128) for the top-k entry),
+ * 16-byte-aligned base; columns d..ldo-1 are written as zero.  Rounding is to
+ * nearest even, NaN stays NaN.  Each of the four per-row arrays may be NULL
+ * (skipped): norm = sqrt(sum), inv_norm = norm > 1e-6 ? 1 / norm : 0 (the
+ * cosine pre-filter factor with the reference's zero-norm rule), sq = sum,
+ * sq_factor = sum * (1 - 2^-18) (the euclidean pre-filter factor), all from
+ * one sum of squares of the ROUNDED values in ndarray's unrolled_dot order
+ * with no FMA contraction: bit-equal to pmm_norms_f32_device on the rounded
+ * rows widened to f32, and to the norms the bf16 top-k computes itself.  One
+ * launch; every f32 element is read once and every bf16 element written once
+ * (6 bytes per element).  No reference counterpart. */
+int pmm_round_bf16_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out,
+                          int64_t ldo, float *norm, float *inv_norm, float *sq, float *sq_factor,
+                          void *stream);
+
 /* k-way merge of per-shard top-k lists: idx/score are [m][lists][k_in] (the
  * lists in any order; idx 0xFFFFFFFF marks an empty slot).  Writes the best k_out of each row to out_idx/out_score
  * [m][k_out].  This is the merge step after the RCCL gather of the
@@ -286,19 +306,31 @@ int pmm_merge_sorted_topk_strided_device(const uint32_t *idx, const float *score
  * the device list (pmm_set_devices) in effect then.  Its row type is fixed at
  * creation: an f32 handle serves pmm_topk_f32_corpus (the reference's f32
  * branch, src/matmul.rs:429-448), an f64 handle pmm_topk_f64_corpus (the f64
- * branch, src/matmul.rs:449-468 -- what Polars' default Float64 columns take).
+ * branch, src/matmul.rs:449-468 -- what Polars' default Float64 columns take),
+ * a bf16 handle pmm_topk_bf16_corpus (PMM_COMPUTE_BF16 of pmm_topk_f32_ex, no
+ * reference counterpart).
  * ------------------------------------------------------------------------- */
 typedef struct pmm_corpus pmm_corpus;
 
 #define PMM_DTYPE_F32 0
 #define PMM_DTYPE_F64 1
+#define PMM_DTYPE_BF16 2
 
 int pmm_corpus_create_f32(const float *c, int64_t n, int64_t d, pmm_corpus **out);
 /* An f64 corpus: rows kept in f64 (stride roundup(d, 16), zero-padded) with
  * their f64 norms of both metrics; with pmm_set_devices in effect, row-sharded
  * over the list like an f32 corpus (pmm_topk_f64_corpus merges the shards). */
 int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **out);
-/* PMM_DTYPE_F32 or PMM_DTYPE_F64. */
+/* A bf16 corpus: host f32 rows in; per shard the rows are uploaded and one
+ * pass (pmm_round_bf16_device's kernel) leaves the rows rounded to bf16 at
+ * stride roundup(d, 128), zero-padded, and the f32 norms of the rounded rows
+ * for both metrics (norm, 1 / norm, squared norm, squared norm * (1 - 2^-18):
+ * 16 bytes per row).  The f32 staging is freed before the call returns, so a
+ * handle holds n * roundup(d, 128) * 2 + 16 n bytes: half an f32 handle's
+ * rows.  Sharded over a device list like an f32 corpus; the f32 creator's
+ * argument errors and texts. */
+int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **out);
+/* PMM_DTYPE_F32, PMM_DTYPE_F64 or PMM_DTYPE_BF16. */
 int pmm_corpus_dtype(const pmm_corpus *corpus, int *dtype);
 int pmm_corpus_destroy(pmm_corpus *corpus);
 int pmm_corpus_info(const pmm_corpus *corpus, int64_t *n, int64_t *d, int *device);
@@ -319,6 +351,22 @@ int pmm_topk_f32_corpus(const pmm_corpus *corpus, const float *q, int64_t m, int
  * pmm_topk_f32_corpus refuses an f64 handle the same way). */
 int pmm_topk_f64_corpus(const pmm_corpus *corpus, const double *q, int64_t m, int64_t k,
                         int metric, uint32_t *out_idx, double *out_score);
+
+/* pmm_topk_f32_ex(..., PMM_COMPUTE_BF16) against a bf16 corpus handle (host
+ * f32 queries in, host results out, f32 scores; 0 <= k <= n).  On one device
+ * the queries are uploaded and rounded by one pass that also writes the
+ * metric's query norms (none for dot), and the search takes the route the host
+ * entry takes with the handle's norms: no corpus upload, rounding or norms
+ * per call.  The results equal pmm_topk_f32_ex(..., PMM_COMPUTE_BF16)'s bit
+ * for bit (indices and scores), the widened route past d > 768 or k > 960
+ * included (there the norms are recomputed from the widened rows, the same
+ * values).  A sharded handle serves k <= 1024 (else PMM_ERR_UNSUPPORTED, as an
+ * f32 handle) and equals the host entry under the same device list.  An f32
+ * or f64 handle: PMM_ERR_ARG naming the entry that serves it (and
+ * pmm_topk_f32_corpus / pmm_topk_f64_corpus refuse a bf16 handle the same
+ * way). */
+int pmm_topk_bf16_corpus(const pmm_corpus *corpus, const float *q, int64_t m, int64_t k,
+                         int metric, uint32_t *out_idx, float *out_score);
 
 /* Per-kernel timing on the launch stream (hipEvents around each launch).
  * enable=1 starts recording; pmm_timing_read returns the summed milliseconds

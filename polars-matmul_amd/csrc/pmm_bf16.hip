@@ -57,6 +57,121 @@ hipError_t launch_f32_to_bf16(const float *src, int64_t rows, int64_t d, int64_t
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// f32 -> bf16 with zero padding AND the rows' norms of both metrics, one pass:
+// what f32_to_bf16_kernel + norms_kernel<float, __bf16> (squared = 0 and 1)
+// give in three launches and 10 bytes of HBM traffic per element, in one and 6.
+//
+// A workgroup takes a band of kRnRows rows, kRnCols columns at a time.  Every
+// thread rounds groups of 8 columns (two 16-byte loads where the source
+// allows, one 16-byte store) and parks the rounded group in LDS; then 8 lanes
+// per row walk the chunk out of LDS in norms_rows' order -- lane j owns the
+// partial sum of columns j, j + 8, ... -- carrying the partial over the
+// chunks, so any d works.  The combine, the tail columns d8..d-1 and the
+// factors are norms_rows' statements (no FMA: -ffp-contract=off).
+// ---------------------------------------------------------------------------
+constexpr int kRnRows = 32;    // rows per workgroup: 256 threads / 8 lanes per row
+constexpr int kRnCols = 256;   // columns per chunk
+constexpr int kRnLd = kRnCols + 8;  // LDS row stride (bf16): 8 rows of a wave land 4 banks apart
+
+__global__ __launch_bounds__(256) void round_norms_bf16_kernel(const float *__restrict__ src, int64_t rows,
+                                                               int64_t d, int64_t lds, uint16_t *__restrict__ dst,
+                                                               int64_t ldd, float *__restrict__ norm,
+                                                               float *__restrict__ inv_norm, float *__restrict__ sq,
+                                                               float *__restrict__ sq_factor, int vec) {
+  __shared__ __attribute__((aligned(16))) __bf16 park[kRnRows * kRnLd];
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kRnRows;
+  const int nrows = (int)((rows - row0) < kRnRows ? (rows - row0) : kRnRows);
+  const int64_t d8 = d & ~(int64_t)7;
+  const int my = tid >> 3, j = tid & 7;  // norm phase: lane j of band row my
+  float acc = 0.0f;
+  float tail[7];
+#pragma unroll
+  for (int t = 0; t < 7; t++) tail[t] = 0.0f;
+  for (int64_t cb = 0; cb < ldd; cb += kRnCols) {
+    const int cw = (int)((ldd - cb) < kRnCols ? (ldd - cb) : kRnCols);  // a multiple of 8
+    const int gpr = cw >> 3;                                             // 8-column groups per row
+    for (int g = tid; g < nrows * gpr; g += 256) {
+      const int r = g / gpr;
+      const int cl = (g - r * gpr) * 8;
+      const int64_t c0 = cb + cl;
+      const float *p = src + (row0 + r) * lds + c0;
+      float x[8];
+      if (vec && c0 + 8 <= d) {
+        const float4 lo = *(const float4 *)p, hi = *(const float4 *)(p + 4);
+        x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w;
+        x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
+      } else {
+#pragma unroll
+        for (int u = 0; u < 8; u++) x[u] = (c0 + u < d) ? p[u] : 0.0f;
+      }
+      bf16x8 v;
+      // plain cast, as f32_to_bf16_kernel: round to nearest even, NaN stays NaN
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = (__bf16)x[u];
+      *(bf16x8 *)(dst + (row0 + r) * ldd + c0) = v;
+      *(bf16x8 *)(park + r * kRnLd + cl) = v;
+    }
+    __syncthreads();
+    if (my < nrows && cb < d) {
+      const __bf16 *pr = park + my * kRnLd;
+      const int lim = (int)((d8 - cb) < cw ? (d8 - cb) : cw);  // columns of this chunk below d8
+      int i = j;
+      for (; i + 56 < lim; i += 64) {
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) x[u] = (float)pr[i + 8 * u];
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc = acc + x[u] * x[u];
+      }
+      for (; i < lim; i += 8) {
+        const float x = (float)pr[i];
+        acc = acc + x * x;
+      }
+      // the tail columns d8..d-1 lie in one chunk: lane 0 keeps them for the end
+      if (j == 0 && d8 < d && d8 >= cb && d8 < cb + cw) {
+#pragma unroll
+        for (int t = 0; t < 7; t++)
+          if (d8 + t < d) tail[t] = (float)pr[(int)(d8 - cb) + t];
+      }
+    }
+    __syncthreads();
+  }
+  const int base = (tid & 63) & ~7;
+  float pp[8];
+#pragma unroll
+  for (int t = 0; t < 8; t++) pp[t] = __shfl(acc, base + t, 64);
+  if (my < nrows && j == 0) {
+    float sum = 0.0f;
+    sum = sum + (pp[0] + pp[4]);
+    sum = sum + (pp[1] + pp[5]);
+    sum = sum + (pp[2] + pp[6]);
+    sum = sum + (pp[3] + pp[7]);
+#pragma unroll
+    for (int t = 0; t < 7; t++)
+      if (d8 + t < d) sum = sum + tail[t] * tail[t];
+    const int64_t row = row0 + my;
+    const float v = sqrt_rn<float>(sum);
+    if (norm) norm[row] = v;
+    if (inv_norm) inv_norm[row] = (v > 1e-6f) ? 1.0f / v : 0.0f;
+    if (sq) sq[row] = sum;
+    if (sq_factor) sq_factor[row] = sum * (float)(1.0 - 0x1p-18);
+  }
+}
+
+hipError_t launch_round_norms_bf16(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst,
+                                   int64_t ldd, float *norm, float *inv_norm, float *sq, float *sq_factor,
+                                   hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (ldd < d || ldd % 8 != 0 || lds < d || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+  const int vec = (((uintptr_t)src & 15) == 0 && lds % 4 == 0) ? 1 : 0;
+  const int64_t grid = (rows + kRnRows - 1) / kRnRows;
+  round_norms_bf16_kernel<<<(unsigned)grid, 256, 0, s>>>(src, rows, d, lds, dst, ldd, norm, inv_norm, sq, sq_factor,
+                                                         vec);
+  return hipGetLastError();
+}
+
 // bf16 -> f32 (exact widening) with zero padding to ldd: one thread per element
 __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const uint16_t *__restrict__ src, int64_t rows,
                                                           int64_t d, int64_t lds, float *__restrict__ dst,

@@ -1264,16 +1264,22 @@ int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, in
 // acquired workspace w (p.total bytes).
 int topk_bf16_native(const Plan &p, const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c, int64_t ldc,
                      int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
-                     float *out_score, char *w, hipStream_t s) {
+                     float *out_score, char *w, hipStream_t s, const float *q_norms = nullptr,
+                     const float *c_norms = nullptr) {
   const int64_t dp = cdiv(d, kBf16DAlign) * kBf16DAlign;
-  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
+  // the precomputed arrays live outside w (a bf16 corpus handle's, and the
+  // query norms its call's rounding pass wrote): the memset below cannot
+  // reach them, and the workspace's own norm slots stay unused
+  const float *qn = q_norms ? q_norms : (const float *)(w + p.off_qn);
+  const float *cn = c_norms ? c_norms : (const float *)(w + p.off_cn);
   HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
   if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
-  if (metric != kMetricDot) {
+  if (metric != kMetricDot && (!q_norms || !c_norms)) {
     const int sq = metric == kMetricEuclidean;
     Timed t("norms_bf16", s);
-    HIP_TRY(launch_norms_bf16(q, m, d, ldq, sq, qn, nullptr, s));
-    HIP_TRY(launch_norms_bf16(c, n, d, ldc, sq, cn, cn + n, s));
+    if (!q_norms) HIP_TRY(launch_norms_bf16(q, m, d, ldq, sq, (float *)(w + p.off_qn), nullptr, s));
+    if (!c_norms)
+      HIP_TRY(launch_norms_bf16(c, n, d, ldc, sq, (float *)(w + p.off_cn), (float *)(w + p.off_cn) + n, s));
   }
   GemmF32Args a = fused_args(m, n, dp, k, metric, p, w);
   a.qb = q;
@@ -1410,7 +1416,12 @@ int ff_rerun(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c, int64
 // caller's workspace, or the arena when ws is NULL.
 int topk_bf16_device_impl(const TopkRoute &r, const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
                           int64_t ldc, int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base,
-                          uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev) {
+                          uint32_t *out_idx, float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev,
+                          const float *q_norms = nullptr, const float *c_norms = nullptr) {
+  // q_norms / c_norms: optional precomputed norms of this metric (q: m norms;
+  // c: [n norms | n pre-filter factors], a bf16 corpus handle's), outside the
+  // workspace; the native route then launches no norms kernel for them.  The
+  // widened route computes its own from the widened rows (the same values).
   const int cus = g_dev[dev].cus;
   Workspace W;
   if (int rc = acquire_workspace(ws, ws_bytes, r.total, dev, s, W)) return rc;
@@ -1427,7 +1438,8 @@ int topk_bf16_device_impl(const TopkRoute &r, const uint16_t *q, int64_t ldq, in
     rc = topk_f32_unscreened(r, wq, r.dpw, m, wc, r.dpw, n, d, k, metric, index_base, out_idx, out_score, w + r.base,
                              s, cus, nullptr, false);
   } else {
-    rc = topk_bf16_native(r.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w, s);
+    rc = topk_bf16_native(r.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w, s,
+                          metric == kMetricDot ? nullptr : q_norms, metric == kMetricDot ? nullptr : c_norms);
 #ifdef PMM_WITH_FF
     if (rc == PMM_OK && r.p.variant == -6)
       rc = ff_rerun(q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
@@ -1602,6 +1614,9 @@ struct ShardSrc {
   const float *host;       // host corpus rows [lo, lo + rows), row stride d, or
   const float *dev_rows;   // resident padded rows (stride dp) of a corpus handle
   const float *dev_norms;  // with dev_rows: the handle's norms of this metric ([rows | rows factors])
+  // a bf16 handle's shard instead of dev_rows: zero-padded bf16 rows of stride
+  // roundup(d, 128), with dev_norms as above (of the rounded rows)
+  const uint16_t *dev_rows16 = nullptr;
 };
 
 std::mutex g_peer_mu;
@@ -1674,7 +1689,7 @@ void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t
       L.off_c[g] = off;
       if (sh[g].host) off = al256(off + (size_t)sh[g].rows * (bf16 ? d : dp) * 4);
       L.off_cb[g] = off;
-      if (bf16) off = al256(off + (size_t)sh[g].rows * dp * 2);
+      if (bf16 && sh[g].host) off = al256(off + (size_t)sh[g].rows * dp * 2);  // (resident: the handle's rows)
       L.off_list[g] = off;
       off = al256(off + list_bytes);
     }
@@ -1763,12 +1778,17 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
     uint32_t *li = (uint32_t *)(p.base + off_list[g]);
     float *ls = (float *)(li + (size_t)m * k);
     if (bf16) {
-      SH_TRY(hipMemcpyAsync(p.base + off_c[g], x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
-      SH_TRY(launch_f32_to_bf16((const float *)(p.base + off_c[g]), x.rows, d, d,
-                                (uint16_t *)(p.base + off_cb[g]), dp, p.s));
-      SH_RC(topk_bf16_device_impl(L.route[g], (const uint16_t *)(p.base + p.off_qb), dp, m,
-                                  (const uint16_t *)(p.base + off_cb[g]), dp, x.rows, d, k, metric,
-                                  (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev));
+      const uint16_t *cb = x.dev_rows16;
+      if (x.host) {
+        SH_TRY(hipMemcpyAsync(p.base + off_c[g], x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
+        SH_TRY(launch_f32_to_bf16((const float *)(p.base + off_c[g]), x.rows, d, d,
+                                  (uint16_t *)(p.base + off_cb[g]), dp, p.s));
+        cb = (const uint16_t *)(p.base + off_cb[g]);
+      }
+      // (a resident shard brings its norms; the query norms are this call's)
+      SH_RC(topk_bf16_device_impl(L.route[g], (const uint16_t *)(p.base + p.off_qb), dp, m, cb, dp, x.rows, d, k,
+                                  metric, (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev, nullptr,
+                                  x.host ? nullptr : x.dev_norms));
     } else {
       const float *c = x.dev_rows;
       if (x.host) {
@@ -2265,6 +2285,9 @@ int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }
 // take the reference's f64 branch, src/matmul.rs:449-468) keeps its rows in
 // f64 with the f64 norms of both metrics, sharded over a device list the same
 // way (round 6).
+// A bf16 corpus (pmm_corpus_create_bf16) keeps the rows rounded to bf16 at
+// stride roundup(d, 128) -- what the bf16 kernels read -- and the f32 norms of
+// the rounded rows in the f32 layout, both from one round_norms_bf16 pass.
 struct CorpusShard {
   int device = 0;
   int64_t lo = 0, n = 0;       // rows [lo, lo + n) of the corpus
@@ -2272,12 +2295,21 @@ struct CorpusShard {
   float *norms = nullptr;      // f32: [cosine: n norms | n 1/norm][euclid: n sq | n sq*(1-2^-18)]
   double *data64 = nullptr;    // f64: n x dp
   double *norms64 = nullptr;   // f64: [cosine: n norms][euclid: n sq]
+  uint16_t *data16 = nullptr;  // bf16: n x dp bit patterns (norms: the f32 layout, of the rounded rows)
 };
 struct pmm_corpus {
   int64_t n = 0, d = 0, dp = 0;
   int dtype = PMM_DTYPE_F32;
   std::vector<CorpusShard> shards;
 };
+
+// A handle serves the one top-k entry of its row type: the others refuse it
+// and name that entry.
+static int wrong_handle(const pmm_corpus *h) {
+  static const char *const kRows[] = {"f32", "f64", "bf16"};
+  static const char *const kEntry[] = {"pmm_topk_f32_corpus", "pmm_topk_f64_corpus", "pmm_topk_bf16_corpus"};
+  return fail(PMM_ERR_ARG, "the corpus handle holds %s rows: use %s", kRows[h->dtype], kEntry[h->dtype]);
+}
 
 // ===========================================================================
 // C ABI
@@ -2505,8 +2537,11 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     char *b = (char *)base;
     HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b + off_cf, c, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_f32_to_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db, s));
-    HIP_TRY(launch_f32_to_bf16((const float *)(b + off_cf), n, d, d, (uint16_t *)(b + off_cb), db, s));
+    {
+      Timed t("f32_to_bf16", s);  // (measured against round_norms_bf16, profiles/bf16_corpus)
+      HIP_TRY(launch_f32_to_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db, s));
+      HIP_TRY(launch_f32_to_bf16((const float *)(b + off_cf), n, d, d, (uint16_t *)(b + off_cb), db, s));
+    }
     rc = topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, (const uint16_t *)(b + off_cb),
                                db, n, d, k, metric, 0u, (uint32_t *)(b + off_i),
                                (float *)(b + off_s), b + off_w, ws_need, s, dev);
@@ -2844,13 +2879,14 @@ int pmm_corpus_destroy(pmm_corpus *h) {
   int cur = 0;
   (void)hipGetDevice(&cur);
   for (auto &x : h->shards) {
-    if (!x.data && !x.norms && !x.data64 && !x.norms64) continue;
+    if (!x.data && !x.norms && !x.data64 && !x.norms64 && !x.data16) continue;
     (void)hipSetDevice(x.device);
     (void)hipDeviceSynchronize();
     if (x.data) (void)hipFree(x.data);
     if (x.norms) (void)hipFree(x.norms);
     if (x.data64) (void)hipFree(x.data64);
     if (x.norms64) (void)hipFree(x.norms64);
+    if (x.data16) (void)hipFree(x.data16);
   }
   (void)hipSetDevice(cur);
   delete h;
@@ -2941,8 +2977,7 @@ int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **ou
 int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, double *out_score) {
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->dtype != PMM_DTYPE_F64)
-    return fail(PMM_ERR_ARG, "the corpus handle holds f32 rows: use pmm_topk_f32_corpus");
+  if (h->dtype != PMM_DTYPE_F64) return wrong_handle(h);
   int rc = validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
   if ((rc = check_metric(metric))) return rc;
@@ -2989,8 +3024,7 @@ int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t
 int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, float *out_score) {
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->dtype != PMM_DTYPE_F32)
-    return fail(PMM_ERR_ARG, "the corpus handle holds f64 rows: use pmm_topk_f64_corpus");
+  if (h->dtype != PMM_DTYPE_F32) return wrong_handle(h);
   int rc = validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
   if ((rc = check_metric(metric))) return rc;
@@ -3030,6 +3064,151 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.data, dp, h->n, h->d, k, metric,
                             0u, (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need,
                             s, dev, shard_norms(x));
+  if (rc) return rc;
+  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+}
+
+int pmm_round_bf16_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,
+                          float *norm, float *inv_norm, float *sq, float *sq_factor, void *stream) {
+  if (rows < 0 || d < 0 || ld < d || ldo < d || ldo % 8 != 0)
+    return fail(PMM_ERR_ARG, "bad rounding sizes (rows=%lld d=%lld ld=%lld ldo=%lld: ld >= d, ldo >= d a multiple of 8)",
+                (long long)rows, (long long)d, (long long)ld, (long long)ldo);
+  if (rows == 0) return PMM_OK;
+  if (!a || !out) return fail(PMM_ERR_ARG, "null argument");
+  if ((uintptr_t)out & 15) return fail(PMM_ERR_ARG, "the bf16 output needs a 16-byte-aligned base");
+  int dev, rc;
+  if ((rc = ensure_device(&dev))) return rc;
+  hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
+  Timed t("round_norms_bf16", s);
+  HIP_TRY(launch_round_norms_bf16(a, rows, d, ld, out, ldo, norm, inv_norm, sq, sq_factor, s));
+  return PMM_OK;
+}
+
+int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **out) {
+  if (!out) return fail(PMM_ERR_ARG, "null argument");
+  *out = nullptr;
+  int rc = validate_sizes(0, n, d, 0, false);
+  if (rc) return rc;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
+  if (!c) return fail(PMM_ERR_ARG, "null argument");
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
+  // sharded over a device list exactly as pmm_corpus_create_f32
+  std::vector<int> devs = devices_snapshot();
+  if (devs.size() <= 1) devs.assign(1, dev);
+  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
+  pmm_corpus *h = new pmm_corpus();
+  h->n = n;
+  h->d = d;
+  h->dp = cdiv(d, kBf16DAlign) * kBf16DAlign;  // pmm_topk_bf16_device's stride rule
+  h->dtype = PMM_DTYPE_BF16;
+  h->shards.resize(G);
+  for (int g = 0; g < G; g++) {
+    CorpusShard &x = h->shards[g];
+    x.device = devs[g];
+    x.lo = shard_lo(n, G, g);
+    x.n = shard_lo(n, G, g + 1) - x.lo;
+  }
+  for (int g = 0; g < G; g++) {
+    CorpusShard &x = h->shards[g];
+    hipStream_t s;
+    hipError_t e = hipSetDevice(x.device);
+    if (e == hipSuccess && (rc = thread_stream(x.device, &s))) {
+      pmm_corpus_destroy(h);
+      return rc;
+    }
+    // the f32 rows only pass through: a staging buffer of the shard's own,
+    // freed below (the arena would keep it for the thread's lifetime)
+    float *stage = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&x.data16, (size_t)x.n * h->dp * 2);
+    if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)x.n * 4 * 4);
+    if (e == hipSuccess) e = hipMalloc(&stage, (size_t)x.n * d * 4);
+    if (e != hipSuccess) {
+      pmm_corpus_destroy(h);
+      return fail(PMM_ERR_HIP, "corpus allocation failed on device %d: %s", x.device, hipGetErrorString(e));
+    }
+    hipError_t e1, e2;
+    {
+      Timed t("h2d", s);
+      e1 = hipMemcpyAsync(stage, c + x.lo * d, (size_t)x.n * d * 4, hipMemcpyHostToDevice, s);
+    }
+    {
+      // rows and the norms of both metrics in one pass over the f32 rows
+      Timed t("round_norms_bf16", s);
+      e2 = launch_round_norms_bf16(stage, x.n, d, d, x.data16, h->dp, x.norms, x.norms + x.n, x.norms + 2 * x.n,
+                                   x.norms + 3 * x.n, s);
+    }
+    hipError_t e3 = hipStreamSynchronize(s);
+    (void)hipFree(stage);
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+      pmm_corpus_destroy(h);
+      return fail(PMM_ERR_HIP, "corpus rounding failed");
+    }
+  }
+  (void)hipSetDevice(dev);
+  *out = h;
+  return PMM_OK;
+}
+
+int pmm_topk_bf16_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric, uint32_t *out_idx,
+                         float *out_score) {
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (h->dtype != PMM_DTYPE_BF16) return wrong_handle(h);
+  int rc = validate_sizes(m, h->n, h->d, k, true);
+  if (rc) return rc;
+  if ((rc = check_metric(metric))) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
+  // which of a shard's norm arrays this metric reads (none for dot)
+  auto shard_norms = [&](const CorpusShard &x) -> const float * {
+    return metric == kMetricCosine ? x.norms : metric == kMetricEuclidean ? x.norms + 2 * x.n : nullptr;
+  };
+  if (h->shards.size() > 1 && k <= kFusedMaxK) {
+    std::vector<ShardSrc> sh(h->shards.size());
+    for (size_t g = 0; g < sh.size(); g++) {
+      const CorpusShard &x = h->shards[g];
+      sh[g] = ShardSrc{x.device, x.lo, x.n, nullptr, nullptr, shard_norms(x), x.data16};
+    }
+    return topk_sharded(q, m, h->d, k, metric, PMM_COMPUTE_BF16, sh, out_idx, out_score);
+  }
+  if (h->shards.size() > 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
+                (long long)k);
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  const int64_t d = h->d, db = h->dp, n = h->n;
+  // the route pmm_topk_f32_ex's bf16 branch asks for, so the same kernels run
+  const TopkRoute route = route_topk(m, n, d, k, metric, PMM_COMPUTE_BF16, g_dev[dev].cus, true, true);
+  const size_t ws_need = route.total;
+  // query norms sit outside the route's workspace (topk_bf16_native zeroes its top)
+  size_t off_qf = 0, off_qb = al256((size_t)m * d * 4), off_qn = off_qb + al256((size_t)m * db * 2);
+  size_t off_i = off_qn + al256((size_t)m * 4), off_s = off_i + al256((size_t)m * k * 4);
+  size_t off_w = off_s + al256((size_t)m * k * 4);
+  void *base;
+  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
+  char *b = (char *)base;
+  {
+    Timed t("h2d", s);
+    HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
+  }
+  // the native route reads the metric's query norms; the widened one computes
+  // its own from the widened rows
+  float *qn = (metric != kMetricDot && route.kind == Route::kBf16Native) ? (float *)(b + off_qn) : nullptr;
+  {
+    Timed t("round_norms_bf16", s);
+    HIP_TRY(launch_round_norms_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db,
+                                    metric == kMetricCosine ? qn : nullptr, nullptr,
+                                    metric == kMetricEuclidean ? qn : nullptr, nullptr, s));
+  }
+  rc = topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, x.data16, db, n, d, k, metric, 0u,
+                             (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need, s, dev, qn,
+                             shard_norms(x));
   if (rc) return rc;
   return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
 }

@@ -184,6 +184,16 @@ hipError_t launch_ff_bucket(const GemmF32Args &a, unsigned *fb_count, int *fb_ro
 // d..ldd-1 zero-filled.
 hipError_t launch_f32_to_bf16(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst,
                               int64_t ldd, hipStream_t s);
+// The same rounding and, in the same pass, the rows' norms of both metrics:
+// norm = sqrt(sum), inv_norm = the cosine pre-filter factor, sq = sum,
+// sq_factor = the euclidean one, all from one sum of squares of the ROUNDED
+// values in norms_rows' order -- bit-equal to launch_f32_to_bf16 followed by
+// launch_norms_bf16 with squared = 0 and 1.  A null array is skipped.  lds >= d
+// (any alignment; 16-byte loads when src and lds allow), ldd >= d a multiple
+// of 8, dst 16-byte aligned.
+hipError_t launch_round_norms_bf16(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst,
+                                   int64_t ldd, float *norm, float *inv_norm, float *sq, float *sq_factor,
+                                   hipStream_t s);
 // bf16 rows -> f32 rows (exact), columns d..ldd-1 zero-filled
 hipError_t launch_bf16_to_f32(const uint16_t *src, int64_t rows, int64_t d, int64_t lds, float *dst, int64_t ldd,
                               hipStream_t s);

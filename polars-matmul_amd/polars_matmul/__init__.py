@@ -5,7 +5,10 @@ Drop-in for the reference package ``polars_matmul`` (NivekNey/polars-matmul
 v0.1.4): importing it registers the ``pmm`` expression namespace on Polars
 (python/polars_matmul/__init__.py:39 in the reference) with the same
 ``topk(corpus, k, metric)`` and ``matmul(corpus, flatten)`` methods, result
-dtypes and errors.  The numerics run on MI355X through hand-written HIP
+dtypes and errors.  An extension: ``.pmm.topk(corpus, k, metric,
+compute="bf16")`` (and ``_topk(..., compute="bf16")``) reads both columns as
+f32 and searches them on the bf16 MFMA path; the corpus stays on the device
+as a bf16 handle (half an f32 handle's HBM) while its Series is reused.  The numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
 Usage:
@@ -61,8 +64,7 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     rows widened to f32 beyond)."""
     q = np.asarray(queries)
     c = np.asarray(corpus)
-    if compute not in ("f32", "bf16"):
-        raise ValueError(f"compute must be 'f32' or 'bf16', not {compute!r}")
+    _native.check_compute(compute)
     dt = np.float32 if (q.dtype == np.float32 and c.dtype == np.float32) else np.float64
     if compute == "bf16":
         dt = np.float32
@@ -97,15 +99,22 @@ if pl is not None:
         def __init__(self, expr: "pl.Expr"):
             self._expr = expr
 
-        def topk(self, corpus: "pl.Series", k: int, metric: Metric = "cosine") -> "pl.Expr":
-            """Top-k matches per embedding: List[Struct{index: u32, score: f64}]."""
+        def topk(self, corpus: "pl.Series", k: int, metric: Metric = "cosine",
+                 compute: Compute = "f32") -> "pl.Expr":
+            """Top-k matches per embedding: List[Struct{index: u32, score: f64}].
+            compute="bf16" (an extension): both columns read as f32 and
+            searched on the bf16 MFMA path, the corpus kept on the device as a
+            bf16 handle between calls."""
             if isinstance(corpus, pl.Expr):
                 raise TypeError(
                     "corpus must be a Polars Series, not an Expression. "
                     "Use corpus['column_name'] or corpus.get_column('column_name')."
                 )
+            _native.check_compute(compute)
+            # (the default stays the reference's four-argument call)
+            extra = {} if compute == "f32" else {"compute": compute}
             return self._expr.map_batches(
-                lambda s: _topk(s, corpus, k, metric),
+                lambda s: _topk(s, corpus, k, metric, **extra),
                 is_elementwise=True,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
             )

@@ -67,14 +67,17 @@ EXPORTED_SYMBOLS = (
     "pmm_merge_sorted_topk_strided_device",
     "pmm_norms_f32_device",
     "pmm_norms_f64_device",
+    "pmm_round_bf16_device",
     "pmm_corpus_create_f32",
     "pmm_corpus_create_f64",
+    "pmm_corpus_create_bf16",
     "pmm_corpus_dtype",
     "pmm_corpus_destroy",
     "pmm_corpus_info",
     "pmm_corpus_shards",
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
+    "pmm_topk_bf16_corpus",
     "pmm_timing_enable",
     "pmm_timing_reset",
     "pmm_timing_read",
@@ -155,7 +158,9 @@ _SIGS = {
         [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_norms_f32_device": ([_vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_norms_f64_device": ([_vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    "pmm_round_bf16_device": ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "pmm_corpus_create_f32": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_create_bf16": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_create_f64": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_dtype": ([_vp, ctypes.POINTER(ctypes.c_int)], _i32),
     "pmm_corpus_destroy": ([_vp], _i32),
@@ -166,6 +171,7 @@ _SIGS = {
     "pmm_corpus_shards": ([_vp, ctypes.POINTER(ctypes.c_int)], _i32),
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
+    "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_timing_enable": ([_i32], _i32),
     "pmm_timing_reset": ([], _i32),
     "pmm_timing_read": (
@@ -482,6 +488,17 @@ def norms_device(a_ptr: int, ld: int, rows: int, d: int, squared: bool, out_ptr:
     check(fn(a_ptr, ld, rows, d, 1 if squared else 0, out_ptr, stream or None))
 
 
+def round_bf16_device(a_ptr: int, ld: int, rows: int, d: int, out_ptr: int, ldo: int, *, norm: int = 0,
+                      inv_norm: int = 0, sq: int = 0, sq_factor: int = 0, stream: int = 0) -> None:
+    """f32 device rows -> zero-padded bf16 rows of stride ``ldo`` (a multiple of
+    8, >= d; roundup(d, 128) for ``topk_bf16_device``) and, in the same pass,
+    any of the four per-row f32 arrays of the rounded rows: norm, the cosine
+    factor 1 / norm (0 at or below 1e-6), squared norm, the euclidean factor
+    (pmm_round_bf16_device).  0 skips an array."""
+    check(_lib.pmm_round_bf16_device(a_ptr, ld, rows, d, out_ptr, ldo, norm or None, inv_norm or None,
+                                     sq or None, sq_factor or None, stream or None))
+
+
 def workspace_bytes(m: int, n: int, d: int, k: int, metric: int, compute: int = COMPUTE_F32) -> int:
     return int(_lib.pmm_topk_workspace_bytes(m, n, d, k, metric, compute))
 
@@ -511,14 +528,29 @@ def timing_read(kernel: str):
 
 DTYPE_F32 = 0
 DTYPE_F64 = 1
+DTYPE_BF16 = 2
+
+_COMPUTE_MODES = ("f32", "bf16")
 
 
-def corpus_device_bytes(n: int, d: int, dtype=np.float32) -> int:
+def check_compute(compute: str) -> str:
+    """``compute`` if it names a compute mode, else the ValueError every
+    ``compute=`` keyword of the package raises (the numpy-level ``topk``'s)."""
+    if compute not in _COMPUTE_MODES:
+        raise ValueError(f"compute must be 'f32' or 'bf16', not {compute!r}")
+    return compute
+
+
+def corpus_device_bytes(n: int, d: int, dtype=np.float32, compute: str = "f32") -> int:
     """HBM a DeviceCorpus of n x d rows holds.  f32 (pmm_corpus_create_f32):
     the rows padded to a multiple of 32 floats plus four norm arrays (cosine
     norms and pre-filter factors, euclidean squared norms and factors).  f64
     (pmm_corpus_create_f64): the rows padded to a multiple of 16 doubles plus
-    two norm arrays (cosine norms, euclidean squared norms)."""
+    two norm arrays (cosine norms, euclidean squared norms).  compute="bf16"
+    (pmm_corpus_create_bf16, whatever ``dtype``): the rows rounded to bf16 and
+    padded to a multiple of 128 plus the four f32 norm arrays."""
+    if check_compute(compute) == "bf16":
+        return n * (-(-d // 128) * 128) * 2 + n * 4 * 4
     if np.dtype(dtype) == np.float64:
         dp = -(-d // 16) * 16
         return n * dp * 8 + n * 2 * 8
@@ -529,25 +561,31 @@ def corpus_device_bytes(n: int, d: int, dtype=np.float32) -> int:
 class DeviceCorpus:
     """A corpus uploaded once to HBM with its norms (pmm_corpus_*), f32 or f64
     rows by the dtype of ``c`` (the reference's two branches,
-    src/matmul.rs:427-468).
+    src/matmul.rs:427-468).  ``compute="bf16"``: ``c`` is taken as f32 and kept
+    rounded to bf16 with the norms of the rounded rows (pmm_corpus_create_bf16,
+    half the HBM of an f32 handle); ``topk`` then takes f32 queries and returns
+    f32 scores, those of ``topk_host(..., compute=COMPUTE_BF16)``.
 
     Reference-counted: ``acquire()`` / ``release()`` bracket a use (``topk``
     does so itself); ``close()`` frees the device memory at once if no use is
     in flight, else when the last one releases it -- a cache may evict a
     handle while another thread is still searching it."""
 
-    def __init__(self, c: np.ndarray):
-        self.dtype = np.dtype(np.float64 if np.asarray(c).dtype == np.float64 else np.float32)
+    def __init__(self, c: np.ndarray, compute: str = "f32"):
+        self.compute = check_compute(compute)
+        bf16 = compute == "bf16"
+        self.dtype = np.dtype(np.float64 if np.asarray(c).dtype == np.float64 and not bf16 else np.float32)
         c = np.ascontiguousarray(c, dtype=self.dtype)
         h = ctypes.c_void_p()
-        create = _lib.pmm_corpus_create_f64 if self.dtype == np.float64 else _lib.pmm_corpus_create_f32
+        create = (_lib.pmm_corpus_create_bf16 if bf16 else
+                  _lib.pmm_corpus_create_f64 if self.dtype == np.float64 else _lib.pmm_corpus_create_f32)
         check(create(ptr(c), c.shape[0], c.shape[1], ctypes.byref(h)))
         self._h = h
         self._lock = threading.Lock()
         self._refs = 0
         self._closing = False
         self.n, self.d = c.shape
-        self.nbytes = corpus_device_bytes(self.n, self.d, self.dtype)  # device footprint, not host bytes
+        self.nbytes = corpus_device_bytes(self.n, self.d, self.dtype, compute)  # device footprint, not host bytes
 
     def acquire(self) -> "DeviceCorpus":
         with self._lock:
@@ -571,7 +609,8 @@ class DeviceCorpus:
         m = q.shape[0]
         idx = np.empty((m, k), dtype=np.uint32)
         sc = np.empty((m, k), dtype=self.dtype)
-        fn = _lib.pmm_topk_f64_corpus if self.dtype == np.float64 else _lib.pmm_topk_f32_corpus
+        fn = (_lib.pmm_topk_bf16_corpus if self.compute == "bf16" else
+              _lib.pmm_topk_f64_corpus if self.dtype == np.float64 else _lib.pmm_topk_f32_corpus)
         self.acquire()
         try:
             check(fn(self._h, ptr(q), m, k, metric, ptr(idx), ptr(sc)))
@@ -593,7 +632,7 @@ class DeviceCorpus:
 
     @property
     def device_dtype(self) -> int:
-        """DTYPE_F32 / DTYPE_F64 as the library reports it (pmm_corpus_dtype)."""
+        """DTYPE_F32 / DTYPE_F64 / DTYPE_BF16 as the library reports it (pmm_corpus_dtype)."""
         v = ctypes.c_int(-1)
         check(_lib.pmm_corpus_dtype(self._h, ctypes.byref(v)))
         return v.value

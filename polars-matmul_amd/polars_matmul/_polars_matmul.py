@@ -2,7 +2,8 @@
 (src/lib.rs:15-62, module path pyproject.toml:114), re-implemented over the HIP
 C ABI.  Exports ``_topk(left, right, k, metric)`` and ``_matmul(left, right)``
 with the reference's argument meaning, result dtypes, error texts and edge
-rules:
+rules (``_topk`` also takes ``compute="bf16"``, an extension: both columns read
+as f32, searched on the bf16 MFMA path against a cached bf16 corpus handle):
 
 * input extraction / marshalling ..... src/matmul.rs:12-286
 * ``_matmul`` -> ``matmul_impl`` ...... src/matmul.rs:295-417
@@ -230,7 +231,7 @@ def _arrow_key(arr):
     return (str(arr.type), arr.offset, len(arr), bufs)
 
 
-def _cached_corpus(original, rv, c: np.ndarray):
+def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
     """An ACQUIRED DeviceCorpus for this corpus (the caller releases it), or
     None when the corpus is not cacheable."""
     # Only inputs whose Arrow buffers persist across calls: a single-chunk
@@ -248,9 +249,10 @@ def _cached_corpus(original, rv, c: np.ndarray):
     if key is not None:
         # the compute dtype: an f32 column searched by f64 queries runs the
         # f64 branch (src/matmul.rs:427) on an f64 copy of the same buffers;
-        # a handle is sharded over the device list of its creation
-        key = key + (c.dtype.str, tuple(_native.get_devices()))
-    dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype)
+        # a handle is sharded over the device list of its creation; an f32
+        # and a bf16 handle of one column are two entries
+        key = key + (c.dtype.str, tuple(_native.get_devices()), compute)
+    dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
     if not _CACHE_ON or key is None or c.nbytes < _CACHE_MIN_BYTES or dev_bytes > _CACHE_BYTES:
         return None
     with _cache_lock:
@@ -260,7 +262,7 @@ def _cached_corpus(original, rv, c: np.ndarray):
             return hit[1].acquire()
         if not _fits_device(dev_bytes):
             return None
-        dc = _native.DeviceCorpus(c)
+        dc = _native.DeviceCorpus(c) if compute == "f32" else _native.DeviceCorpus(c, compute=compute)
         _cache[key] = (rv, dc)
         total = sum(v[1].nbytes for v in _cache.values())
         while total > _CACHE_BYTES and len(_cache) > 1:
@@ -340,11 +342,14 @@ def _wrap(arrow_arr: pa.Array, name: str, polars_out: bool):
 # ---------------------------------------------------------------------------
 # Public extension functions
 # ---------------------------------------------------------------------------
-def _topk(left, right, k, metric):
-    """src/lib.rs:33-55 -> src/matmul.rs:473-519 topk_impl."""
+def _topk(left, right, k, metric, compute="f32"):
+    """src/lib.rs:33-55 -> src/matmul.rs:473-519 topk_impl.  compute="bf16"
+    (an extension): both columns are read as f32 whatever their dtype and
+    searched on the bf16 path (the numpy-level ``topk``'s compute="bf16")."""
     k = _as_usize(k)
     if not isinstance(metric, str):
         raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
+    bf16 = _native.check_compute(compute) == "bf16"
     polars_out = _is_polars_series(left)
     t = time.perf_counter()
     lv = _to_arrow(left)
@@ -356,7 +361,7 @@ def _topk(left, right, k, metric):
         metric_id = _native.metric_from_str(metric)
     except _native.PmmError as e:  # src/metrics.rs:25 text
         raise _compute_error(str(e)) from None
-    use_f32 = _is_f32(lv) and _is_f32(rv)  # src/matmul.rs:427
+    use_f32 = bf16 or (_is_f32(lv) and _is_f32(rv))  # src/matmul.rs:427
     dt = np.float32 if use_f32 else np.float64
     q = _series_to_matrix(lv, dt)
     c = _series_to_matrix(rv, dt)
@@ -370,10 +375,10 @@ def _topk(left, right, k, metric):
         sc = np.zeros((m, 0), dtype=np.float64)
     else:
         _apply_devices_env()
-        # (an f32 handle sharded over several GPUs serves k <= 1024; larger k
-        # runs on one GPU, the device list's first.  An f64 handle is sharded
-        # the same way and serves any k.)
-        dc = (_cached_corpus(right, rv, c)
+        # (an f32 or bf16 handle sharded over several GPUs serves k <= 1024;
+        # larger k runs on one GPU, the device list's first.  An f64 handle is
+        # sharded the same way and serves any k.)
+        dc = (_cached_corpus(right, rv, c, compute)
               if (not use_f32 or kk <= 1024 or len(_native.get_devices()) <= 1) else None)
         if dc is not None:
             try:
@@ -381,7 +386,8 @@ def _topk(left, right, k, metric):
             finally:
                 dc.release()
         else:
-            idx, sc = _native.topk_host(q, c, kk, metric_id)
+            idx, sc = _native.topk_host(q, c, kk, metric_id,
+                                        compute=_native.COMPUTE_BF16 if bf16 else _native.COMPUTE_F32)
         t = _lap("device", t)
         sc = sc.astype(np.float64, copy=False)  # src/matmul.rs:447 (f32 -> f64)
     out = _wrap(_topk_arrow(idx, sc, m, kk), "topk", polars_out)
