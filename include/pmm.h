@@ -263,6 +263,29 @@ int pmm_round_bf16_device(const float *a, int64_t ld, int64_t rows, int64_t d, u
                           int64_t ldo, float *norm, float *inv_norm, float *sq, float *sq_factor,
                           void *stream);
 
+/* f32 device rows prepared for the screened f32 cosine top-k (the bf16 screen
+ * with an exact f32 re-score) in one read of the rows: what the handle's
+ * screened call runs over its queries and the handle's image build over the
+ * corpus.  a, ld, out and ldo as for pmm_round_bf16_device (any alignment of
+ * a; out 16-byte aligned, ldo >= d a multiple of 8, columns d..ldo-1 zero;
+ * round to nearest even, NaN stays NaN).  Each per-row array may be NULL
+ * (skipped):
+ *   norm, inv_norm: the cosine norm and pre-filter factor of the UNROUNDED
+ *     row, bit-equal to pmm_norms_f32_device (squared = 0) and to
+ *     norm > 1e-6 ? 1 / norm : 0;
+ *   rel: an upper bound of ||x - bf16(x)|| / ||x||, the measured ratio
+ *     inflated by 2^-9 and capped at 2^-8 (2^-8 for an unsafe row);
+ *   unsafe: 1 when the screen's bound does not hold for the row -- an element
+ *     that is not finite or, unless zero, lies outside [2^-48, 2^48], a norm
+ *     at or below 1e-6, a zero sum of squares -- else 0.
+ * scalars (NULL, or two words the caller zeroed): [0] takes the maximum rel
+ * over the safe rows (f32 bits, atomically), [1] is set when any row is
+ * unsafe.  One launch, 6 bytes of traffic per element.  No reference
+ * counterpart. */
+int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out,
+                              int64_t ldo, float *norm, float *inv_norm, float *rel,
+                              uint32_t *unsafe, uint32_t *scalars, void *stream);
+
 /* k-way merge of per-shard top-k lists: idx/score are [m][lists][k_in] (the
  * lists in any order; idx 0xFFFFFFFF marks an empty slot).  Writes the best k_out of each row to out_idx/out_score
  * [m][k_out].  This is the merge step after the RCCL gather of the
@@ -337,9 +360,25 @@ int pmm_corpus_info(const pmm_corpus *corpus, int64_t *n, int64_t *d, int *devic
 /* Number of device shards of a corpus handle (1, or the device list's length
  * capped at n when pmm_set_devices was in effect at creation). */
 int pmm_corpus_shards(const pmm_corpus *corpus, int *shards);
+/* HBM the handle holds now: its rows and norm arrays and, once an f32 handle
+ * has built it (pmm_topk_f32_corpus), its screen image. */
+int pmm_corpus_bytes(const pmm_corpus *corpus, size_t *bytes);
 
 /* pmm_topk_f32 against a device-resident corpus (host queries in, host
- * results out; 0 <= k <= n). */
+ * results out; 0 <= k <= n).  Results are pmm_topk_f32's bit for bit.
+ *
+ * A cosine call whose shape asks for the bf16 screen (the limits, thresholds
+ * and per-call PMM_F32_SCREEN of pmm_topk_f32_device) on a handle of one
+ * shard screens against the handle's screen image: the rows rounded to bf16
+ * at stride roundup(d, 128) with each row's rounding residual and unsafe flag
+ * (n * roundup(d, 128) * 2 + 8 n bytes; pmm_screen_prepare_device's kernel).
+ * The first such call builds it, when it fits in half of the free HBM; it is
+ * published whole, so concurrent callers see no image or all of it, and
+ * pmm_corpus_destroy frees it.  A failed allocation is no error: the call runs
+ * unscreened and a later call tries again.  A corpus with an unsafe row (zero,
+ * non-finite or out-of-window values) keeps no image and never screens: the
+ * flag is read once, at the build.  pmm_corpus_create_f32 builds no image.
+ * Sharded handles run unscreened. */
 int pmm_topk_f32_corpus(const pmm_corpus *corpus, const float *q, int64_t m, int64_t k,
                         int metric, uint32_t *out_idx, float *out_score);
 

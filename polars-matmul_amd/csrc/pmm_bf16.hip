@@ -172,6 +172,165 @@ hipError_t launch_round_norms_bf16(const float *src, int64_t rows, int64_t d, in
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Rows prepared for the f32 cosine screen in one read of the
+// f32 rows: the bf16 image, the EXACT cosine norm and pre-filter factor of the
+// unrounded row (norms_kernel<float, float>'s bits), the rounding residual
+// bound and the unsafe flag -- what norms_kernel + screen_round_kernel give in
+// two launches and 10 bytes of HBM traffic per element, in one and 6.
+//
+// round_norms_bf16_kernel's shape: a band of kRnRows rows, kRnCols columns at
+// a time.  Every thread rounds groups of 8 columns (16-byte loads where the
+// source allows, one 16-byte store) and parks the UNROUNDED group in LDS; then
+// 8 lanes per row walk the chunk in norms_rows' order -- lane j owns columns
+// j, j + 8, ... -- carrying the sum of squares over the chunks (norms_rows'
+// statements, no FMA) and, beside it, the sum of squared residuals and the
+// element-window test (any order: the 2^-9 inflation covers their rounding).
+// ---------------------------------------------------------------------------
+constexpr int kSpLd = kRnCols + 8;  // LDS row stride (f32): the 8 rows of a wave land 8 banks apart
+
+// round to nearest even, NaN stays NaN (screen_round_kernel's statement)
+__device__ __forceinline__ uint32_t screen_bf16_bits(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (x != x) ? ((u >> 16) | 0x40u) : ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+// one element's share of the residual sum and of the window test
+__device__ __forceinline__ void screen_element(float x, float &r2, bool &ok) {
+  const float r = x - __uint_as_float(screen_bf16_bits(x) << 16);  // (exact for a safe element)
+  r2 = fmaf(r, r, r2);
+  const float ax = fabsf(x);
+  ok = ok && (ax == 0.0f || (ax >= kScreenMinAbs && ax <= kScreenMaxAbs));
+}
+
+__global__ __launch_bounds__(256) void screen_prepare_kernel(const float *__restrict__ src, int64_t rows, int64_t d,
+                                                             int64_t lds, uint16_t *__restrict__ dst, int64_t ldd,
+                                                             float *__restrict__ norm, float *__restrict__ inv_norm,
+                                                             float *__restrict__ rel, unsigned *__restrict__ bad,
+                                                             unsigned *scal, int vec) {
+  __shared__ __attribute__((aligned(16))) float park[kRnRows * kSpLd];
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kRnRows;
+  const int nrows = (int)((rows - row0) < kRnRows ? (rows - row0) : kRnRows);
+  const int64_t d8 = d & ~(int64_t)7;
+  const int my = tid >> 3, j = tid & 7;  // norm phase: lane j of band row my
+  float acc = 0.0f, r2 = 0.0f;
+  bool ok = true;
+  float tail[7];
+#pragma unroll
+  for (int t = 0; t < 7; t++) tail[t] = 0.0f;
+  for (int64_t cb = 0; cb < ldd; cb += kRnCols) {
+    const int cw = (int)((ldd - cb) < kRnCols ? (ldd - cb) : kRnCols);  // a multiple of 8
+    const int gpr = cw >> 3;                                             // 8-column groups per row
+    for (int g = tid; g < nrows * gpr; g += 256) {
+      const int r = g / gpr;
+      const int cl = (g - r * gpr) * 8;
+      const int64_t c0 = cb + cl;
+      const float *p = src + (row0 + r) * lds + c0;
+      f32x4 lo = {0.0f, 0.0f, 0.0f, 0.0f}, hi = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (vec && c0 + 8 <= d) {
+        lo = *(const f32x4 *)p;
+        hi = *(const f32x4 *)(p + 4);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          lo[u] = (c0 + u < d) ? p[u] : 0.0f;
+          hi[u] = (c0 + 4 + u < d) ? p[4 + u] : 0.0f;
+        }
+      }
+      uint32_t b[8];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        b[u] = screen_bf16_bits(lo[u]);
+        b[4 + u] = screen_bf16_bits(hi[u]);
+      }
+      *(uint4 *)(dst + (row0 + r) * ldd + c0) =
+          make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16));
+      *(f32x4 *)(park + r * kSpLd + cl) = lo;
+      *(f32x4 *)(park + r * kSpLd + cl + 4) = hi;
+    }
+    __syncthreads();
+    if (my < nrows && cb < d) {
+      const float *pr = park + my * kSpLd;
+      const int lim = (int)((d8 - cb) < cw ? (d8 - cb) : cw);  // columns of this chunk below d8
+      int i = j;
+      for (; i + 56 < lim; i += 64) {
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) x[u] = pr[i + 8 * u];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          acc = acc + x[u] * x[u];
+          screen_element(x[u], r2, ok);
+        }
+      }
+      for (; i < lim; i += 8) {
+        const float x = pr[i];
+        acc = acc + x * x;
+        screen_element(x, r2, ok);
+      }
+      // the tail columns d8..d-1 lie in one chunk: lane 0 keeps them for the end
+      if (j == 0 && d8 < d && d8 >= cb && d8 < cb + cw) {
+#pragma unroll
+        for (int t = 0; t < 7; t++)
+          if (d8 + t < d) {
+            tail[t] = pr[(int)(d8 - cb) + t];
+            screen_element(tail[t], r2, ok);
+          }
+      }
+    }
+    __syncthreads();
+  }
+  const int base = (tid & 63) & ~7;
+  float pp[8];
+#pragma unroll
+  for (int t = 0; t < 8; t++) pp[t] = __shfl(acc, base + t, 64);
+  int okw = ok ? 1 : 0;
+#pragma unroll
+  for (int off = 4; off; off >>= 1) {
+    r2 += __shfl_xor(r2, off, 64);
+    okw &= __shfl_xor(okw, off, 64);
+  }
+  if (my < nrows && j == 0) {
+    float sum = 0.0f;
+    sum = sum + (pp[0] + pp[4]);
+    sum = sum + (pp[1] + pp[5]);
+    sum = sum + (pp[2] + pp[6]);
+    sum = sum + (pp[3] + pp[7]);
+#pragma unroll
+    for (int t = 0; t < 7; t++)
+      if (d8 + t < d) sum = sum + tail[t] * tail[t];
+    const int64_t row = row0 + my;
+    const float v = sqrt_rn<float>(sum);
+    if (norm) norm[row] = v;
+    if (inv_norm) inv_norm[row] = (v > 1e-6f) ? 1.0f / v : 0.0f;
+    const bool unsafe = !okw || !(v > 1e-6f) || !(sum > 0.0f);
+    // (the sums' and the square root's rounding: far inside the 2^-9 inflation;
+    // a safe row's true ratio is below 2^-8, bf16's half ulp)
+    const float rl = unsafe ? 0x1p-8f : fminf(__builtin_sqrtf(r2 / sum) * (1.0f + 0x1p-9f), 0x1p-8f);
+    if (rel) rel[row] = rl;
+    if (bad) bad[row] = unsafe ? 1u : 0u;
+    if (scal) {
+      if (unsafe) {
+        atomicOr(scal + 1, 1u);
+      } else if (__float_as_uint(rl) > __hip_atomic_load(scal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        atomicMax(scal, __float_as_uint(rl));  // (non-negative floats order as their bits)
+      }
+    }
+  }
+}
+
+hipError_t launch_screen_prepare(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst, int64_t ldd,
+                                 float *norm, float *inv_norm, float *rel, unsigned *bad, unsigned *scal,
+                                 hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (ldd < d || ldd % 8 != 0 || lds < d || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+  const int vec = (((uintptr_t)src & 15) == 0 && lds % 4 == 0) ? 1 : 0;
+  const int64_t grid = (rows + kRnRows - 1) / kRnRows;
+  screen_prepare_kernel<<<(unsigned)grid, 256, 0, s>>>(src, rows, d, lds, dst, ldd, norm, inv_norm, rel, bad, scal,
+                                                       vec);
+  return hipGetLastError();
+}
+
 // bf16 -> f32 (exact widening) with zero padding to ldd: one thread per element
 __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const uint16_t *__restrict__ src, int64_t rows,
                                                           int64_t d, int64_t lds, float *__restrict__ dst,

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -770,6 +771,7 @@ constexpr double kScreenMinWork = 4e12, kScreenMinWorkLongCorpus = 5e11;
 // thresholds, counts, candidates, norms), which starts it.
 struct ScreenPlan {
   int64_t dpb = 0, dp = 0, rr = 0;
+  bool ext = false;  // the corpus image is supplied (a handle's ScreenImage): no off_cb, no off_crel
   size_t off_qb = 0, off_cb = 0, off_rel = 0, off_eps = 0, off_bad = 0, off_ovf = 0, off_scal = 0, off_rows = 0,
          off_crel = 0, off_gq = 0, off_f32 = 0, f32_bytes = 0, total = 0;
 };
@@ -782,15 +784,31 @@ bool screen_wanted(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
   const double work = (double)m * (double)n * (double)(cdiv(d, 32) * 32);
   return work >= kScreenMinWork || (work >= kScreenMinWorkLongCorpus && n >= 100 * m);
 }
-// b: the bf16 kernel's plan of the call (padded D = roundup(d, 128))
-void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, const Plan &b, ScreenPlan &sp) {
+// A corpus' share of the screen's inputs, computed once and kept by an f32
+// corpus handle (CorpusShard::screen): what topk_f32_screened derives from C
+// other than the exact norms and factors, which the handle holds already.
+// Only a corpus without an unsafe row keeps one.
+struct ScreenImage {
+  uint16_t *cb = nullptr;  // n x roundup(d, 128) bf16 bit patterns, zero-padded
+  float *crel = nullptr;   // per row: [residual bound n | unsafe flag n]
+  float max_rel = 0.0f;    // the maximum residual bound over the rows
+};
+size_t screen_image_bytes(int64_t n, int64_t d) {
+  return (size_t)n * (cdiv(d, kBf16DAlign) * kBf16DAlign) * 2 + (size_t)n * 8;
+}
+// b: the bf16 kernel's plan of the call (padded D = roundup(d, 128));
+// corpus_image: the caller supplies a ScreenImage, so the workspace leaves out
+// the corpus' bf16 rows and per-row residuals
+void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, const Plan &b, ScreenPlan &sp,
+                 bool corpus_image = false) {
   sp.dpb = cdiv(d, kBf16DAlign) * kBf16DAlign;
   sp.dp = cdiv(d, 32) * 32;
+  sp.ext = corpus_image;
   size_t off = b.total;
   sp.off_qb = off;
   off = al256(off + (size_t)m * sp.dpb * 2);
   sp.off_cb = off;
-  off = al256(off + (size_t)n * sp.dpb * 2);
+  if (!corpus_image) off = al256(off + (size_t)n * sp.dpb * 2);
   sp.off_rel = off;
   off = al256(off + (size_t)m * 4);
   sp.off_eps = off;
@@ -804,7 +822,7 @@ void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus
   sp.off_rows = off;
   off = al256(off + (size_t)m * 4);
   sp.off_crel = off;  // per corpus row: [residual n | unsafe flag n]
-  off = al256(off + (size_t)n * 8);
+  if (!corpus_image) off = al256(off + (size_t)n * 8);
   // re-run: gathered query rows, their lists, and the f32 path's own workspace
   // (sized for the whole call, which an unsafe corpus sends there)
   sp.rr = std::min<int64_t>(m, kScreenRerunRows);
@@ -857,15 +875,17 @@ struct TopkRoute {
 };
 
 // allow_screen = false: a caller whose call cannot screen (thresholds carried
-// between corpus chunks, cached corpus norms, per-device shards, the widened
-// bf16 path, the screen's own re-runs); allow_ff = false: the fire-and-forget
+// between corpus chunks, cached corpus norms without a screen image, per-device
+// shards, the widened bf16 path, the screen's own re-runs); allow_ff = false: the fire-and-forget
 // kernel's re-run.
 // d may arrive already padded (callers name d, roundup(d, 32) or, for bf16,
 // roundup(d, 128)): every decision and size below reads d through one of those
 // roundings, so the route is the same.  The one exception is the widened bf16
 // path, whose f32 rows are roundup(d, 32) wide: a d padded to 128 sizes more.
+// corpus_image = true: the screened route of a corpus handle, whose ScreenImage
+// stands for the corpus' share of the screen's workspace (plan_screen).
 TopkRoute route_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int compute, int cus,
-                     bool allow_screen, bool allow_ff) {
+                     bool allow_screen, bool allow_ff, bool corpus_image = false) {
   TopkRoute r;
   const int64_t dp = cdiv(d, 32) * 32;
   if (compute == PMM_COMPUTE_BF16) {
@@ -897,7 +917,7 @@ TopkRoute route_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int
     if (r.p.variant == -2 && r.p.capg <= kBf16WsMaxCapg && r.p.ctrig >= k + k / 2 + 32 &&
         r.p.ctrig <= r.p.capg - 64) {
       r.kind = Route::kF32Screened;
-      plan_screen(m, n, d, k, metric, cus, r.p, r.sp);
+      plan_screen(m, n, d, k, metric, cus, r.p, r.sp, corpus_image);
       r.total = r.sp.total;
       return r;
     }
@@ -1084,29 +1104,45 @@ int topk_f32_materialised(const MatPlan &p, const float *q, int64_t ldq, int64_t
 }
 
 // The screened route's executor over its acquired workspace w (r.total bytes).
+// img (with c_norms = the corpus' [norms n | factors n]; r planned with
+// corpus_image): a handle's call, which launches nothing over C before the
+// seed -- the corpus' share of the inputs is read from the handle -- and
+// prepares Q in one pass (screen_prepare_kernel).
 int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
                       int64_t n, int64_t d, int64_t k, uint32_t index_base, uint32_t *out_idx, float *out_score,
-                      char *w, hipStream_t s, int cus) {
+                      char *w, hipStream_t s, int cus, const ScreenImage *img = nullptr,
+                      const float *c_norms = nullptr) {
   const int metric = kMetricCosine;
   const ScreenPlan &sp = r.sp;
   const Plan &p = r.p;
-  float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
-  uint16_t *qb = (uint16_t *)(w + sp.off_qb), *cb = (uint16_t *)(w + sp.off_cb);
+  float *qn = (float *)(w + p.off_qn);
+  const float *cn = img ? c_norms : (float *)(w + p.off_cn);
+  uint16_t *qb = (uint16_t *)(w + sp.off_qb);
+  const uint16_t *cb = img ? img->cb : (uint16_t *)(w + sp.off_cb);
   float *rel = (float *)(w + sp.off_rel), *eps = (float *)(w + sp.off_eps);
   unsigned *bad = (unsigned *)(w + sp.off_bad), *ovf = (unsigned *)(w + sp.off_ovf);
   unsigned *scal = (unsigned *)(w + sp.off_scal);
   int *rows = (int *)(w + sp.off_rows);
-  float *crel = (float *)(w + sp.off_crel);
   HIP_TRY(hipMemsetAsync(w, 0, p.off_gthr + (size_t)m * 8, s));
   if (p.qb_full) HIP_TRY(hipMemsetAsync(w + p.off_cnt, 0, (size_t)m * p.S * 4, s));
   HIP_TRY(hipMemsetAsync(w + sp.off_ovf, 0, sp.off_rows - sp.off_ovf, s));
-  {
+  if (img) {
+    // the query rows' exact norms, image, residuals and flags in one read; the
+    // corpus' maximum residual from the handle (scal[1], corpus unsafe, stays 0)
+    Timed t("norms_f32/prepare", s);
+    HIP_TRY(launch_screen_prepare(q, m, d, ldq, qb, sp.dpb, qn, nullptr, rel, bad, nullptr, s));
+    uint32_t bits;
+    memcpy(&bits, &img->max_rel, 4);
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)scal, (int)bits, 1, s));
+  } else {
     // the exact norms and factors (norms_rows, as the unscreened path's), then
     // the bf16 images with the rounding residuals and the unsafe flags
     Timed t("norms_f32/round", s);
-    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, cn, cn + n, d, 0, s));
+    float *wcn = (float *)(w + p.off_cn), *crel = (float *)(w + sp.off_crel);
+    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, wcn, wcn + n, d, 0, s));
     HIP_TRY(launch_screen_round(q, m, d, ldq, qn, qb, sp.dpb, rel, bad, nullptr, s));
-    HIP_TRY(launch_screen_round(c, n, d, ldc, cn, cb, sp.dpb, crel, (unsigned *)(crel + n), scal, s));
+    HIP_TRY(launch_screen_round(c, n, d, ldc, wcn, (uint16_t *)(w + sp.off_cb), sp.dpb, crel,
+                                (unsigned *)(crel + n), scal, s));
   }
   GemmF32Args a = fused_args(m, n, sp.dpb, k, metric, p, w);
   a.qb = qb;
@@ -1181,15 +1217,16 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     memcpy(&rc, &h[0], 4);
     fprintf(stderr,
             "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
-            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld\n",
-            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m);
+            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld handle=%d\n",
+            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m,
+            img ? 1 : 0);
   }
   // The f32 kernel's runs never screen (k <= kScreenMaxK: always its fused
   // route); plan_screen reserved their workspace at off_f32.
   if (whole) {
     const TopkRoute f = route_topk(m, n, d, k, metric, PMM_COMPUTE_F32, cus, false, false);
     return topk_f32_fused(f.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w + sp.off_f32,
-                          s, cus, nullptr, false);
+                          s, cus, c_norms, false);
   }
   for (int64_t r0 = 0; r0 < (int64_t)h[2]; r0 += sp.rr) {
     const int64_t nr = std::min<int64_t>(sp.rr, (int64_t)h[2] - r0);
@@ -1200,7 +1237,7 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
                               out_idx, out_score, s, "screen re-run",
                               [&](const char *gq, uint32_t *gi, float *gs, char *fw) {
                                 return topk_f32_fused(f.p, (const float *)gq, sp.dp, nr, c, ldc, n, d, k, metric,
-                                                      index_base, gi, gs, fw, s, cus, nullptr, false);
+                                                      index_base, gi, gs, fw, s, cus, c_norms, false);
                               });
     if (rc) return rc;
   }
@@ -1223,25 +1260,28 @@ int topk_f32_unscreened(const TopkRoute &r, const float *q, int64_t ldq, int64_t
 int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
                          int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
                          float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev,
-                         const float *c_norms = nullptr, bool keep_gthr = false) {
+                         const float *c_norms = nullptr, bool keep_gthr = false,
+                         const ScreenImage *img = nullptr) {
   const int cus = g_dev[dev].cus;
   const int64_t dp = cdiv(d, 32) * 32;
   // What the screen asks of a call and route_topk cannot see (row strides and
-  // alignment of the rows it rounds, norms it computes itself, thresholds it
-  // starts from zero): without it the call takes the unscreened route, whose
-  // workspace the screened one contains (plan_screen reserves it).
+  // alignment of the rows it rounds, norms it computes itself or reads beside
+  // a handle's image, thresholds it starts from zero): without it the call
+  // takes the unscreened route, whose workspace the screened one contains
+  // (plan_screen reserves it).
   TopkRoute plain;
   const TopkRoute *r = &route;
   if (route.kind == Route::kF32Screened &&
-      (c_norms || keep_gthr || ldq % 4 != 0 || ldc % 4 != 0 || ldq < dp || ldc < dp ||
-       (((uintptr_t)q | (uintptr_t)c) & 15))) {
+      ((c_norms != nullptr) != (img != nullptr) || route.sp.ext != (img != nullptr) || keep_gthr || ldq % 4 != 0 ||
+       ldc % 4 != 0 || ldq < dp || ldc < dp || (((uintptr_t)q | (uintptr_t)c) & 15))) {
     plain = route_topk(m, n, d, k, metric, PMM_COMPUTE_F32, cus, false, false);
     r = &plain;
   }
   Workspace W;
   if (int rc = acquire_workspace(ws, ws_bytes, r->total, dev, s, W)) return rc;
   const int rc = r->kind == Route::kF32Screened
-                     ? topk_f32_screened(*r, q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, W.w, s, cus)
+                     ? topk_f32_screened(*r, q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, W.w, s, cus,
+                                         img, c_norms)
                      : topk_f32_unscreened(*r, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
                                            W.w, s, cus, c_norms, keep_gthr);
   return rc ? rc : W.done();
@@ -2301,7 +2341,68 @@ struct pmm_corpus {
   int64_t n = 0, d = 0, dp = 0;
   int dtype = PMM_DTYPE_F32;
   std::vector<CorpusShard> shards;
+  // An f32 handle of one shard: the corpus' share of the cosine screen's
+  // inputs (shard 0's rows), built under screen_mu by the
+  // first pmm_topk_f32_corpus call whose shape asks for the screen and
+  // published whole (release / acquire; a call reads the pointer once).
+  // screen_never: the corpus has an unsafe row -- no image is kept and no
+  // later call screens.
+  mutable std::mutex screen_mu;
+  mutable std::atomic<const ScreenImage *> screen{nullptr};
+  mutable std::atomic<bool> screen_never{false};
 };
+
+static void free_screen_image(const ScreenImage *img) {
+  if (!img) return;
+  if (img->cb) (void)hipFree(img->cb);
+  if (img->crel) (void)hipFree(img->crel);
+  delete img;
+}
+
+// The handle's ScreenImage on the current device (shard 0's) and stream s,
+// built and published on first use.  nullptr: the handle does not screen this
+// call -- the image does not fit in half of the free HBM or an allocation
+// failed (a later call tries again), or the corpus has an unsafe row (read
+// back once, here: no later call tries).
+static const ScreenImage *corpus_screen_image(const pmm_corpus *h, hipStream_t s) {
+  const ScreenImage *img = h->screen.load(std::memory_order_acquire);
+  if (img || h->screen_never.load(std::memory_order_acquire)) return img;
+  std::lock_guard<std::mutex> lk(h->screen_mu);
+  img = h->screen.load(std::memory_order_acquire);
+  if (img || h->screen_never.load(std::memory_order_acquire)) return img;
+  const CorpusShard &x = h->shards[0];
+  const int64_t dpb = cdiv(h->d, kBf16DAlign) * kBf16DAlign;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || screen_image_bytes(h->n, h->d) > free_b / 2) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  ScreenImage *ni = new ScreenImage();
+  unsigned *scal = nullptr;  // [0] max residual bound over the safe rows, [1] any unsafe row
+  unsigned hs[2] = {0u, 0u};
+  hipError_t e = hipMalloc(&ni->cb, (size_t)h->n * dpb * 2);
+  if (e == hipSuccess) e = hipMalloc(&ni->crel, (size_t)h->n * 8);
+  if (e == hipSuccess) e = hipMalloc(&scal, 256);
+  if (e == hipSuccess) e = hipMemsetAsync(scal, 0, 8, s);
+  if (e == hipSuccess) {
+    // (the norms were computed at creation and stay)
+    Timed t("corpus_image_build", s);
+    e = launch_screen_prepare(x.data, h->n, h->d, h->dp, ni->cb, dpb, nullptr, nullptr, ni->crel,
+                              (unsigned *)(ni->crel + h->n), scal, s);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(hs, scal, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (scal) (void)hipFree(scal);
+  if (e != hipSuccess || hs[1] != 0u) {
+    free_screen_image(ni);
+    if (e == hipSuccess) h->screen_never.store(true, std::memory_order_release);
+    else (void)hipGetLastError();  // (not an error of the call: it runs unscreened)
+    return nullptr;
+  }
+  memcpy(&ni->max_rel, &hs[0], 4);
+  h->screen.store(ni, std::memory_order_release);
+  return ni;
+}
 
 // A handle serves the one top-k entry of its row type: the others refuse it
 // and name that entry.
@@ -2887,9 +2988,22 @@ int pmm_corpus_destroy(pmm_corpus *h) {
     if (x.data64) (void)hipFree(x.data64);
     if (x.norms64) (void)hipFree(x.norms64);
     if (x.data16) (void)hipFree(x.data16);
+    if (&x == &h->shards[0]) free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
   }
   (void)hipSetDevice(cur);
   delete h;
+  return PMM_OK;
+}
+
+int pmm_corpus_bytes(const pmm_corpus *h, size_t *bytes) {
+  if (!h || !bytes) return fail(PMM_ERR_ARG, "null argument");
+  size_t b = 0;
+  for (const auto &x : h->shards) {
+    if (h->dtype == PMM_DTYPE_F64) b += (size_t)x.n * h->dp * 8 + (size_t)x.n * 2 * 8;
+    else b += (size_t)x.n * h->dp * (h->dtype == PMM_DTYPE_BF16 ? 2 : 4) + (size_t)x.n * 4 * 4;
+  }
+  if (h->screen.load(std::memory_order_acquire)) b += screen_image_bytes(h->n, h->d);
+  *bytes = b;
   return PMM_OK;
 }
 
@@ -3052,8 +3166,12 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = h->dp;
-  // (cached corpus norms: unscreened)
-  const TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
+  // The screened route when the shape asks for it (screen_wanted, as the
+  // device entry's) and the handle has, or can now build, its ScreenImage;
+  // else the f32 kernel on the cached norms, as for every other metric.
+  TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, true, true, true);
+  const ScreenImage *img = route.kind == Route::kF32Screened ? corpus_screen_image(h, s) : nullptr;
+  if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
   const size_t ws_need = route.total;
   size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
   size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
@@ -3063,9 +3181,26 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 4, s))) return rc;
   rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.data, dp, h->n, h->d, k, metric,
                             0u, (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need,
-                            s, dev, shard_norms(x));
+                            s, dev, shard_norms(x), false, img);
   if (rc) return rc;
   return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+}
+
+int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,
+                              float *norm, float *inv_norm, float *rel, uint32_t *unsafe, uint32_t *scalars,
+                              void *stream) {
+  if (rows < 0 || d < 0 || ld < d || ldo < d || ldo % 8 != 0)
+    return fail(PMM_ERR_ARG, "bad screen sizes (rows=%lld d=%lld ld=%lld ldo=%lld: ld >= d, ldo >= d a multiple of 8)",
+                (long long)rows, (long long)d, (long long)ld, (long long)ldo);
+  if (rows == 0) return PMM_OK;
+  if (!a || !out) return fail(PMM_ERR_ARG, "null argument");
+  if ((uintptr_t)out & 15) return fail(PMM_ERR_ARG, "the bf16 output needs a 16-byte-aligned base");
+  int dev, rc;
+  if ((rc = ensure_device(&dev))) return rc;
+  hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
+  Timed t("screen_prepare", s);
+  HIP_TRY(launch_screen_prepare(a, rows, d, ld, out, ldo, norm, inv_norm, rel, unsafe, scalars, s));
+  return PMM_OK;
 }
 
 int pmm_round_bf16_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,

@@ -507,6 +507,12 @@ __device__ inline void compact_row(const GemmF32Args &a, int s, int grow, u64 *t
 // (DESIGN.md §4a derives each term), inflated by 2^-9 relative for the f32
 // arithmetic of this function and of the measured rq, rc.
 // ===========================================================================
+// The element window of a "safe" row: inside it squares, products and sums of
+// up to 2^16 of them stay normal f32 numbers (no overflow, no subnormal the
+// MFMA might flush), and the bf16 rounding (same exponent range) keeps its
+// 2^-8 relative bound.  Zero is safe (exact in bf16).
+constexpr float kScreenMinAbs = 0x1p-48f, kScreenMaxAbs = 0x1p48f;
+
 __device__ __forceinline__ float screen_eps(float rq, float rc, int dp) {
   const float round = rq * (1.0f + rc) + rc;
   const float accum = (float)dp * (8.0f * (1.0f + 0x1p-7f) + 2.0f) * 0x1p-24f;

@@ -210,6 +210,14 @@ size_t merge_lds_bytes_per_wave(int P);
 hipError_t launch_screen_round(const float *src, int64_t rows, int64_t d, int64_t lds, const float *norm,
                                uint16_t *dst, int64_t ldd, float *rel, unsigned *bad, unsigned *scal,
                                hipStream_t s);
+// launch_screen_round's image, rel[], bad[] and scal AND the rows' exact cosine
+// norms and pre-filter factors (launch_norms_f32's bits, squared = 0) in one
+// read of the rows (pmm_bf16.hip).  A null array is skipped.  lds >= d (any
+// alignment; 16-byte loads when src and lds allow), ldd >= d a multiple of 8,
+// dst 16-byte aligned.
+hipError_t launch_screen_prepare(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst, int64_t ldd,
+                                 float *norm, float *inv_norm, float *rel, unsigned *bad, unsigned *scal,
+                                 hipStream_t s);
 // eps[row] from rel[row] and the corpus scalar; with `seeded` the rows' bf16
 // seed thresholds in gthr are lowered by eps into bounds of the exact k-th
 hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int dp, float *eps,

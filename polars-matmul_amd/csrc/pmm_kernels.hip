@@ -2436,12 +2436,7 @@ hipError_t launch_rowsort_global(const void *scores, int64_t lds, int rows, int 
 // Screened f32 top-k (cosine), the passes around the bf16 screen kernel
 // (pmm_bf16_ws_kernel.h, SCREEN; the bound is screen_eps in pmm_device.h).
 // ===========================================================================
-// The element window of a "safe" row: inside it squares, products and sums of
-// up to 2^16 of them stay normal f32 numbers (no overflow, no subnormal the
-// MFMA might flush), and the bf16 rounding (same exponent range) keeps its
-// 2^-8 relative bound.  Zero is safe (exact in bf16).
-constexpr float kScreenMinAbs = 0x1p-48f, kScreenMaxAbs = 0x1p48f;
-
+// (the element window of a "safe" row: kScreenMinAbs / kScreenMaxAbs, pmm_device.h)
 // One wave per row, four elements per lane and step (16-byte loads, 8-byte
 // stores: rows 16-byte aligned, strides multiples of 4).
 __global__ __launch_bounds__(256) void screen_round_kernel(const float *__restrict__ src, int64_t rows, int64_t d,

@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "pmm_norms_f32_device",
     "pmm_norms_f64_device",
     "pmm_round_bf16_device",
+    "pmm_screen_prepare_device",
     "pmm_corpus_create_f32",
     "pmm_corpus_create_f64",
     "pmm_corpus_create_bf16",
@@ -75,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "pmm_corpus_destroy",
     "pmm_corpus_info",
     "pmm_corpus_shards",
+    "pmm_corpus_bytes",
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
@@ -159,6 +161,7 @@ _SIGS = {
     "pmm_norms_f32_device": ([_vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_norms_f64_device": ([_vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_round_bf16_device": ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "pmm_screen_prepare_device": ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "pmm_corpus_create_f32": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_create_bf16": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_create_f64": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
@@ -169,6 +172,7 @@ _SIGS = {
         _i32,
     ),
     "pmm_corpus_shards": ([_vp, ctypes.POINTER(ctypes.c_int)], _i32),
+    "pmm_corpus_bytes": ([_vp, ctypes.POINTER(_sz)], _i32),
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
@@ -499,6 +503,20 @@ def round_bf16_device(a_ptr: int, ld: int, rows: int, d: int, out_ptr: int, ldo:
                                      sq or None, sq_factor or None, stream or None))
 
 
+def screen_prepare_device(a_ptr: int, ld: int, rows: int, d: int, out_ptr: int, ldo: int, *, norm: int = 0,
+                          inv_norm: int = 0, rel: int = 0, unsafe: int = 0, scalars: int = 0,
+                          stream: int = 0) -> None:
+    """f32 device rows -> what the screened f32 cosine top-k needs of them, in
+    one pass (pmm_screen_prepare_device): the zero-padded bf16 rows of stride
+    ``ldo`` and any of the per-row arrays -- norm and 1 / norm of the unrounded
+    row (``norms_device``'s bits), the rounding residual bound ``rel``, the
+    ``unsafe`` flag (uint32) -- and, with ``scalars`` (two zeroed uint32
+    words), the maximum ``rel`` over the safe rows and the OR of the flags.
+    0 skips an array."""
+    check(_lib.pmm_screen_prepare_device(a_ptr, ld, rows, d, out_ptr, ldo, norm or None, inv_norm or None,
+                                         rel or None, unsafe or None, scalars or None, stream or None))
+
+
 def workspace_bytes(m: int, n: int, d: int, k: int, metric: int, compute: int = COMPUTE_F32) -> int:
     return int(_lib.pmm_topk_workspace_bytes(m, n, d, k, metric, compute))
 
@@ -541,21 +559,25 @@ def check_compute(compute: str) -> str:
     return compute
 
 
-def corpus_device_bytes(n: int, d: int, dtype=np.float32, compute: str = "f32") -> int:
+def corpus_device_bytes(n: int, d: int, dtype=np.float32, compute: str = "f32", screen: bool = False) -> int:
     """HBM a DeviceCorpus of n x d rows holds.  f32 (pmm_corpus_create_f32):
     the rows padded to a multiple of 32 floats plus four norm arrays (cosine
     norms and pre-filter factors, euclidean squared norms and factors).  f64
     (pmm_corpus_create_f64): the rows padded to a multiple of 16 doubles plus
     two norm arrays (cosine norms, euclidean squared norms).  compute="bf16"
     (pmm_corpus_create_bf16, whatever ``dtype``): the rows rounded to bf16 and
-    padded to a multiple of 128 plus the four f32 norm arrays."""
+    padded to a multiple of 128 plus the four f32 norm arrays.
+    ``screen=True``: with the screen image an f32 handle builds on its first
+    screened cosine call -- the rows rounded to bf16 at stride roundup(d, 128)
+    plus a residual and a flag per row.  Only f32 handles have one: an f64 or
+    ``compute="bf16"`` handle's figure is the same with and without it."""
     if check_compute(compute) == "bf16":
         return n * (-(-d // 128) * 128) * 2 + n * 4 * 4
     if np.dtype(dtype) == np.float64:
         dp = -(-d // 16) * 16
         return n * dp * 8 + n * 2 * 8
     dp = -(-d // 32) * 32
-    return n * dp * 4 + n * 4 * 4
+    return n * dp * 4 + n * 4 * 4 + (n * (-(-d // 128) * 128) * 2 + 8 * n if screen else 0)
 
 
 class DeviceCorpus:
@@ -585,7 +607,22 @@ class DeviceCorpus:
         self._refs = 0
         self._closing = False
         self.n, self.d = c.shape
-        self.nbytes = corpus_device_bytes(self.n, self.d, self.dtype, compute)  # device footprint, not host bytes
+        self._nbytes0 = corpus_device_bytes(self.n, self.d, self.dtype, compute)  # device footprint, not host bytes
+
+    @property
+    def nbytes(self) -> int:
+        """HBM the handle holds now (pmm_corpus_bytes): the creation-time
+        footprint until an f32 handle has built its screen image.  The
+        creation-time figure when the handle is closed or the loaded library
+        has no such entry."""
+        fn = getattr(_lib, "pmm_corpus_bytes", None)
+        with self._lock:
+            if fn is None or not self._h:
+                return self._nbytes0
+            out = _sz(0)
+            if fn(self._h, ctypes.byref(out)) != PMM_OK:
+                return self._nbytes0
+            return int(out.value)
 
     def acquire(self) -> "DeviceCorpus":
         with self._lock:

@@ -272,6 +272,25 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
         return dc.acquire()
 
 
+def _reaccount_cache(used) -> None:
+    """After a call on the cached handle ``used``: an f32 handle grows when its
+    first screened cosine call builds its screen image (DeviceCorpus.nbytes
+    reports the library's figure), so the cache is summed again and
+    least-recently-used OTHER entries leave while it holds more than
+    PMM_CORPUS_CACHE_BYTES.  The entry in use stays."""
+    with _cache_lock:
+        total = sum(v[1].nbytes for v in _cache.values())
+        for key in list(_cache):  # least recently used first
+            if total <= _CACHE_BYTES:
+                break
+            old = _cache[key][1]
+            if old is used:
+                continue
+            del _cache[key]
+            total -= old.nbytes
+            old.close()  # freed now, or by its last in-flight user
+
+
 def clear_corpus_cache() -> None:
     with _cache_lock:
         while _cache:
@@ -383,6 +402,7 @@ def _topk(left, right, k, metric, compute="f32"):
         if dc is not None:
             try:
                 idx, sc = dc.topk(q, kk, metric_id)
+                _reaccount_cache(dc)
             finally:
                 dc.release()
         else:
