@@ -364,6 +364,49 @@ int pmm_corpus_shards(const pmm_corpus *corpus, int *shards);
  * has built it (pmm_topk_f32_corpus), its screen image. */
 int pmm_corpus_bytes(const pmm_corpus *corpus, size_t *bytes);
 
+/* A handle derived on the device from a resident handle and a set of allowed
+ * rows: subset search ("filter, then search") without a second upload.  ids
+ * is a host array of s parent row numbers, strictly ascending, each < n,
+ * 1 <= s <= n; it is validated on the host in O(s) and a violation is
+ * PMM_ERR_ARG naming the first offending position.  The derived handle holds
+ * those rows densely at the parent's stride, the parent's norms of both
+ * metrics for them (gathered, not recomputed: the bits the norm kernels
+ * produce), a uint32[s] index map and, when an f32 parent has its screen image
+ * and the gathered image fits in half of the free HBM, that image's rows,
+ * residuals and flags with the parent's maximum residual (an upper bound over
+ * a superset of the rows: it only widens the screen's slack).  A gathered
+ * unsafe flag drops the gathered image and the derived handle never screens;
+ * a parent's own "never screens" state is not inherited (the subset may leave
+ * the unsafe row out), and without a parent image the derived handle builds
+ * its own on its first screened call.  No row crosses PCIe and no norm is
+ * recomputed.  The result is an ordinary pmm_corpus of the parent's row type
+ * with n = s, independent of the parent (pmm_corpus_destroy frees it), and
+ * every pmm_topk_*_corpus entry serves it through its usual routes -- but
+ * returns the PARENT's row numbers: ascending ids keep "lower index first"
+ * the same order in both numberings, so the lists are the exact top-k among
+ * the allowed rows, ties included.  One-shard f32, f64 and bf16 parents; a
+ * sharded parent is PMM_ERR_UNSUPPORTED, a null or derived parent PMM_ERR_ARG.
+ * Runs on the calling thread's stream and synchronises before it returns; a
+ * failed allocation is PMM_ERR_HIP with the HIP text and leaks nothing (a
+ * failed allocation of the optional image: no image, no error).  No reference
+ * counterpart. */
+int pmm_corpus_subset_ids(const pmm_corpus *parent, const uint32_t *ids, int64_t s, pmm_corpus **out);
+
+/* pmm_corpus_subset_ids with the rows given as an Arrow validity-style bitmap
+ * (host memory, least significant bit first): row r of the parent is allowed
+ * iff bit bit_offset + r is set, r in [0, n); bit_offset >= 0, any value (a
+ * sliced Arrow Boolean array's offset).  The bitmap's bytes are uploaded and
+ * compacted into the ascending index map on the device; the count is read back
+ * once to size the allocations.  An empty selection is PMM_ERR_ARG.  No
+ * reference counterpart. */
+int pmm_corpus_subset_mask(const pmm_corpus *parent, const uint8_t *bitmap, int64_t bit_offset,
+                           pmm_corpus **out);
+
+/* A derived handle's index map copied to the host: *s takes its length and ids
+ * (may be NULL when cap is 0) its first min(cap, s) entries.  A handle that is
+ * not derived: *s = 0.  No reference counterpart. */
+int pmm_corpus_index_map(const pmm_corpus *corpus, uint32_t *ids, int64_t cap, int64_t *s);
+
 /* pmm_topk_f32 against a device-resident corpus (host queries in, host
  * results out; 0 <= k <= n).  Results are pmm_topk_f32's bit for bit.
  *

@@ -2350,6 +2350,10 @@ struct pmm_corpus {
   mutable std::mutex screen_mu;
   mutable std::atomic<const ScreenImage *> screen{nullptr};
   mutable std::atomic<bool> screen_never{false};
+  // A derived handle (pmm_corpus_subset_*): its row i is the
+  // parent's row map[i], ascending (n entries on shard 0's device); the top-k
+  // entries return map[i].  NULL: not derived.
+  uint32_t *map = nullptr;
 };
 
 static void free_screen_image(const ScreenImage *img) {
@@ -2410,6 +2414,122 @@ static int wrong_handle(const pmm_corpus *h) {
   static const char *const kRows[] = {"f32", "f64", "bf16"};
   static const char *const kEntry[] = {"pmm_topk_f32_corpus", "pmm_topk_f64_corpus", "pmm_topk_bf16_corpus"};
   return fail(PMM_ERR_ARG, "the corpus handle holds %s rows: use %s", kRows[h->dtype], kEntry[h->dtype]);
+}
+
+// A derived handle's lists leave in the parent's numbering: one launch over
+// the m x k device index buffer between the executor and the download.  A
+// handle without a map launches nothing.
+static int remap_lists(const pmm_corpus *h, uint32_t *idx, int64_t m, int64_t k, hipStream_t s) {
+  if (!h->map) return PMM_OK;
+  Timed t("remap_index", s);
+  HIP_TRY(launch_remap_index(idx, m * k, h->map, h->n, s));
+  return PMM_OK;
+}
+
+// What both subset creators refuse in a parent.
+static int check_subset_parent(const pmm_corpus *p, pmm_corpus **out) {
+  if (!out) return fail(PMM_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (!p) return fail(PMM_ERR_ARG, "null corpus");
+  if (p->map)
+    return fail(PMM_ERR_ARG, "the parent is itself a derived handle: compose the selections and derive from its parent");
+  if (p->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no subsets: derive from a handle of one shard",
+                (int)p->shards.size());
+  return PMM_OK;
+}
+
+// The derived handle of parent p for the s ascending parent rows in `map`
+// (device memory the handle takes over, freed here on failure), on the
+// current device (p's) and stream st: the rows and the per-row norm arrays
+// gathered in one launch, the screen image's rows, residuals and flags in one
+// more when p has an image; `flag` is a device word for the gathered flags.
+// Synchronises st before it returns.
+static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned *flag, hipStream_t st,
+                        pmm_corpus **out) {
+  const CorpusShard &px = p->shards[0];
+  pmm_corpus *h = new pmm_corpus();
+  h->n = s;
+  h->d = p->d;
+  h->dp = p->dp;
+  h->dtype = p->dtype;
+  h->map = map;
+  h->shards.resize(1);
+  CorpusShard &x = h->shards[0];
+  x.device = px.device;
+  x.lo = 0;
+  x.n = s;
+  const bool f64 = p->dtype == PMM_DTYPE_F64, b16 = p->dtype == PMM_DTYPE_BF16;
+  const size_t row_bytes = (size_t)p->dp * (f64 ? 8 : b16 ? 2 : 4);  // a multiple of 128
+  void *rows = nullptr, *norms = nullptr;
+  hipError_t e = hipMalloc(&rows, (size_t)s * row_bytes);
+  if (f64) x.data64 = (double *)rows;
+  else if (b16) x.data16 = (uint16_t *)rows;
+  else x.data = (float *)rows;
+  if (e == hipSuccess) e = hipMalloc(&norms, (size_t)s * 16);  // f32 x 4 arrays, f64 x 2
+  if (f64) x.norms64 = (double *)norms;
+  else x.norms = (float *)norms;
+  if (e != hipSuccess) {
+    pmm_corpus_destroy(h);
+    return fail(PMM_ERR_HIP, "subset allocation failed on device %d: %s", px.device, hipGetErrorString(e));
+  }
+  {
+    Timed t("subset_gather_rows", st);
+    const void *src = f64 ? (const void *)px.data64 : b16 ? (const void *)px.data16 : (const void *)px.data;
+    const void *nsrc = f64 ? (const void *)px.norms64 : (const void *)px.norms;
+    e = launch_subset_gather(src, map, s, (int)(row_bytes / 16), rows, nsrc, norms, f64 ? 2 : 4, f64 ? 8 : 4, p->n,
+                             -1, nullptr, st);
+  }
+  // The parent's image, read once: its rows gathered too when they fit in
+  // half of the free HBM (else, or when an allocation fails, the derived
+  // handle starts without one and builds its own on its first screened call).
+  const ScreenImage *pimg = p->dtype == PMM_DTYPE_F32 ? p->screen.load(std::memory_order_acquire) : nullptr;
+  ScreenImage *ni = nullptr;
+  unsigned hflag = 0u;
+  if (e == hipSuccess && pimg) {
+    const int64_t dpb = cdiv(p->d, kBf16DAlign) * kBf16DAlign;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && screen_image_bytes(s, p->d) <= free_b / 2) {
+      ni = new ScreenImage();
+      hipError_t ei = hipMalloc(&ni->cb, (size_t)s * dpb * 2);
+      if (ei == hipSuccess) ei = hipMalloc(&ni->crel, (size_t)s * 8);
+      if (ei != hipSuccess) {
+        (void)hipGetLastError();
+        free_screen_image(ni);
+        ni = nullptr;
+      }
+    } else {
+      (void)hipGetLastError();
+    }
+    if (ni) {
+      e = hipMemsetAsync(flag, 0, 4, st);
+      if (e == hipSuccess) {
+        Timed t("subset_gather_image", st);
+        e = launch_subset_gather(pimg->cb, map, s, (int)(dpb * 2 / 16), ni->cb, pimg->crel, ni->crel, 2, 4, p->n, 1,
+                                 flag, st);
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st);
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    free_screen_image(ni);
+    pmm_corpus_destroy(h);
+    return fail(PMM_ERR_HIP, "subset gather failed: %s", hipGetErrorString(e));
+  }
+  if (ni && hflag != 0u) {
+    // (a parent with an image has no unsafe row, so this does not happen
+    // today; the rule is kept for a parent whose image carries flags)
+    free_screen_image(ni);
+    h->screen_never.store(true, std::memory_order_release);
+  } else if (ni) {
+    // the parent's bound holds over a superset of these rows: a larger bound
+    // only widens the screen's slack, the screen stays exact
+    ni->max_rel = pimg->max_rel;
+    h->screen.store(ni, std::memory_order_release);
+  }
+  *out = h;
+  return PMM_OK;
 }
 
 // ===========================================================================
@@ -2980,7 +3100,7 @@ int pmm_corpus_destroy(pmm_corpus *h) {
   int cur = 0;
   (void)hipGetDevice(&cur);
   for (auto &x : h->shards) {
-    if (!x.data && !x.norms && !x.data64 && !x.norms64 && !x.data16) continue;
+    if (!x.data && !x.norms && !x.data64 && !x.norms64 && !x.data16 && !h->map) continue;
     (void)hipSetDevice(x.device);
     (void)hipDeviceSynchronize();
     if (x.data) (void)hipFree(x.data);
@@ -2988,7 +3108,10 @@ int pmm_corpus_destroy(pmm_corpus *h) {
     if (x.data64) (void)hipFree(x.data64);
     if (x.norms64) (void)hipFree(x.norms64);
     if (x.data16) (void)hipFree(x.data16);
-    if (&x == &h->shards[0]) free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
+    if (&x == &h->shards[0]) {
+      free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
+      if (h->map) (void)hipFree(h->map);
+    }
   }
   (void)hipSetDevice(cur);
   delete h;
@@ -3003,6 +3126,7 @@ int pmm_corpus_bytes(const pmm_corpus *h, size_t *bytes) {
     else b += (size_t)x.n * h->dp * (h->dtype == PMM_DTYPE_BF16 ? 2 : 4) + (size_t)x.n * 4 * 4;
   }
   if (h->screen.load(std::memory_order_acquire)) b += screen_image_bytes(h->n, h->d);
+  if (h->map) b += (size_t)h->n * 4;
   *bytes = b;
   return PMM_OK;
 }
@@ -3024,6 +3148,110 @@ int pmm_corpus_shards(const pmm_corpus *h, int *shards) {
 int pmm_corpus_dtype(const pmm_corpus *h, int *dtype) {
   if (!h || !dtype) return fail(PMM_ERR_ARG, "null argument");
   *dtype = h->dtype;
+  return PMM_OK;
+}
+
+int pmm_corpus_subset_ids(const pmm_corpus *p, const uint32_t *ids, int64_t s, pmm_corpus **out) {
+  int rc = check_subset_parent(p, out);
+  if (rc) return rc;
+  if (!ids) return fail(PMM_ERR_ARG, "null argument");
+  if (s < 1 || s > p->n)
+    return fail(PMM_ERR_ARG, "a subset holds 1 <= s <= n rows (s=%lld n=%lld)", (long long)s, (long long)p->n);
+  for (int64_t i = 0; i < s; i++) {
+    if ((int64_t)ids[i] >= p->n)
+      return fail(PMM_ERR_ARG, "ids[%lld] = %u is not a row of the corpus (n=%lld)", (long long)i, ids[i],
+                  (long long)p->n);
+    if (i > 0 && ids[i] <= ids[i - 1])
+      return fail(PMM_ERR_ARG, "ids must be strictly ascending: ids[%lld] = %u follows %u", (long long)i, ids[i],
+                  ids[i - 1]);
+  }
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, p->shards[0].device))) return rc;
+  hipStream_t st;
+  if ((rc = thread_stream(dev, &st))) return rc;
+  void *flag;
+  if ((rc = arena(dev, st, 256, &flag))) return rc;
+  uint32_t *map = nullptr;
+  hipError_t e = hipMalloc(&map, (size_t)s * 4);
+  if (e != hipSuccess)
+    return fail(PMM_ERR_HIP, "subset allocation failed on device %d: %s", dev, hipGetErrorString(e));
+  {
+    Timed t("h2d", st);
+    e = hipMemcpyAsync(map, ids, (size_t)s * 4, hipMemcpyHostToDevice, st);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(map);
+    return fail(PMM_ERR_HIP, "subset upload failed: %s", hipGetErrorString(e));
+  }
+  return subset_build(p, map, s, (unsigned *)flag, st, out);
+}
+
+int pmm_corpus_subset_mask(const pmm_corpus *p, const uint8_t *bitmap, int64_t bit_offset, pmm_corpus **out) {
+  int rc = check_subset_parent(p, out);
+  if (rc) return rc;
+  if (!bitmap) return fail(PMM_ERR_ARG, "null argument");
+  if (bit_offset < 0) return fail(PMM_ERR_ARG, "bit_offset must be >= 0 (got %lld)", (long long)bit_offset);
+  const int64_t n = p->n;
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, p->shards[0].device))) return rc;
+  hipStream_t st;
+  if ((rc = thread_stream(dev, &st))) return rc;
+  // The bitmap from the byte that holds the first row's bit, as 64-bit words
+  // with one zero word behind (a word's rows straddle two when the offset is
+  // no multiple of 8), the per-block counts and their exclusive sums.
+  const int shift = (int)(bit_offset & 7);
+  const size_t in_bytes = (size_t)((shift + n + 7) / 8);
+  const int64_t nwords = cdiv(n, 64) + 1, nblk = cdiv(n, kMaskBlockRows);
+  const size_t off_w = 256, off_cnt = off_w + al256((size_t)nwords * 8);
+  const size_t off_base = off_cnt + al256((size_t)nblk * 4), total = off_base + al256((size_t)(nblk + 1) * 4);
+  void *base;
+  if ((rc = arena(dev, st, total, &base))) return rc;
+  char *b = (char *)base;  // [0, 256): subset_build's flag word
+  const unsigned long long *words = (const unsigned long long *)(b + off_w);
+  uint32_t *counts = (uint32_t *)(b + off_cnt), *bases = (uint32_t *)(b + off_base);
+  uint32_t hs = 0;
+  HIP_TRY(hipMemsetAsync(b + off_w, 0, (size_t)nwords * 8, st));
+  {
+    Timed t("h2d", st);
+    HIP_TRY(hipMemcpyAsync(b + off_w, bitmap + (bit_offset >> 3), in_bytes, hipMemcpyHostToDevice, st));
+  }
+  {
+    Timed t("subset_mask_count", st);
+    HIP_TRY(launch_mask_count(words, shift, n, counts, st));
+    HIP_TRY(launch_mask_scan(counts, nblk, bases, st));
+  }
+  // the one read-back: the allocations below are sized by the count
+  HIP_TRY(hipMemcpyAsync(&hs, bases + nblk, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t s = (int64_t)hs;
+  if (s == 0) return fail(PMM_ERR_ARG, "empty selection: no bit of the mask's %lld is set", (long long)n);
+  uint32_t *map = nullptr;
+  hipError_t e = hipMalloc(&map, (size_t)s * 4);
+  if (e != hipSuccess)
+    return fail(PMM_ERR_HIP, "subset allocation failed on device %d: %s", dev, hipGetErrorString(e));
+  {
+    Timed t("subset_mask_write", st);
+    e = launch_mask_write(words, shift, n, bases, map, st);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(map);
+    return fail(PMM_ERR_HIP, "subset compaction failed: %s", hipGetErrorString(e));
+  }
+  return subset_build(p, map, s, (unsigned *)b, st, out);
+}
+
+int pmm_corpus_index_map(const pmm_corpus *h, uint32_t *ids, int64_t cap, int64_t *s) {
+  if (!h || !s) return fail(PMM_ERR_ARG, "null argument");
+  *s = h->map ? h->n : 0;
+  const int64_t take = std::min<int64_t>(cap, *s);
+  if (take <= 0) return PMM_OK;
+  if (!ids) return fail(PMM_ERR_ARG, "null argument");
+  int dev, rc;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, h->shards[0].device))) return rc;
+  HIP_TRY(hipMemcpy(ids, h->map, (size_t)take * 4, hipMemcpyDeviceToHost));
   return PMM_OK;
 }
 
@@ -3126,6 +3354,7 @@ int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t
   rc = topk_f64_device_impl((const double *)(b + off_q), dp, m, x.data64, dp, n, h->d, k, metric, 0u, oi, os,
                             b + off_w, s, fused, cn);
   if (rc) return rc;
+  if ((rc = remap_lists(h, oi, m, k, s))) return rc;
   {
     Timed t("d2h", s);
     HIP_TRY(hipMemcpyAsync(out_idx, oi, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
@@ -3183,6 +3412,7 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
                             0u, (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need,
                             s, dev, shard_norms(x), false, img);
   if (rc) return rc;
+  if ((rc = remap_lists(h, (uint32_t *)(b + off_i), m, k, s))) return rc;
   return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
 }
 
@@ -3345,6 +3575,7 @@ int pmm_topk_bf16_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t
                              (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need, s, dev, qn,
                              shard_norms(x));
   if (rc) return rc;
+  if ((rc = remap_lists(h, (uint32_t *)(b + off_i), m, k, s))) return rc;
   return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
 }
 

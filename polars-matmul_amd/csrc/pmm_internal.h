@@ -251,6 +251,32 @@ hipError_t launch_gather_rows(const void *src, int64_t ld_units, const int *rows
 // out_idx / out_score row rows[i] = the dense lists' row i (k entries each)
 hipError_t launch_scatter_lists(const uint32_t *oi, const float *os, const int *rows, int r, int k,
                                 uint32_t *out_idx, float *out_score, hipStream_t s);
+// ---- derived corpus handles: subset search (pmm_subset.hip) ----
+// Bitmap compaction.  words: the bitmap as 64-bit words from the byte that
+// holds bit 0 of the selection (8-byte aligned, cdiv(n + shift, 64) + 1 words
+// readable), shift = the first bit's position in that byte (0..7): row r is
+// selected iff bit shift + r is set, r < n.  One 256-thread block takes
+// kMaskBlockRows rows, a lane one word of 64.
+constexpr int kMaskBlockRows = 256 * 64;
+// launch one: counts[b] = selected rows of block b
+hipError_t launch_mask_count(const unsigned long long *words, int shift, int64_t n, uint32_t *counts,
+                             hipStream_t s);
+// the one-block scan between the two: bases[b] = counts[0] + .. + counts[b - 1], bases[nblk] = the total
+hipError_t launch_mask_scan(const uint32_t *counts, int64_t nblk, uint32_t *bases, hipStream_t s);
+// launch two: out[bases[b] ..] = block b's selected rows, ascending (so all of out is)
+hipError_t launch_mask_write(const unsigned long long *words, int shift, int64_t n, const uint32_t *bases,
+                             uint32_t *out, hipStream_t s);
+// dst row i (units 16-byte units, dense) = src row ids[i] (row stride the
+// same units), i < s: one wave per destination row, four rows in flight per
+// wave.  In the same launch the na (<= 4) per-row arrays of aux_bytes-wide
+// (4 or 8) elements: aux_dst[a * s + i] = aux_src[a * n_src + ids[i]].  With
+// `any` and flag_arr >= 0: *any = 1 when a gathered element of array flag_arr
+// is non-zero (4-byte elements; zeroed by the caller).
+hipError_t launch_subset_gather(const void *src, const uint32_t *ids, int64_t s, int units, void *dst,
+                                const void *aux_src, void *aux_dst, int na, int aux_bytes, int64_t n_src,
+                                int flag_arr, unsigned *any, hipStream_t st);
+// idx[t] = map[idx[t]] for t < count; entries at or above s (the empty slot 0xFFFFFFFF) stay
+hipError_t launch_remap_index(uint32_t *idx, int64_t count, const uint32_t *map, int64_t s, hipStream_t st);
 hipError_t launch_gemm_f64_store(const double *q, int64_t ldq, const double *c, int64_t ldc,
                                  const double *qn, const double *cn, int M, int N, int D,
                                  int metric, int store_metric, double *out, int64_t ldo,

@@ -8,7 +8,10 @@ v0.1.4): importing it registers the ``pmm`` expression namespace on Polars
 dtypes and errors.  An extension: ``.pmm.topk(corpus, k, metric,
 compute="bf16")`` (and ``_topk(..., compute="bf16")``) reads both columns as
 f32 and searches them on the bf16 MFMA path; the corpus stays on the device
-as a bf16 handle (half an f32 handle's HBM) while its Series is reused.  The numerics run on MI355X through hand-written HIP
+as a bf16 handle (half an f32 handle's HBM) while its Series is reused.
+``subset=`` (an extension, on all three) searches only the selected corpus rows
+-- a Boolean mask Series or integer row ids -- from a handle derived on the
+device, and returns indices that number the full corpus.  The numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
 Usage:
@@ -34,6 +37,7 @@ import numpy as np
 
 from polars_matmul._polars_matmul import (  # noqa: F401
     PanicException,
+    _check_subset,
     _matmul,
     _topk,
     get_devices,
@@ -54,14 +58,17 @@ except Exception:  # polars is optional (not installable in this image)
 
 
 def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosine",
-         compute: Compute = "f32"):
+         compute: Compute = "f32", subset=None):
     """numpy-level top-k: returns (indices uint32 [m, k'], scores float64 [m, k'])
     with k' = min(k, len(corpus)); f32 compute iff both inputs are float32
     (src/matmul.rs:427), scores widened to f64 (src/matmul.rs:447).
     compute="bf16" (an extension, not in the reference): f32 inputs rounded to
     bf16 on the device, bf16 MFMA with f32 accumulation (include/pmm.h
     PMM_COMPUTE_BF16: the bf16 kernels up to d = 768 and k = 960, the rounded
-    rows widened to f32 beyond)."""
+    rows widened to f32 beyond).
+    subset (an extension): a bool mask of len(corpus) or integer row ids; only
+    those rows are searched (taken on the host: a numpy corpus has no cached
+    handle), k' = min(k, rows selected), and the indices number ``corpus``."""
     q = np.asarray(queries)
     c = np.asarray(corpus)
     _native.check_compute(compute)
@@ -75,9 +82,14 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
             f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
             f"right has {c.shape[1]} dimensional vectors"
         )
+    ids = _check_subset(subset, c.shape[0]).row_ids() if subset is not None else None
+    if ids is not None:
+        c = np.ascontiguousarray(c[ids])
     kk = min(int(k), c.shape[0])
     mode = _native.COMPUTE_BF16 if compute == "bf16" else _native.COMPUTE_F32
     idx, sc = _native.topk_host(q, c, kk, _native.metric_from_str(metric), compute=mode)
+    if ids is not None:
+        idx = ids[idx]
     return idx, sc.astype(np.float64, copy=False)
 
 
@@ -100,19 +112,30 @@ if pl is not None:
             self._expr = expr
 
         def topk(self, corpus: "pl.Series", k: int, metric: Metric = "cosine",
-                 compute: Compute = "f32") -> "pl.Expr":
+                 compute: Compute = "f32", subset: "pl.Series | None" = None) -> "pl.Expr":
             """Top-k matches per embedding: List[Struct{index: u32, score: f64}].
             compute="bf16" (an extension): both columns read as f32 and
             searched on the bf16 MFMA path, the corpus kept on the device as a
-            bf16 handle between calls."""
+            bf16 handle between calls.
+            subset (an extension): a Boolean Series of len(corpus) (nulls count
+            as false) or a Series of integer row ids; only those corpus rows
+            are searched, ``index`` still numbers ``corpus``, and k clips to
+            the number of selected rows."""
             if isinstance(corpus, pl.Expr):
                 raise TypeError(
                     "corpus must be a Polars Series, not an Expression. "
                     "Use corpus['column_name'] or corpus.get_column('column_name')."
                 )
+            if isinstance(subset, pl.Expr):
+                raise TypeError(
+                    "subset must be a Polars Series, not an Expression. "
+                    "Use frame['column_name'] or frame.get_column('column_name')."
+                )
             _native.check_compute(compute)
             # (the default stays the reference's four-argument call)
             extra = {} if compute == "f32" else {"compute": compute}
+            if subset is not None:
+                extra["subset"] = subset
             return self._expr.map_batches(
                 lambda s: _topk(s, corpus, k, metric, **extra),
                 is_elementwise=True,

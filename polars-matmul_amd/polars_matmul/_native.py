@@ -77,6 +77,9 @@ EXPORTED_SYMBOLS = (
     "pmm_corpus_info",
     "pmm_corpus_shards",
     "pmm_corpus_bytes",
+    "pmm_corpus_subset_ids",
+    "pmm_corpus_subset_mask",
+    "pmm_corpus_index_map",
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
@@ -173,6 +176,9 @@ _SIGS = {
     ),
     "pmm_corpus_shards": ([_vp, ctypes.POINTER(ctypes.c_int)], _i32),
     "pmm_corpus_bytes": ([_vp, ctypes.POINTER(_sz)], _i32),
+    "pmm_corpus_subset_ids": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_subset_mask": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_index_map": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
@@ -580,6 +586,26 @@ def corpus_device_bytes(n: int, d: int, dtype=np.float32, compute: str = "f32", 
     return n * dp * 4 + n * 4 * 4 + (n * (-(-d // 128) * 128) * 2 + 8 * n if screen else 0)
 
 
+def subset_device_bytes(s: int, d: int, dtype=np.float32, compute: str = "f32", screen: bool = False) -> int:
+    """HBM a derived handle of s rows holds (``DeviceCorpus.subset``): a
+    handle of s x d rows of the parent's kind -- ``corpus_device_bytes`` -- plus
+    its uint32 index map."""
+    return corpus_device_bytes(s, d, dtype, compute, screen) + 4 * s
+
+
+def ascending_ids(ids, n: int) -> np.ndarray:
+    """Row ids as the subset entries take them: uint32, ascending, unique.
+    An id outside [0, n) raises ValueError."""
+    ids = np.asarray(ids)
+    if ids.dtype.kind not in "iu":
+        raise TypeError(f"row ids must be integers, not {ids.dtype}")
+    ids = np.unique(ids.reshape(-1))  # sorted, duplicates dropped
+    if ids.size and (int(ids[0]) < 0 or int(ids[-1]) >= n):
+        bad = int(ids[0]) if int(ids[0]) < 0 else int(ids[-1])
+        raise ValueError(f"subset row id {bad} is out of range for a corpus of {n} rows")
+    return np.ascontiguousarray(ids, dtype=np.uint32)
+
+
 class DeviceCorpus:
     """A corpus uploaded once to HBM with its norms (pmm_corpus_*), f32 or f64
     rows by the dtype of ``c`` (the reference's two branches,
@@ -654,6 +680,85 @@ class DeviceCorpus:
         finally:
             self.release()
         return idx, sc
+
+    def _derived(self, h: ctypes.c_void_p) -> "DeviceCorpus":
+        """The DeviceCorpus of a handle the library derived from this one."""
+        dc = DeviceCorpus.__new__(DeviceCorpus)
+        dc.compute, dc.dtype, dc.d = self.compute, self.dtype, self.d
+        dc._h = h
+        dc._lock = threading.Lock()
+        dc._refs = 0
+        dc._closing = False
+        n = ctypes.c_int64(0)
+        check(_lib.pmm_corpus_info(h, ctypes.byref(n), None, None))
+        dc.n = int(n.value)
+        dc._nbytes0 = subset_device_bytes(dc.n, dc.d, dc.dtype, dc.compute)
+        return dc
+
+    def subset(self, sel) -> "DeviceCorpus":
+        """A handle derived on the device for the selected rows
+        (pmm_corpus_subset_mask / pmm_corpus_subset_ids): ``sel`` is a bool
+        array of length n (numpy, or an Arrow Boolean array without nulls,
+        whose bitmap is passed as it is), or an integer array of strictly
+        ascending row ids (``ascending_ids`` makes one; the library refuses
+        others).  No row is uploaded and no norm
+        recomputed; compute mode and dtype are this handle's.  ``topk`` on the
+        result searches only those rows and returns THIS handle's row numbers.
+        The result is independent of this handle and is closed on its own."""
+        if hasattr(sel, "buffers") and hasattr(sel, "offset"):
+            # an Arrow Boolean array without nulls: its bitmap goes to the
+            # device as it is, at the array's offset (no unpacking here)
+            if str(sel.type) != "bool" or sel.null_count or len(sel) != self.n:
+                raise ValueError(f"an Arrow mask is a Boolean array of {self.n} rows without nulls")
+            buf = sel.buffers()[1]  # (kept alive by sel for the call)
+            return self.subset_bitmap(buf.address, sel.offset)
+        sel = np.asarray(sel)
+        h = ctypes.c_void_p()
+        self.acquire()
+        try:
+            if sel.dtype == np.bool_:
+                if sel.shape != (self.n,):
+                    raise ValueError(f"a mask selects among {self.n} rows, got shape {sel.shape}")
+                bits = np.packbits(sel, bitorder="little")
+                check(_lib.pmm_corpus_subset_mask(self._h, ptr(bits), 0, ctypes.byref(h)))
+            elif sel.dtype.kind in "iu":
+                if sel.ndim != 1 or (sel.size and (int(sel.min()) < 0 or int(sel.max()) > 0xFFFFFFFF)):
+                    raise ValueError("row ids are a 1-D array of values in [0, n)")
+                ids = np.ascontiguousarray(sel, dtype=np.uint32)
+                check(_lib.pmm_corpus_subset_ids(self._h, ptr(ids), ids.size, ctypes.byref(h)))
+            else:
+                raise TypeError(f"a selection is a bool mask or integer row ids, not {sel.dtype}")
+            return self._derived(h)
+        finally:
+            self.release()
+
+    def subset_bitmap(self, address: int, bit_offset: int) -> "DeviceCorpus":
+        """``subset`` for a mask held as an Arrow validity-style bitmap in host
+        memory (least significant bit first): row r is selected iff bit
+        ``bit_offset + r`` of the bytes at ``address`` is set.  The bitmap is
+        uploaded as it is and compacted on the device."""
+        h = ctypes.c_void_p()
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_subset_mask(self._h, ctypes.c_void_p(address), bit_offset, ctypes.byref(h)))
+            return self._derived(h)
+        finally:
+            self.release()
+
+    def index_map(self):
+        """A derived handle's parent row numbers (uint32, ascending), one per
+        row; None for a handle that is not derived."""
+        s = ctypes.c_int64(0)
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_index_map(self._h, None, 0, ctypes.byref(s)))
+            if s.value == 0:
+                return None
+            ids = np.empty(s.value, dtype=np.uint32)
+            check(_lib.pmm_corpus_index_map(self._h, ptr(ids), ids.size, ctypes.byref(s)))
+            return ids
+        finally:
+            self.release()
 
     def _destroy(self) -> None:  # with self._lock held
         if self._h:

@@ -231,21 +231,24 @@ def _arrow_key(arr):
     return (str(arr.type), arr.offset, len(arr), bufs)
 
 
-def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
-    """An ACQUIRED DeviceCorpus for this corpus (the caller releases it), or
-    None when the corpus is not cacheable."""
-    # Only inputs whose Arrow buffers persist across calls: a single-chunk
-    # Polars Series (rechunk() then returns the same buffers; a multi-chunk
-    # one is concatenated into a fresh buffer on every call, whose address
-    # key would never hit while each miss pinned host and device memory), an
-    # Arrow array, or a single-chunk ChunkedArray.
+def _persistent_key(original, arrow):
+    """``_arrow_key`` of an input whose Arrow buffers persist across calls,
+    else None: a single-chunk Polars Series (rechunk() then returns the same
+    buffers; a multi-chunk one is concatenated into a fresh buffer on every
+    call, whose address key would never hit while each miss pinned host and
+    device memory), an Arrow array, or a single-chunk ChunkedArray."""
     if _is_polars_series(original):
         if original.n_chunks() != 1:
             return None
     elif not (isinstance(original, pa.Array)
               or (isinstance(original, pa.ChunkedArray) and original.num_chunks == 1)):
         return None
-    key = _arrow_key(rv)
+    return _arrow_key(arrow)
+
+
+def _corpus_key(original, rv, c: np.ndarray, compute: str):
+    """The cache key of this corpus, or None when it is not cacheable."""
+    key = _persistent_key(original, rv)
     if key is not None:
         # the compute dtype: an f32 column searched by f64 queries runs the
         # f64 branch (src/matmul.rs:427) on an f64 copy of the same buffers;
@@ -255,6 +258,16 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
     dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
     if not _CACHE_ON or key is None or c.nbytes < _CACHE_MIN_BYTES or dev_bytes > _CACHE_BYTES:
         return None
+    return key
+
+
+def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
+    """An ACQUIRED DeviceCorpus for this corpus (the caller releases it), or
+    None when the corpus is not cacheable."""
+    key = _corpus_key(original, rv, c, compute)
+    if key is None:
+        return None
+    dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
     with _cache_lock:
         hit = _cache.get(key)
         if hit is not None:
@@ -296,6 +309,136 @@ def clear_corpus_cache() -> None:
         while _cache:
             _, (_, dc) = _cache.popitem()
             dc.close()
+
+
+# ---------------------------------------------------------------------------
+# subset=: search only some rows of the corpus (an extension; the reference
+# filters the corpus frame on the host, which here would miss the cache,
+# upload the kept rows again and number the result by the filtered frame).
+# The selection becomes a handle derived on the device from the cached parent
+# (DeviceCorpus.subset), cached beside it under the parent's key plus the
+# selection's buffers.
+# ---------------------------------------------------------------------------
+class _Selection:
+    """A checked ``subset=`` argument: ``mask`` (an Arrow Boolean array of
+    len(corpus) without nulls) or ``ids`` (uint32, ascending, unique), the
+    number of selected rows, and -- when the argument's buffers persist across
+    calls -- their ``_arrow_key`` with the array that keeps them alive."""
+
+    __slots__ = ("mask", "ids", "count", "key", "keep")
+
+    def __init__(self, mask, ids, count, key, keep):
+        self.mask, self.ids, self.count, self.key, self.keep = mask, ids, count, key, keep
+
+    def row_ids(self) -> np.ndarray:
+        if self.ids is None:
+            self.ids = np.flatnonzero(self.mask.to_numpy(zero_copy_only=False)).astype(np.uint32)
+        return self.ids
+
+
+def _check_subset(subset, n: int) -> _Selection:
+    """TypeError / ValueError for a selection of the wrong kind or length, the
+    compute error for an empty one or an id outside the corpus: all before
+    any device work."""
+    original = subset
+    if _is_polars_series(subset):
+        subset = subset.rechunk().to_arrow()
+    if isinstance(subset, pa.ChunkedArray):
+        subset = subset.combine_chunks() if subset.num_chunks != 1 else subset.chunk(0)
+    if isinstance(subset, (list, tuple)):
+        subset = np.asarray(subset)
+    key = keep = mask = ids = None
+    if isinstance(subset, pa.Array):
+        key, keep = _persistent_key(original, subset), subset
+        if pa.types.is_boolean(subset.type):
+            mask = subset
+        elif pa.types.is_integer(subset.type):
+            ids = (subset.drop_null() if subset.null_count else subset).to_numpy(zero_copy_only=False)
+        else:
+            raise TypeError(f"subset must be a Boolean mask or integer row ids, got {subset.type}")
+    elif isinstance(subset, np.ndarray):
+        if subset.dtype == np.bool_:
+            if subset.ndim != 1:
+                raise ValueError(f"subset mask must be 1-D, got shape {subset.shape}")
+            mask = pa.array(subset)
+        elif subset.dtype.kind in "iu":
+            ids = subset
+        else:
+            raise TypeError(f"subset must be a Boolean mask or integer row ids, got {subset.dtype}")
+    else:
+        raise TypeError(f"subset must be a Series or array (a Boolean mask or integer row ids), "
+                        f"got {type(original).__name__}")
+    if mask is not None:
+        if len(mask) != n:
+            raise ValueError(f"subset mask has {len(mask)} rows, the corpus has {n}")
+        if mask.null_count:  # nulls count as false
+            mask = mask.fill_null(False)
+        count = mask.true_count
+    else:
+        try:
+            ids = _native.ascending_ids(ids, n)
+        except ValueError as e:
+            raise _compute_error(str(e)) from None
+        count = int(ids.size)
+    if count == 0:
+        raise _compute_error("Empty series")  # what an empty corpus raises
+    return _Selection(mask, ids, count, key, keep)
+
+
+def _cached_subset(parent, parent_key, sel: _Selection, c: np.ndarray, compute: str):
+    """(an ACQUIRED derived DeviceCorpus for ``sel`` of the cached ``parent``,
+    transient) -- the caller releases it, and closes it when ``transient`` (a
+    selection whose buffers do not persist is derived per call and not
+    cached) -- or (None, False) when it would not fit in half of the free HBM."""
+    key = None if sel.key is None else parent_key + ("subset", sel.key)
+    need = _native.subset_device_bytes(sel.count, c.shape[1], c.dtype, compute)
+    with _cache_lock:
+        hit = _cache.get(key) if key is not None else None
+        if hit is not None:
+            _cache.move_to_end(key)
+            return hit[1].acquire(), False
+        if not _fits_device(need):
+            return None, False
+        dc = parent.subset(sel.mask if sel.mask is not None else sel.ids)
+        if key is None or need > _CACHE_BYTES:
+            return dc.acquire(), True
+        _cache[key] = ((sel.keep, sel.mask), dc)  # the entry keeps the selection's buffers alive
+        total = sum(v[1].nbytes for v in _cache.values())
+        while total > _CACHE_BYTES and len(_cache) > 1:
+            _, (_, old) = _cache.popitem(last=False)
+            total -= old.nbytes
+            old.close()  # freed now, or by its last in-flight user
+        return dc.acquire(), False
+
+
+def _topk_subset(q, c, original, rv, sel: _Selection, kk: int, metric_id: int, compute: str):
+    """Top-kk of q among the selected rows of c, indices numbering c.  On the
+    device from the cached corpus handle when there is one (one GPU); else the
+    host fallback: the selected rows taken on the host, the uncached search,
+    and the indices mapped back through the ids."""
+    dc, transient = None, False
+    if len(_native.get_devices()) <= 1:
+        parent_key = _corpus_key(original, rv, c, compute)
+        parent = _cached_corpus(original, rv, c, compute) if parent_key is not None else None
+        if parent is not None:
+            try:
+                dc, transient = _cached_subset(parent, parent_key, sel, c, compute)
+            finally:
+                parent.release()
+    if dc is not None:
+        try:
+            idx, sc = dc.topk(q, kk, metric_id)
+            if not transient:
+                _reaccount_cache(dc)
+        finally:
+            dc.release()
+            if transient:
+                dc.close()
+        return idx, sc
+    ids = sel.row_ids()
+    idx, sc = _native.topk_host(q, np.ascontiguousarray(c[ids]), kk, metric_id,
+                                compute=_native.COMPUTE_BF16 if compute == "bf16" else _native.COMPUTE_F32)
+    return ids[idx], sc
 
 
 # ---------------------------------------------------------------------------
@@ -361,10 +504,16 @@ def _wrap(arrow_arr: pa.Array, name: str, polars_out: bool):
 # ---------------------------------------------------------------------------
 # Public extension functions
 # ---------------------------------------------------------------------------
-def _topk(left, right, k, metric, compute="f32"):
+def _topk(left, right, k, metric, compute="f32", subset=None):
     """src/lib.rs:33-55 -> src/matmul.rs:473-519 topk_impl.  compute="bf16"
     (an extension): both columns are read as f32 whatever their dtype and
-    searched on the bf16 path (the numpy-level ``topk``'s compute="bf16")."""
+    searched on the bf16 path (the numpy-level ``topk``'s compute="bf16").
+    subset (an extension): search only the selected rows of ``right`` -- a
+    Boolean Series / Arrow array / numpy mask of len(right) (nulls count as
+    false) or integer row ids (sorted and de-duplicated here).  The returned
+    ``index`` values number ``right``, k clips to the number of selected rows
+    (the reference's clip-to-n rule on the searched rows), and an empty
+    selection raises what an empty corpus raises."""
     k = _as_usize(k)
     if not isinstance(metric, str):
         raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
@@ -373,6 +522,7 @@ def _topk(left, right, k, metric, compute="f32"):
     t = time.perf_counter()
     lv = _to_arrow(left)
     rv = _to_arrow(right)
+    sel = _check_subset(subset, _nrows(rv)) if subset is not None else None
     if _nrows(lv) == 0:  # src/matmul.rs:480-487
         empty = pa.array([], type=pa.large_list(_TOPK_STRUCT))
         return _wrap(empty, "topk", polars_out)
@@ -387,11 +537,16 @@ def _topk(left, right, k, metric, compute="f32"):
     t = _lap("extract", t)
     if q.shape[1] != c.shape[1]:  # src/matmul.rs:433-441
         raise _dim_mismatch(q.shape[1], c.shape[1])
-    kk = min(k, c.shape[0])  # src/matmul.rs:443
+    kk = min(k, c.shape[0] if sel is None else sel.count)  # src/matmul.rs:443
     m = q.shape[0]
     if kk == 0:
         idx = np.zeros((m, 0), dtype=np.uint32)
         sc = np.zeros((m, 0), dtype=np.float64)
+    elif sel is not None:
+        _apply_devices_env()
+        idx, sc = _topk_subset(q, c, right, rv, sel, kk, metric_id, compute)
+        t = _lap("device", t)
+        sc = sc.astype(np.float64, copy=False)
     else:
         _apply_devices_env()
         # (an f32 or bf16 handle sharded over several GPUs serves k <= 1024;
