@@ -21,6 +21,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace pmm;
@@ -213,6 +214,36 @@ int next_pow2(int x, int lo = 64) {
 }
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// What the rows of one type (PMM_DTYPE_*) look like on the device, wherever
+// they sit (a call's arena, a corpus handle's shard): the one statement of the
+// element and norm widths, the padding rule and the norm arrays kept per row.
+struct RowKind {
+  size_t elem;       // bytes of a row element
+  int64_t align;     // elements a row's zero-padded stride is a multiple of (the kernels' K step)
+  size_t norm_elem;  // bytes of a norm
+  // norm arrays per row, n entries each.  The f32 layout (f32 and bf16 rows,
+  // the latter's of the rounded rows): [norm | 1/norm | squared norm | squared
+  // norm * (1 - 2^-18)]; f64: [norm | squared norm].
+  int norm_arrays;
+  int euclid_array;  // which of them euclidean reads (cosine reads array 0, dot none)
+  // the offset, in norms, of the array `metric` reads in a shard of n rows (-1: none)
+  int64_t norm_offset(int metric, int64_t n) const {
+    return metric == kMetricCosine ? 0 : metric == kMetricEuclidean ? euclid_array * n : -1;
+  }
+};
+RowKind row_kind(int dtype) {
+  switch (dtype) {
+    case PMM_DTYPE_F64: return RowKind{8, 16, 8, 2, 1};
+    case PMM_DTYPE_BF16: return RowKind{2, kBf16DAlign, 4, 4, 2};
+    default: return RowKind{4, 32, 4, 4, 2};
+  }
+}
+// The row stride, in elements, of d columns of this row type.
+int64_t padded_dim(int dtype, int64_t d) {
+  const int64_t a = row_kind(dtype).align;
+  return cdiv(d, a) * a;
+}
+
 struct Timed {
   hipStream_t s;
   TimingRec rec{};
@@ -327,7 +358,7 @@ int choose_variant(int mode, int capg, int64_t m = 1 << 30, int64_t n = 1 << 30,
 bool bf16_ws_enabled(int capg, int64_t d) {
   const char *e = getenv("PMM_BF16_WS");
   if (e && atoi(e) == 0) return false;
-  const int dp = (int)(cdiv(d, kBf16DAlign) * kBf16DAlign);
+  const int dp = (int)padded_dim(PMM_DTYPE_BF16, d);
   return capg <= kBf16WsMaxCapg && gemm_bf16_ws_lds_bytes(capg, dp) <= 160 * 1024;
 }
 
@@ -357,7 +388,7 @@ bool bf16_ff_enabled(int64_t k, int64_t n, int64_t d) {
   const char *e = getenv("PMM_BF16_FF");
   const int mode = e ? atoi(e) : 0;  // 2 (tests): whenever the kernel can run, however bad the guess
   if (mode == 0) return false;
-  const int dp = (int)(cdiv(d, kBf16DAlign) * kBf16DAlign);
+  const int dp = (int)padded_dim(PMM_DTYPE_BF16, d);
   const int64_t ns = ff_guess_ns(n);
   const bool guess_ok = (double)n * ff_guess_j() / (double)ns >= 4.0 * (double)k;
   return ns >= 256 && ns >= ff_guess_j() && (guess_ok || mode == 2) && k + 64 <= 8192 && n < (1 << 26) &&
@@ -753,7 +784,7 @@ hipError_t run_fused_f32(GemmF32Args a, const Plan &p, uint32_t index_base, uint
 // Whether the bf16 MFMA kernels take the shape themselves (see the bf16
 // compute path below for their limits).
 bool bf16_native(int64_t d, int64_t k, int64_t n) {
-  return cdiv(d, kBf16DAlign) * kBf16DAlign <= kBf16MaxD && n < (int64_t(1) << 27) &&
+  return padded_dim(PMM_DTYPE_BF16, d) <= kBf16MaxD && n < (int64_t(1) << 27) &&
          next_pow2((int)std::min<int64_t>(k, 1 << 20) + 64, 128) <= kBf16MaxCapg;
 }
 constexpr int64_t kScreenMaxK = 192;      // k + its 2 eps band + a drain round fit capg = 512
@@ -781,7 +812,7 @@ bool screen_wanted(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
   if (metric != kMetricCosine || k > kScreenMaxK || !bf16_native(d, k, n)) return false;
   const char *e = getenv("PMM_F32_SCREEN");
   if (e) return atoi(e) != 0;
-  const double work = (double)m * (double)n * (double)(cdiv(d, 32) * 32);
+  const double work = (double)m * (double)n * (double)padded_dim(PMM_DTYPE_F32, d);
   return work >= kScreenMinWork || (work >= kScreenMinWorkLongCorpus && n >= 100 * m);
 }
 // A corpus' share of the screen's inputs, computed once and kept by an f32
@@ -794,15 +825,15 @@ struct ScreenImage {
   float max_rel = 0.0f;    // the maximum residual bound over the rows
 };
 size_t screen_image_bytes(int64_t n, int64_t d) {
-  return (size_t)n * (cdiv(d, kBf16DAlign) * kBf16DAlign) * 2 + (size_t)n * 8;
+  return (size_t)n * padded_dim(PMM_DTYPE_BF16, d) * 2 + (size_t)n * 8;
 }
 // b: the bf16 kernel's plan of the call (padded D = roundup(d, 128));
 // corpus_image: the caller supplies a ScreenImage, so the workspace leaves out
 // the corpus' bf16 rows and per-row residuals
 void plan_screen(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int cus, const Plan &b, ScreenPlan &sp,
                  bool corpus_image = false) {
-  sp.dpb = cdiv(d, kBf16DAlign) * kBf16DAlign;
-  sp.dp = cdiv(d, 32) * 32;
+  sp.dpb = padded_dim(PMM_DTYPE_BF16, d);
+  sp.dp = padded_dim(PMM_DTYPE_F32, d);
   sp.ext = corpus_image;
   size_t off = b.total;
   sp.off_qb = off;
@@ -887,11 +918,11 @@ struct TopkRoute {
 TopkRoute route_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int compute, int cus,
                      bool allow_screen, bool allow_ff, bool corpus_image = false) {
   TopkRoute r;
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   if (compute == PMM_COMPUTE_BF16) {
     if (bf16_native(d, k, n)) {
       r.kind = Route::kBf16Native;
-      plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
+      plan_topk(m, n, padded_dim(PMM_DTYPE_BF16, d), k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
       r.total = r.p.total;
       return r;
     }
@@ -913,7 +944,7 @@ TopkRoute route_topk(int64_t m, int64_t n, int64_t d, int64_t k, int metric, int
   if (allow_screen && screen_wanted(m, n, d, k, metric)) {
     // the wave-specialised kernel, with room above k for the kept band before
     // a drain round could pass the segment's end
-    plan_topk(m, n, cdiv(d, kBf16DAlign) * kBf16DAlign, k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
+    plan_topk(m, n, padded_dim(PMM_DTYPE_BF16, d), k, metric, cus, r.p, PMM_COMPUTE_BF16, allow_ff);
     if (r.p.variant == -2 && r.p.capg <= kBf16WsMaxCapg && r.p.ctrig >= k + k / 2 + 32 &&
         r.p.ctrig <= r.p.capg - 64) {
       r.kind = Route::kF32Screened;
@@ -978,7 +1009,7 @@ int rerun_rows(const void *q, int64_t ld_bytes, int64_t row_bytes, const int *ro
 int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc, int64_t n,
                    int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, float *out_score,
                    char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr) {
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
   if (c_norms) cn = const_cast<float *>(c_norms);
   // Threshold seeding.  When every unit spans few corpus tiles (small
@@ -1067,7 +1098,7 @@ int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const 
 int topk_f32_materialised(const MatPlan &p, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
                           int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
                           float *out_score, char *w, hipStream_t s, int cus, const float *c_norms) {
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
   float *sc = (float *)(w + p.off_scores);
   if (c_norms) cn = const_cast<float *>(c_norms);
@@ -1263,7 +1294,7 @@ int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, in
                          const float *c_norms = nullptr, bool keep_gthr = false,
                          const ScreenImage *img = nullptr) {
   const int cus = g_dev[dev].cus;
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   // What the screen asks of a call and route_topk cannot see (row strides and
   // alignment of the rows it rounds, norms it computes itself or reads beside
   // a handle's image, thresholds it starts from zero): without it the call
@@ -1306,7 +1337,7 @@ int topk_bf16_native(const Plan &p, const uint16_t *q, int64_t ldq, int64_t m, c
                      int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
                      float *out_score, char *w, hipStream_t s, const float *q_norms = nullptr,
                      const float *c_norms = nullptr) {
-  const int64_t dp = cdiv(d, kBf16DAlign) * kBf16DAlign;
+  const int64_t dp = padded_dim(PMM_DTYPE_BF16, d);
   // the precomputed arrays live outside w (a bf16 corpus handle's, and the
   // query norms its call's rounding pass wrote): the memset below cannot
   // reach them, and the workspace's own norm slots stay unused
@@ -1505,14 +1536,15 @@ int upload_padded(void *dst, const void *src, int64_t rows, int64_t d, int64_t d
   return PMM_OK;
 }
 
-// The end of a host f32 top-k call: both m x k result lists to the host, and
-// the call's one synchronisation.
-int download_lists(uint32_t *out_idx, float *out_score, const void *idx, const void *score, int64_t m, int64_t k,
+// The end of a host top-k call: both m x k result lists (f32 or f64 scores)
+// to the host, and the call's one synchronisation.
+template <typename Score>
+int download_lists(uint32_t *out_idx, Score *out_score, const void *idx, const void *score, int64_t m, int64_t k,
                    hipStream_t s) {
   {
     Timed t("d2h", s);
     HIP_TRY(hipMemcpyAsync(out_idx, idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_score, score, (size_t)m * k * sizeof(Score), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
   return PMM_OK;
@@ -1554,7 +1586,7 @@ constexpr int kChunks = 4;
 
 int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
                           int metric, uint32_t *out_idx, float *out_score, int dev, hipStream_t s) {
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   int64_t bnd[kChunks + 1];
   bnd[0] = 0;
   bnd[1] = std::max<int64_t>(k, n / 16);
@@ -1648,16 +1680,32 @@ int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, 
 // list is the exact top-k of its rows under the total order, so the merged
 // list equals the one-device result bit for bit.
 // ---------------------------------------------------------------------------
-struct ShardSrc {
+// One shard of a sharded search, T = float (ShardSrc: topk_sharded, f32 or
+// bf16 compute) or double (ShardSrc64: topk_sharded_f64).
+template <typename T>
+struct ShardSrcT {
   int dev;
   int64_t lo, rows;
-  const float *host;       // host corpus rows [lo, lo + rows), row stride d, or
-  const float *dev_rows;   // resident padded rows (stride dp) of a corpus handle
-  const float *dev_norms;  // with dev_rows: the handle's norms of this metric ([rows | rows factors])
-  // a bf16 handle's shard instead of dev_rows: zero-padded bf16 rows of stride
-  // roundup(d, 128), with dev_norms as above (of the rounded rows)
-  const uint16_t *dev_rows16 = nullptr;
+  const T *host;         // host corpus rows [lo, lo + rows), row stride d, or
+  const void *dev_rows;  // a corpus handle's resident rows at their padded stride: T, or bf16 under bf16 compute
+  const T *dev_norms;    // with dev_rows: the handle's norm array of this metric (nullptr for dot)
 };
+using ShardSrc = ShardSrcT<float>;
+using ShardSrc64 = ShardSrcT<double>;
+
+// The shards of n host rows (row stride d) over a device list: one per listed
+// device, at most n, contiguous, sizes differing by at most one.
+int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }  // shard g: rows [n g / G, n (g + 1) / G)
+template <typename T>
+std::vector<ShardSrcT<T>> host_shards(const std::vector<int> &devs, const T *c, int64_t n, int64_t d) {
+  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
+  std::vector<ShardSrcT<T>> sh(G);
+  for (int g = 0; g < G; g++) {
+    const int64_t lo = shard_lo(n, G, g), hi = shard_lo(n, G, g + 1);
+    sh[g] = ShardSrcT<T>{devs[g], lo, hi - lo, c + lo * d, nullptr, nullptr};
+  }
+  return sh;
+}
 
 std::mutex g_peer_mu;
 bool g_peer_tried[kMaxDevices][kMaxDevices];
@@ -1673,6 +1721,78 @@ void enable_peer(int dev, int peer) {
   if (hipDeviceCanAccessPeer(&can, dev, peer) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(peer, 0);
   (void)hipGetLastError();
 }
+
+// What the two sharded searches (topk_sharded, topk_sharded_f64) share.  Their
+// per-device plans (DevPlan, Dev64) differ in their offsets; both carry dev,
+// the thread's stream s on it, the arena base and the plan's total bytes.
+//
+// The distinct devices of the list, appended to dps in order of first use;
+// returns shard -> index into dps.  (Pure: plan_sharded runs without a GPU.)
+template <typename Dev, typename T>
+std::vector<int> distinct_devices(const std::vector<ShardSrcT<T>> &sh, std::vector<Dev> &dps) {
+  std::vector<int> plan_of(sh.size());
+  for (size_t g = 0; g < sh.size(); g++) {
+    int j = 0;
+    while (j < (int)dps.size() && dps[j].dev != sh[g].dev) j++;
+    if (j == (int)dps.size()) {
+      Dev p;
+      p.dev = sh[g].dev;
+      dps.push_back(p);
+    }
+    plan_of[g] = j;
+  }
+  return plan_of;
+}
+
+// Every planned device's stream of this thread and an arena of its plan's size.
+template <typename Dev>
+int acquire_devices(std::vector<Dev> &dps) {
+  for (auto &p : dps) {
+    HIP_TRY(hipSetDevice(p.dev));
+    if (int rc = thread_stream(p.dev, &p.s)) return rc;
+    void *b;
+    if (int rc = arena(p.dev, p.s, p.total, &b)) return rc;
+    p.base = (char *)b;
+  }
+  return PMM_OK;
+}
+
+// The per-shard completion events of a sharded search and its one exit: a
+// failure first drains every device's stream (queued work writes into the
+// arenas), then the events are destroyed on their devices.
+template <typename Dev, typename T>
+struct ShardedExit {
+  std::vector<Dev> &dps;
+  const std::vector<ShardSrcT<T>> &sh;
+  std::vector<hipEvent_t> ev;
+  ShardedExit(std::vector<Dev> &dps_, const std::vector<ShardSrcT<T>> &sh_) : dps(dps_), sh(sh_), ev(sh_.size(), nullptr) {}
+  int operator()(int code) {
+    if (code != PMM_OK)
+      for (auto &p : dps) {
+        (void)hipSetDevice(p.dev);
+        (void)hipStreamSynchronize(p.s);
+      }
+    for (size_t g = 0; g < ev.size(); g++)
+      if (ev[g]) {
+        (void)hipSetDevice(sh[g].dev);
+        (void)hipEventDestroy(ev[g]);
+      }
+    return code;
+  }
+};
+// (in a function with a ShardedExit named `finish`)
+#define SH_TRY(expr)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return finish(fail(PMM_ERR_HIP, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), \
+                         __FILE__, __LINE__, #expr));                                     \
+  } while (0)
+#define SH_RC(expr)                        \
+  do {                                     \
+    int rc_ = (expr);                      \
+    if (rc_ != PMM_OK) return finish(rc_); \
+  } while (0)
 
 // Memory plan of topk_sharded (pure: no HIP call, so the CPU tests check it
 // through pmm_shard_plan).  One DevPlan per DISTINCT device of the list: that
@@ -1698,24 +1818,14 @@ void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t
                   ShardLayout &L) {
   const int G = (int)sh.size();
   const bool bf16 = compute == PMM_COMPUTE_BF16;
-  const int64_t dp = bf16 ? cdiv(d, kBf16DAlign) * kBf16DAlign : cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(bf16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, d);
   const size_t list_bytes = (size_t)2 * m * k * 4;
   L.dps.clear();
-  L.plan_of.assign(G, 0);
+  L.plan_of = distinct_devices(sh, L.dps);
   L.off_c.assign(G, 0);
   L.off_cb.assign(G, 0);
   L.off_list.assign(G, 0);
   L.route.assign(G, TopkRoute());
-  for (int g = 0; g < G; g++) {
-    int j = 0;
-    while (j < (int)L.dps.size() && L.dps[j].dev != sh[g].dev) j++;
-    if (j == (int)L.dps.size()) {
-      DevPlan p;
-      p.dev = sh[g].dev;
-      L.dps.push_back(p);
-    }
-    L.plan_of[g] = j;
-  }
   for (auto &p : L.dps) {
     size_t off = 0;
     p.off_q = off;  // f32: padded rows; bf16: f32 staging rows (stride d)
@@ -1746,14 +1856,10 @@ void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t
 int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, int compute,
                  const std::vector<ShardSrc> &sh, uint32_t *out_idx, float *out_score) {
   const int G = (int)sh.size();
-  int cur = 0;
-  HIP_TRY(hipGetDevice(&cur));
-  struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-  } restore{cur};
+  DevScope restore;
+  HIP_TRY(hipGetDevice(&restore.prev));
   const bool bf16 = compute == PMM_COMPUTE_BF16;
-  const int64_t dp = bf16 ? cdiv(d, kBf16DAlign) * kBf16DAlign : cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(bf16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, d);
   const int root = sh[0].dev;
   const size_t list_bytes = (size_t)2 * m * k * 4;
   for (const ShardSrc &x : sh)
@@ -1765,39 +1871,9 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
   const std::vector<size_t> &off_c = L.off_c, &off_cb = L.off_cb, &off_list = L.off_list;
   DevPlan &rp = dps[plan_of[0]];
   const size_t off_gather = L.off_gather, off_out = L.off_out;
-  for (auto &p : dps) {
-    HIP_TRY(hipSetDevice(p.dev));
-    if (int rc = thread_stream(p.dev, &p.s)) return rc;
-    void *b;
-    if (int rc = arena(p.dev, p.s, p.total, &b)) return rc;
-    p.base = (char *)b;
-  }
-  std::vector<hipEvent_t> ev(G, nullptr);
-  auto finish = [&](int code) {
-    if (code != PMM_OK)
-      for (auto &p : dps) {
-        (void)hipSetDevice(p.dev);
-        (void)hipStreamSynchronize(p.s);
-      }
-    for (int g = 0; g < G; g++)
-      if (ev[g]) {
-        (void)hipSetDevice(sh[g].dev);
-        (void)hipEventDestroy(ev[g]);
-      }
-    return code;
-  };
-#define SH_TRY(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return finish(fail(PMM_ERR_HIP, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), \
-                         __FILE__, __LINE__, #expr));                                     \
-  } while (0)
-#define SH_RC(expr)                   \
-  do {                                \
-    int rc_ = (expr);                 \
-    if (rc_ != PMM_OK) return finish(rc_); \
-  } while (0)
+  if (int rc = acquire_devices(dps)) return rc;
+  ShardedExit<DevPlan, float> finish(dps, sh);
+  std::vector<hipEvent_t> &ev = finish.ev;
   // queries to every device
   for (auto &p : dps) {
     SH_TRY(hipSetDevice(p.dev));
@@ -1818,7 +1894,7 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
     uint32_t *li = (uint32_t *)(p.base + off_list[g]);
     float *ls = (float *)(li + (size_t)m * k);
     if (bf16) {
-      const uint16_t *cb = x.dev_rows16;
+      const uint16_t *cb = (const uint16_t *)x.dev_rows;
       if (x.host) {
         SH_TRY(hipMemcpyAsync(p.base + off_c[g], x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
         SH_TRY(launch_f32_to_bf16((const float *)(p.base + off_c[g]), x.rows, d, d,
@@ -1830,7 +1906,7 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
                                   metric, (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev, nullptr,
                                   x.host ? nullptr : x.dev_norms));
     } else {
-      const float *c = x.dev_rows;
+      const float *c = (const float *)x.dev_rows;
       if (x.host) {
         SH_RC(upload_padded(p.base + off_c[g], x.host, x.rows, d, dp, 4, p.s));
         c = (const float *)(p.base + off_c[g]);
@@ -1861,8 +1937,6 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
   SH_TRY(hipMemcpyAsync(out_idx, ma.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipMemcpyAsync(out_score, ma.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipStreamSynchronize(rp.s));
-#undef SH_TRY
-#undef SH_RC
   return finish(PMM_OK);
 }
 
@@ -1951,7 +2025,7 @@ int topk_f64_materialised(const double *dq, int64_t ldq, int64_t m, const double
     if (cn_pre) cn = (double *)cn_pre;
     else HIP_TRY(launch_norms_f64(dc, n, d, ldc, sq, cn, s));
   }
-  const int64_t dp = cdiv(d, 16) * 16;
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
   for (int64_t r0 = 0; r0 < m; r0 += p.rows) {
     const int64_t rows = std::min<int64_t>(p.rows, m - r0);
     {
@@ -1993,7 +2067,7 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
     return topk_f64_materialised(dq, ldq, m, dc, ldc, n, d, k, metric, index_base, oi, os, w, s, cn_pre);
   F64Plan p;
   plan_f64(m, n, k, p);
-  const int64_t dp = cdiv(d, 16) * 16;
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
   double *qn = (double *)(w + p.off_qn), *cn = (double *)(w + p.off_cn);
   unsigned *flag = (unsigned *)(w + p.off_flag);
   if (metric != kMetricDot) {
@@ -2099,24 +2173,12 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
 // its rows under the f64 total order, so the merged list equals the
 // one-device result bit for bit (indices and f64 scores).
 // ---------------------------------------------------------------------------
-struct ShardSrc64 {
-  int dev;
-  int64_t lo, rows;
-  const double *host;       // host rows [lo, lo + rows), row stride d, or
-  const double *dev_rows;   // a corpus handle's resident padded rows (stride dp)
-  const double *dev_norms;  // with dev_rows: the handle's norms of this metric (nullptr for dot)
-};
-
 int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metric, const std::vector<ShardSrc64> &sh,
                      uint32_t *out_idx, double *out_score) {
   const int G = (int)sh.size();
-  int cur = 0;
-  HIP_TRY(hipGetDevice(&cur));
-  struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-  } restore{cur};
-  const int64_t dp = cdiv(d, 16) * 16;
+  DevScope restore;
+  HIP_TRY(hipGetDevice(&restore.prev));
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
   const int root = sh[0].dev;
   for (const ShardSrc64 &x : sh)
     if (int rc = probe_device(x.dev)) return rc;
@@ -2127,15 +2189,12 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
     size_t off_q = 0, off_ws = 0, ws_bytes = 0, off_flags = 0, total = 0;
   };
   std::vector<Dev64> dps;
-  std::vector<int> plan_of(G), slot(G);
+  const std::vector<int> plan_of = distinct_devices(sh, dps);
+  std::vector<int> slot(G);
   std::vector<int64_t> kg(G);
   std::vector<bool> fused(G);
   std::vector<size_t> off_c(G), off_tmp(G), off_li(G), off_ls(G);
   for (int g = 0; g < G; g++) {
-    int j = 0;
-    while (j < (int)dps.size() && dps[j].dev != sh[g].dev) j++;
-    if (j == (int)dps.size()) dps.push_back(Dev64{sh[g].dev});
-    plan_of[g] = j;
     kg[g] = std::min<int64_t>(k, sh[g].rows);
     fused[g] = f64_use_fused(m, sh[g].rows, kg[g]);
   }
@@ -2168,39 +2227,9 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
   const size_t off_gi = rp.total, off_gs = al256(off_gi + (size_t)G * m * k * 4);
   const size_t off_oi = al256(off_gs + (size_t)G * m * k * 8), off_os = al256(off_oi + (size_t)m * k * 4);
   rp.total = al256(off_os + (size_t)m * k * 8);
-  for (auto &p : dps) {
-    HIP_TRY(hipSetDevice(p.dev));
-    if (int rc = thread_stream(p.dev, &p.s)) return rc;
-    void *b;
-    if (int rc = arena(p.dev, p.s, p.total, &b)) return rc;
-    p.base = (char *)b;
-  }
-  std::vector<hipEvent_t> ev(G, nullptr);
-  auto finish = [&](int code) {
-    if (code != PMM_OK)
-      for (auto &p : dps) {
-        (void)hipSetDevice(p.dev);
-        (void)hipStreamSynchronize(p.s);
-      }
-    for (int g = 0; g < G; g++)
-      if (ev[g]) {
-        (void)hipSetDevice(sh[g].dev);
-        (void)hipEventDestroy(ev[g]);
-      }
-    return code;
-  };
-#define SH_TRY(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return finish(fail(PMM_ERR_HIP, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), \
-                         __FILE__, __LINE__, #expr));                                     \
-  } while (0)
-#define SH_RC(expr)                        \
-  do {                                     \
-    int rc_ = (expr);                      \
-    if (rc_ != PMM_OK) return finish(rc_); \
-  } while (0)
+  if (int rc = acquire_devices(dps)) return rc;
+  ShardedExit<Dev64, double> finish(dps, sh);
+  std::vector<hipEvent_t> &ev = finish.ev;
   for (auto &p : dps) {
     SH_TRY(hipSetDevice(p.dev));
     SH_RC(upload_padded(p.base + p.off_q, q, m, d, dp, 8, p.s));
@@ -2210,7 +2239,7 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
   auto run_shard = [&](int g, bool materialised) -> int {
     Dev64 &p = dps[plan_of[g]];
     const ShardSrc64 &x = sh[g];
-    const double *c = x.dev_rows;
+    const double *c = (const double *)x.dev_rows;
     if (x.host) c = (const double *)(p.base + off_c[g]);
     uint32_t *li = (uint32_t *)(p.base + off_li[g]);
     double *ls = (double *)(p.base + off_ls[g]);
@@ -2292,10 +2321,10 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
   SH_TRY(hipMemcpyAsync(out_idx, ma.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipMemcpyAsync(out_score, ma.out_score, (size_t)m * k * 8, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipStreamSynchronize(rp.s));
-#undef SH_TRY
-#undef SH_RC
   return finish(PMM_OK);
 }
+#undef SH_TRY
+#undef SH_RC
 
 std::vector<int> devices_snapshot() {
   std::lock_guard<std::mutex> lk(g_devs_mu);
@@ -2312,9 +2341,6 @@ int list_root() {
   return g_devs.empty() ? -1 : g_devs[0];
 }
 
-// shard g of n rows over G shards: rows [n g / G, n (g + 1) / G)
-int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }
-
 }  // namespace
 
 // Device-resident corpus (pmm_corpus_*): padded f32 rows in HBM plus the
@@ -2328,14 +2354,16 @@ int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }
 // A bf16 corpus (pmm_corpus_create_bf16) keeps the rows rounded to bf16 at
 // stride roundup(d, 128) -- what the bf16 kernels read -- and the f32 norms of
 // the rounded rows in the f32 layout, both from one round_norms_bf16 pass.
+// What the three kinds of handle store differs only by row_kind(dtype).
 struct CorpusShard {
   int device = 0;
-  int64_t lo = 0, n = 0;       // rows [lo, lo + n) of the corpus
-  float *data = nullptr;       // f32: n x dp
-  float *norms = nullptr;      // f32: [cosine: n norms | n 1/norm][euclid: n sq | n sq*(1-2^-18)]
-  double *data64 = nullptr;    // f64: n x dp
-  double *norms64 = nullptr;   // f64: [cosine: n norms][euclid: n sq]
-  uint16_t *data16 = nullptr;  // bf16: n x dp bit patterns (norms: the f32 layout, of the rounded rows)
+  int64_t lo = 0, n = 0;  // rows [lo, lo + n) of the corpus
+  void *rows = nullptr;   // n x dp elements of the handle's row type
+  void *norms = nullptr;  // the row type's norm arrays, n norms each (RowKind)
+  template <typename T>
+  const T *rows_as() const {
+    return (const T *)rows;
+  }
 };
 struct pmm_corpus {
   int64_t n = 0, d = 0, dp = 0;
@@ -2363,6 +2391,34 @@ static void free_screen_image(const ScreenImage *img) {
   delete img;
 }
 
+// The norm array of shard x that `metric` reads (nullptr for dot); T is the
+// row type's norm type.
+template <typename T>
+static const T *shard_norms(const pmm_corpus *h, const CorpusShard &x, int metric) {
+  const int64_t off = row_kind(h->dtype).norm_offset(metric, x.n);
+  return off < 0 ? nullptr : (const T *)x.norms + off;
+}
+
+// A ScreenImage with the buffers for n rows of d columns on the current
+// device, when they fit in half of the free HBM; else, or when an allocation
+// fails, nullptr with the HIP error cleared (the caller goes on without one).
+static ScreenImage *alloc_screen_image(int64_t n, int64_t d) {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || screen_image_bytes(n, d) > free_b / 2) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  ScreenImage *ni = new ScreenImage();
+  hipError_t e = hipMalloc(&ni->cb, (size_t)n * padded_dim(PMM_DTYPE_BF16, d) * 2);
+  if (e == hipSuccess) e = hipMalloc(&ni->crel, (size_t)n * 8);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    free_screen_image(ni);
+    return nullptr;
+  }
+  return ni;
+}
+
 // The handle's ScreenImage on the current device (shard 0's) and stream s,
 // built and published on first use.  nullptr: the handle does not screen this
 // call -- the image does not fit in half of the free HBM or an allocation
@@ -2374,25 +2430,17 @@ static const ScreenImage *corpus_screen_image(const pmm_corpus *h, hipStream_t s
   std::lock_guard<std::mutex> lk(h->screen_mu);
   img = h->screen.load(std::memory_order_acquire);
   if (img || h->screen_never.load(std::memory_order_acquire)) return img;
-  const CorpusShard &x = h->shards[0];
-  const int64_t dpb = cdiv(h->d, kBf16DAlign) * kBf16DAlign;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || screen_image_bytes(h->n, h->d) > free_b / 2) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  ScreenImage *ni = new ScreenImage();
+  ScreenImage *ni = alloc_screen_image(h->n, h->d);
+  if (!ni) return nullptr;
   unsigned *scal = nullptr;  // [0] max residual bound over the safe rows, [1] any unsafe row
   unsigned hs[2] = {0u, 0u};
-  hipError_t e = hipMalloc(&ni->cb, (size_t)h->n * dpb * 2);
-  if (e == hipSuccess) e = hipMalloc(&ni->crel, (size_t)h->n * 8);
-  if (e == hipSuccess) e = hipMalloc(&scal, 256);
+  hipError_t e = hipMalloc(&scal, 256);
   if (e == hipSuccess) e = hipMemsetAsync(scal, 0, 8, s);
   if (e == hipSuccess) {
     // (the norms were computed at creation and stay)
     Timed t("corpus_image_build", s);
-    e = launch_screen_prepare(x.data, h->n, h->d, h->dp, ni->cb, dpb, nullptr, nullptr, ni->crel,
-                              (unsigned *)(ni->crel + h->n), scal, s);
+    e = launch_screen_prepare(h->shards[0].rows_as<float>(), h->n, h->d, h->dp, ni->cb, padded_dim(PMM_DTYPE_BF16, h->d),
+                              nullptr, nullptr, ni->crel, (unsigned *)(ni->crel + h->n), scal, s);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(hs, scal, 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -2459,26 +2507,18 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
   x.device = px.device;
   x.lo = 0;
   x.n = s;
-  const bool f64 = p->dtype == PMM_DTYPE_F64, b16 = p->dtype == PMM_DTYPE_BF16;
-  const size_t row_bytes = (size_t)p->dp * (f64 ? 8 : b16 ? 2 : 4);  // a multiple of 128
-  void *rows = nullptr, *norms = nullptr;
-  hipError_t e = hipMalloc(&rows, (size_t)s * row_bytes);
-  if (f64) x.data64 = (double *)rows;
-  else if (b16) x.data16 = (uint16_t *)rows;
-  else x.data = (float *)rows;
-  if (e == hipSuccess) e = hipMalloc(&norms, (size_t)s * 16);  // f32 x 4 arrays, f64 x 2
-  if (f64) x.norms64 = (double *)norms;
-  else x.norms = (float *)norms;
+  const RowKind rk = row_kind(p->dtype);
+  const size_t row_bytes = (size_t)p->dp * rk.elem;  // a multiple of 128
+  hipError_t e = hipMalloc(&x.rows, (size_t)s * row_bytes);
+  if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)s * rk.norm_arrays * rk.norm_elem);
   if (e != hipSuccess) {
     pmm_corpus_destroy(h);
     return fail(PMM_ERR_HIP, "subset allocation failed on device %d: %s", px.device, hipGetErrorString(e));
   }
   {
     Timed t("subset_gather_rows", st);
-    const void *src = f64 ? (const void *)px.data64 : b16 ? (const void *)px.data16 : (const void *)px.data;
-    const void *nsrc = f64 ? (const void *)px.norms64 : (const void *)px.norms;
-    e = launch_subset_gather(src, map, s, (int)(row_bytes / 16), rows, nsrc, norms, f64 ? 2 : 4, f64 ? 8 : 4, p->n,
-                             -1, nullptr, st);
+    e = launch_subset_gather(px.rows, map, s, (int)(row_bytes / 16), x.rows, px.norms, x.norms, rk.norm_arrays,
+                             (int)rk.norm_elem, p->n, -1, nullptr, st);
   }
   // The parent's image, read once: its rows gathered too when they fit in
   // half of the free HBM (else, or when an allocation fails, the derived
@@ -2486,30 +2526,14 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
   const ScreenImage *pimg = p->dtype == PMM_DTYPE_F32 ? p->screen.load(std::memory_order_acquire) : nullptr;
   ScreenImage *ni = nullptr;
   unsigned hflag = 0u;
-  if (e == hipSuccess && pimg) {
-    const int64_t dpb = cdiv(p->d, kBf16DAlign) * kBf16DAlign;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && screen_image_bytes(s, p->d) <= free_b / 2) {
-      ni = new ScreenImage();
-      hipError_t ei = hipMalloc(&ni->cb, (size_t)s * dpb * 2);
-      if (ei == hipSuccess) ei = hipMalloc(&ni->crel, (size_t)s * 8);
-      if (ei != hipSuccess) {
-        (void)hipGetLastError();
-        free_screen_image(ni);
-        ni = nullptr;
-      }
-    } else {
-      (void)hipGetLastError();
+  if (e == hipSuccess && pimg && (ni = alloc_screen_image(s, p->d))) {
+    e = hipMemsetAsync(flag, 0, 4, st);
+    if (e == hipSuccess) {
+      Timed t("subset_gather_image", st);
+      e = launch_subset_gather(pimg->cb, map, s, (int)(padded_dim(PMM_DTYPE_BF16, p->d) * 2 / 16), ni->cb, pimg->crel,
+                               ni->crel, 2, 4, p->n, 1, flag, st);
     }
-    if (ni) {
-      e = hipMemsetAsync(flag, 0, 4, st);
-      if (e == hipSuccess) {
-        Timed t("subset_gather_image", st);
-        e = launch_subset_gather(pimg->cb, map, s, (int)(dpb * 2 / 16), ni->cb, pimg->crel, ni->crel, 2, 4, p->n, 1,
-                                 flag, st);
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st);
-    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
@@ -2530,6 +2554,145 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
   }
   *out = h;
   return PMM_OK;
+}
+
+// Shard x of a handle under creation, filled from the corpus' host rows `c` on
+// the current device (x's) and stream s, and waited for.  f32 and f64: the
+// rows padded on their way up, then the norms every call would compute
+// (src/metrics.rs:368-379), by the same kernels on the same padded rows --
+// bit-identical to the per-call ones.  bf16: the f32 rows only pass through
+// `stage` (x.n x d floats of the shard's own; the arena would keep them for
+// the thread's lifetime), rounded with the norms of both metrics in one pass.
+static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const void *c, float *stage, hipStream_t s) {
+  const int64_t d = h->d, dp = h->dp, n = x.n;
+  const size_t elem = h->dtype == PMM_DTYPE_F64 ? 8 : 4;  // of the HOST rows
+  const void *src = (const char *)c + (size_t)x.lo * d * elem;
+  hipError_t e1, e2;
+  if (h->dtype == PMM_DTYPE_BF16) {
+    float *nm = (float *)x.norms;
+    {
+      Timed t("h2d", s);
+      e1 = hipMemcpyAsync(stage, src, (size_t)n * d * 4, hipMemcpyHostToDevice, s);
+    }
+    Timed t("round_norms_bf16", s);
+    e2 = launch_round_norms_bf16(stage, n, d, d, (uint16_t *)x.rows, dp, nm, nm + n, nm + 2 * n, nm + 3 * n, s);
+  } else {
+    if (int rc = upload_padded(x.rows, src, n, d, dp, elem, s)) return rc;
+    if (h->dtype == PMM_DTYPE_F64) {
+      double *nm = (double *)x.norms;
+      e1 = launch_norms_f64(x.rows_as<double>(), n, d, dp, 0, nm, s);
+      e2 = launch_norms_f64(x.rows_as<double>(), n, d, dp, 1, nm + n, s);
+    } else {
+      float *nm = (float *)x.norms;
+      e1 = launch_norms_f32(x.rows_as<float>(), n, d, dp, 0, nm, nm + n, s);
+      e2 = launch_norms_f32(x.rows_as<float>(), n, d, dp, 1, nm + 2 * n, nm + 3 * n, s);
+    }
+  }
+  const hipError_t e3 = hipStreamSynchronize(s);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
+    return fail(PMM_ERR_HIP, h->dtype == PMM_DTYPE_BF16 ? "corpus rounding failed" : "corpus norms failed");
+  return PMM_OK;
+}
+
+// The creator behind pmm_corpus_create_f32 / _f64 / _bf16 (c: f32 host rows
+// for bf16).  With a device list the rows are sharded over it: one contiguous
+// shard per listed device, at most n.
+static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_corpus **out) {
+  if (!out) return fail(PMM_ERR_ARG, "null argument");
+  *out = nullptr;
+  int rc = validate_sizes(0, n, d, 0, false);
+  if (rc) return rc;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
+  if (!c) return fail(PMM_ERR_ARG, "null argument");
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
+  std::vector<int> devs = devices_snapshot();
+  if (devs.size() <= 1) devs.assign(1, dev);
+  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
+  const RowKind rk = row_kind(dtype);
+  pmm_corpus *h = new pmm_corpus();
+  h->n = n;
+  h->d = d;
+  h->dp = padded_dim(dtype, d);  // the stride rule of the row type's device entry
+  h->dtype = dtype;
+  h->shards.resize(G);
+  for (int g = 0; g < G; g++) {
+    CorpusShard &x = h->shards[g];
+    x.device = devs[g];
+    x.lo = shard_lo(n, G, g);
+    x.n = shard_lo(n, G, g + 1) - x.lo;
+  }
+  for (int g = 0; g < G && rc == PMM_OK; g++) {
+    CorpusShard &x = h->shards[g];
+    hipStream_t s = nullptr;
+    float *stage = nullptr;
+    hipError_t e = hipSetDevice(x.device);
+    if (e == hipSuccess) rc = thread_stream(x.device, &s);
+    if (rc) break;
+    if (e == hipSuccess) e = hipMalloc(&x.rows, (size_t)x.n * h->dp * rk.elem);
+    if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)x.n * rk.norm_arrays * rk.norm_elem);
+    if (e == hipSuccess && dtype == PMM_DTYPE_BF16) e = hipMalloc(&stage, (size_t)x.n * d * 4);
+    if (e != hipSuccess)
+      rc = fail(PMM_ERR_HIP, "corpus allocation failed on device %d: %s", x.device, hipGetErrorString(e));
+    else
+      rc = corpus_fill_shard(h, x, c, stage, s);
+    if (stage) (void)hipFree(stage);
+  }
+  (void)hipSetDevice(dev);
+  if (rc) {
+    pmm_corpus_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return PMM_OK;
+}
+
+// The call path of pmm_topk_f32_corpus / _f64_corpus / _bf16_corpus, Score
+// the type of the queries and of the scores.  A sharded handle goes to the
+// sharded search on its resident shards; a handle of one shard to `one_shard`
+// -- what differs by row type: the arena layout, the queries' way to the
+// device, the route and the executor -- on the shard's device and this
+// thread's stream there, which leaves the device lists in *oi and *os.
+template <typename Score, typename OneShard>
+static int corpus_topk(const pmm_corpus *h, int dtype, const Score *q, int64_t m, int64_t k, int metric,
+                       uint32_t *out_idx, Score *out_score, OneShard one_shard) {
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (h->dtype != dtype) return wrong_handle(h);
+  int rc = validate_sizes(m, h->n, h->d, k, true);
+  if (rc) return rc;
+  if ((rc = check_metric(metric))) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
+  if (h->shards.size() > 1) {
+    constexpr bool f64 = std::is_same<Score, double>::value;
+    // (the f32 and bf16 shards run the fused top-k only; f64 has a path for every k)
+    if (!f64 && k > kFusedMaxK)
+      return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
+                  (long long)k);
+    std::vector<ShardSrcT<Score>> sh(h->shards.size());
+    for (size_t g = 0; g < sh.size(); g++) {
+      const CorpusShard &x = h->shards[g];
+      sh[g] = ShardSrcT<Score>{x.device, x.lo, x.n, nullptr, x.rows, shard_norms<Score>(h, x, metric)};
+    }
+    if constexpr (f64)
+      return topk_sharded_f64(q, m, h->d, k, metric, sh, out_idx, out_score);
+    else
+      return topk_sharded(q, m, h->d, k, metric, dtype == PMM_DTYPE_BF16 ? PMM_COMPUTE_BF16 : PMM_COMPUTE_F32, sh,
+                          out_idx, out_score);
+  }
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  uint32_t *oi = nullptr;
+  Score *os = nullptr;
+  if ((rc = one_shard(x, dev, s, &oi, &os))) return rc;
+  if ((rc = remap_lists(h, oi, m, k, s))) return rc;
+  return download_lists(out_idx, out_score, oi, os, m, k, s);
 }
 
 // ===========================================================================
@@ -2700,7 +2863,7 @@ int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, 
   if (m == 0 || k == 0) return PMM_OK;
   if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   if (d == 0 || ldq % 4 != 0 || ldc % 4 != 0 || ldq < dp || ldc < dp || ((uintptr_t)q & 15) ||
       ((uintptr_t)c & 15))
     return fail(PMM_ERR_ARG,
@@ -2729,15 +2892,8 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     // a device list (pmm_set_devices): the corpus row-sharded over it, one
     // shard per listed device (at most n shards), results merged on the first
     const std::vector<int> devs = devices_snapshot();
-    if (devs.size() > 1 && k <= kFusedMaxK) {
-      const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-      std::vector<ShardSrc> sh(G);
-      for (int g = 0; g < G; g++) {
-        const int64_t lo = shard_lo(n, G, g), hi = shard_lo(n, G, g + 1);
-        sh[g] = ShardSrc{devs[g], lo, hi - lo, c + lo * d, nullptr, nullptr};
-      }
-      return topk_sharded(q, m, d, k, metric, compute, sh, out_idx, out_score);
-    }
+    if (devs.size() > 1 && k <= kFusedMaxK)
+      return topk_sharded(q, m, d, k, metric, compute, host_shards(devs, c, n, d), out_idx, out_score);
   }
   int dev;
   DevScope scope;
@@ -2746,7 +2902,7 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
   if ((rc = thread_stream(dev, &s))) return rc;
   if (compute == PMM_COMPUTE_BF16) {
     // f32 rows uploaded as they are, rounded to zero-padded bf16 rows on device
-    const int64_t db = cdiv(d, kBf16DAlign) * kBf16DAlign;
+    const int64_t db = padded_dim(PMM_DTYPE_BF16, d);
     const TopkRoute route = route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true);
     const size_t ws_need = route.total;
     size_t off_qf = 0, off_cf = al256((size_t)m * d * 4);
@@ -2769,7 +2925,7 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     if (rc) return rc;
     return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
   }
-  const int64_t dp = cdiv(d, 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   {
     const char *ce = getenv("PMM_CHUNKED_UPLOAD");  // 0: one upload, then one launch
     if (k <= kFusedMaxK && (size_t)n * dp * 4 >= kChunkedMinBytes && n >= 64 * k && !(ce && atoi(ce) == 0))
@@ -2803,7 +2959,7 @@ int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16
   if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
   if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
-  const int64_t dp = cdiv(d, kBf16DAlign) * kBf16DAlign;
+  const int64_t dp = padded_dim(PMM_DTYPE_BF16, d);
   if (ldq % 8 != 0 || ldc % 8 != 0 || ldq < dp || ldc < dp || ((uintptr_t)q & 15) ||
       ((uintptr_t)c & 15))
     return fail(PMM_ERR_ARG,
@@ -2836,22 +2992,15 @@ int pmm_topk_f64(const double *q, int64_t m, const double *c, int64_t n, int64_t
     // a device list (pmm_set_devices): the corpus row-sharded over it, as the
     // f32 path does (topk_sharded_f64)
     const std::vector<int> devs = devices_snapshot();
-    if (devs.size() > 1 && n > 1) {
-      const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-      std::vector<ShardSrc64> sh(G);
-      for (int g = 0; g < G; g++) {
-        const int64_t lo = shard_lo(n, G, g), hi = shard_lo(n, G, g + 1);
-        sh[g] = ShardSrc64{devs[g], lo, hi - lo, c + lo * d, nullptr, nullptr};
-      }
-      return topk_sharded_f64(q, m, d, k, metric, sh, out_idx, out_score);
-    }
+    if (devs.size() > 1 && n > 1)
+      return topk_sharded_f64(q, m, d, k, metric, host_shards(devs, c, n, d), out_idx, out_score);
   }
   int dev;
   DevScope scope;
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = cdiv(d, 16) * 16;
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
   size_t off_q = 0, off_c = al256((size_t)m * dp * 8), off_i = off_c + al256((size_t)n * dp * 8);
   size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
   void *base;
@@ -2864,13 +3013,7 @@ int pmm_topk_f64(const double *q, int64_t m, const double *c, int64_t n, int64_t
   uint32_t *oi = (uint32_t *)(b + off_i);
   double *os = (double *)(b + off_s);
   if ((rc = topk_f64_device_impl(dq, dp, m, dc, dp, n, d, k, metric, 0u, oi, os, b + off_w, s, fused))) return rc;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, oi, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, os, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return PMM_OK;
+  return download_lists(out_idx, out_score, oi, os, m, k, s);
 }
 
 int pmm_topk_f64_device(const double *q, int64_t ldq, int64_t m, const double *c, int64_t ldc, int64_t n,
@@ -2882,7 +3025,7 @@ int pmm_topk_f64_device(const double *q, int64_t ldq, int64_t m, const double *c
   if (m == 0 || k == 0) return PMM_OK;
   if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
-  const int64_t dp = cdiv(d, 16) * 16;
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
   if (d == 0 || ldq < dp || ldc < dp || ((uintptr_t)q & 15) || ((uintptr_t)c & 15))
     return fail(PMM_ERR_ARG,
                 "device f64 inputs need row strides >= roundup(d, 16) (zero-padded) and 16-byte-aligned "
@@ -2909,7 +3052,7 @@ int pmm_matmul_f32(const float *q, int64_t m, const float *c, int64_t n, int64_t
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = cdiv(std::max<int64_t>(d, 1), 32) * 32;
+  const int64_t dp = padded_dim(PMM_DTYPE_F32, std::max<int64_t>(d, 1));
   const int64_t rows_chunk =
       std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kMaterialiseBudget / ((size_t)n * 4))));
   size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_o = off_c + al256((size_t)n * dp * 4);
@@ -2944,7 +3087,7 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
   hipStream_t s;
   if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = cdiv(std::max<int64_t>(d, 1), 16) * 16;
+  const int64_t dp = padded_dim(PMM_DTYPE_F64, std::max<int64_t>(d, 1));
   const int64_t rows_chunk =
       std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kMaterialiseBudget / ((size_t)n * 8))));
   size_t off_q = 0, off_c = al256((size_t)m * dp * 8), off_o = off_c + al256((size_t)n * dp * 8);
@@ -3040,59 +3183,7 @@ static int merge_strided(const uint32_t *idx, const float *score, int64_t m, int
 }
 
 int pmm_corpus_create_f32(const float *c, int64_t n, int64_t d, pmm_corpus **out) {
-  if (!out) return fail(PMM_ERR_ARG, "null argument");
-  *out = nullptr;
-  int rc = validate_sizes(0, n, d, 0, false);
-  if (rc) return rc;
-  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
-  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
-  if (!c) return fail(PMM_ERR_ARG, "null argument");
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  std::vector<int> devs = devices_snapshot();
-  if (devs.size() <= 1) devs.assign(1, dev);
-  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-  pmm_corpus *h = new pmm_corpus();
-  h->n = n;
-  h->d = d;
-  h->dp = cdiv(d, 32) * 32;
-  h->shards.resize(G);
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    x.device = devs[g];
-    x.lo = shard_lo(n, G, g);
-    x.n = shard_lo(n, G, g + 1) - x.lo;
-  }
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    hipStream_t s;
-    hipError_t e = hipSetDevice(x.device);
-    if (e == hipSuccess && (rc = thread_stream(x.device, &s))) {
-      pmm_corpus_destroy(h);
-      return rc;
-    }
-    if (e == hipSuccess) e = hipMalloc(&x.data, (size_t)x.n * h->dp * 4);
-    if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)x.n * 4 * 4);
-    if (e != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus allocation failed on device %d: %s", x.device, hipGetErrorString(e));
-    }
-    if ((rc = upload_padded(x.data, c + x.lo * d, x.n, d, h->dp, 4, s))) {
-      pmm_corpus_destroy(h);
-      return rc;
-    }
-    hipError_t e1 = launch_norms_f32(x.data, x.n, d, h->dp, 0, x.norms, x.norms + x.n, s);
-    hipError_t e2 = launch_norms_f32(x.data, x.n, d, h->dp, 1, x.norms + 2 * x.n, x.norms + 3 * x.n, s);
-    hipError_t e3 = hipStreamSynchronize(s);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus norms failed");
-    }
-  }
-  (void)hipSetDevice(dev);
-  *out = h;
-  return PMM_OK;
+  return corpus_create(PMM_DTYPE_F32, c, n, d, out);
 }
 
 int pmm_corpus_destroy(pmm_corpus *h) {
@@ -3100,14 +3191,11 @@ int pmm_corpus_destroy(pmm_corpus *h) {
   int cur = 0;
   (void)hipGetDevice(&cur);
   for (auto &x : h->shards) {
-    if (!x.data && !x.norms && !x.data64 && !x.norms64 && !x.data16 && !h->map) continue;
+    if (!x.rows && !x.norms && !h->map) continue;
     (void)hipSetDevice(x.device);
     (void)hipDeviceSynchronize();
-    if (x.data) (void)hipFree(x.data);
+    if (x.rows) (void)hipFree(x.rows);
     if (x.norms) (void)hipFree(x.norms);
-    if (x.data64) (void)hipFree(x.data64);
-    if (x.norms64) (void)hipFree(x.norms64);
-    if (x.data16) (void)hipFree(x.data16);
     if (&x == &h->shards[0]) {
       free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
       if (h->map) (void)hipFree(h->map);
@@ -3120,11 +3208,9 @@ int pmm_corpus_destroy(pmm_corpus *h) {
 
 int pmm_corpus_bytes(const pmm_corpus *h, size_t *bytes) {
   if (!h || !bytes) return fail(PMM_ERR_ARG, "null argument");
+  const RowKind rk = row_kind(h->dtype);
   size_t b = 0;
-  for (const auto &x : h->shards) {
-    if (h->dtype == PMM_DTYPE_F64) b += (size_t)x.n * h->dp * 8 + (size_t)x.n * 2 * 8;
-    else b += (size_t)x.n * h->dp * (h->dtype == PMM_DTYPE_BF16 ? 2 : 4) + (size_t)x.n * 4 * 4;
-  }
+  for (const auto &x : h->shards) b += (size_t)x.n * (h->dp * rk.elem + rk.norm_arrays * rk.norm_elem);
   if (h->screen.load(std::memory_order_acquire)) b += screen_image_bytes(h->n, h->d);
   if (h->map) b += (size_t)h->n * 4;
   *bytes = b;
@@ -3256,164 +3342,51 @@ int pmm_corpus_index_map(const pmm_corpus *h, uint32_t *ids, int64_t cap, int64_
 }
 
 int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **out) {
-  if (!out) return fail(PMM_ERR_ARG, "null argument");
-  *out = nullptr;
-  int rc = validate_sizes(0, n, d, 0, false);
-  if (rc) return rc;
-  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
-  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
-  if (!c) return fail(PMM_ERR_ARG, "null argument");
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  // with a device list the rows are sharded over it, as pmm_corpus_create_f32
-  // does (one contiguous shard per listed device, at most n)
-  std::vector<int> devs = devices_snapshot();
-  if (devs.size() <= 1) devs.assign(1, dev);
-  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-  pmm_corpus *h = new pmm_corpus();
-  h->n = n;
-  h->d = d;
-  h->dp = cdiv(d, 16) * 16;  // the f64 kernels' K step (pmm_topk_f64_device's stride rule)
-  h->dtype = PMM_DTYPE_F64;
-  h->shards.resize(G);
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    x.device = devs[g];
-    x.lo = shard_lo(n, G, g);
-    x.n = shard_lo(n, G, g + 1) - x.lo;
-  }
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    hipStream_t s;
-    hipError_t e = hipSetDevice(x.device);
-    if (e == hipSuccess && (rc = thread_stream(x.device, &s))) {
-      pmm_corpus_destroy(h);
-      return rc;
-    }
-    if (e == hipSuccess) e = hipMalloc(&x.data64, (size_t)x.n * h->dp * 8);
-    if (e == hipSuccess) e = hipMalloc(&x.norms64, (size_t)x.n * 2 * 8);
-    if (e != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus allocation failed on device %d: %s", x.device, hipGetErrorString(e));
-    }
-    if ((rc = upload_padded(x.data64, c + x.lo * d, x.n, d, h->dp, 8, s))) {
-      pmm_corpus_destroy(h);
-      return rc;
-    }
-    // the norms every f64 call would compute (src/metrics.rs:368-379), by the
-    // same kernel on the same padded rows: bit-identical to the per-call ones
-    hipError_t e1 = launch_norms_f64(x.data64, x.n, d, h->dp, 0, x.norms64, s);
-    hipError_t e2 = launch_norms_f64(x.data64, x.n, d, h->dp, 1, x.norms64 + x.n, s);
-    hipError_t e3 = hipStreamSynchronize(s);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus norms failed");
-    }
-  }
-  (void)hipSetDevice(dev);
-  *out = h;
-  return PMM_OK;
+  return corpus_create(PMM_DTYPE_F64, c, n, d, out);
 }
 
 int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, double *out_score) {
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->dtype != PMM_DTYPE_F64) return wrong_handle(h);
-  int rc = validate_sizes(m, h->n, h->d, k, true);
-  if (rc) return rc;
-  if ((rc = check_metric(metric))) return rc;
-  if (m == 0 || k == 0) return PMM_OK;
-  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  if (h->shards.size() > 1) {
-    std::vector<ShardSrc64> sh(h->shards.size());
-    for (size_t g = 0; g < sh.size(); g++) {
-      const CorpusShard &x = h->shards[g];
-      const double *cn = metric == kMetricCosine ? x.norms64 : metric == kMetricEuclidean ? x.norms64 + x.n : nullptr;
-      sh[g] = ShardSrc64{x.device, x.lo, x.n, nullptr, x.data64, cn};
-    }
-    return topk_sharded_f64(q, m, h->d, k, metric, sh, out_idx, out_score);
-  }
-  const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = h->dp, n = h->n;
-  const bool fused = f64_use_fused(m, n, k);
-  size_t off_q = 0, off_i = al256((size_t)m * dp * 8);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
-  void *base;
-  if ((rc = arena(dev, s, off_w + f64_workspace_bytes(m, n, k, fused), &base))) return rc;
-  char *b = (char *)base;
-  if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 8, s))) return rc;
-  const double *cn = metric == kMetricCosine ? x.norms64 : metric == kMetricEuclidean ? x.norms64 + n : nullptr;
-  uint32_t *oi = (uint32_t *)(b + off_i);
-  double *os = (double *)(b + off_s);
-  rc = topk_f64_device_impl((const double *)(b + off_q), dp, m, x.data64, dp, n, h->d, k, metric, 0u, oi, os,
-                            b + off_w, s, fused, cn);
-  if (rc) return rc;
-  if ((rc = remap_lists(h, oi, m, k, s))) return rc;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, oi, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, os, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return PMM_OK;
+  return corpus_topk(h, PMM_DTYPE_F64, q, m, k, metric, out_idx, out_score,
+                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, double **os) -> int {
+    const int64_t dp = h->dp, n = h->n;
+    const bool fused = f64_use_fused(m, n, k);
+    size_t off_q = 0, off_i = al256((size_t)m * dp * 8);
+    size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
+    void *base;
+    if (int rc = arena(dev, s, off_w + f64_workspace_bytes(m, n, k, fused), &base)) return rc;
+    char *b = (char *)base;
+    if (int rc = upload_padded(b + off_q, q, m, h->d, dp, 8, s)) return rc;
+    *oi = (uint32_t *)(b + off_i);
+    *os = (double *)(b + off_s);
+    return topk_f64_device_impl((const double *)(b + off_q), dp, m, x.rows_as<double>(), dp, n, h->d, k, metric, 0u,
+                                *oi, *os, b + off_w, s, fused, shard_norms<double>(h, x, metric));
+  });
 }
 
 int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, float *out_score) {
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->dtype != PMM_DTYPE_F32) return wrong_handle(h);
-  int rc = validate_sizes(m, h->n, h->d, k, true);
-  if (rc) return rc;
-  if ((rc = check_metric(metric))) return rc;
-  if (m == 0 || k == 0) return PMM_OK;
-  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  // which of a shard's norm arrays this metric reads (none for dot)
-  auto shard_norms = [&](const CorpusShard &x) -> const float * {
-    return metric == kMetricCosine ? x.norms : metric == kMetricEuclidean ? x.norms + 2 * x.n : nullptr;
-  };
-  if (h->shards.size() > 1 && k <= kFusedMaxK) {
-    std::vector<ShardSrc> sh(h->shards.size());
-    for (size_t g = 0; g < sh.size(); g++) {
-      const CorpusShard &x = h->shards[g];
-      sh[g] = ShardSrc{x.device, x.lo, x.n, nullptr, x.data, shard_norms(x)};
-    }
-    return topk_sharded(q, m, h->d, k, metric, PMM_COMPUTE_F32, sh, out_idx, out_score);
-  }
-  if (h->shards.size() > 1)
-    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
-                (long long)k);
-  const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = h->dp;
-  // The screened route when the shape asks for it (screen_wanted, as the
-  // device entry's) and the handle has, or can now build, its ScreenImage;
-  // else the f32 kernel on the cached norms, as for every other metric.
-  TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, true, true, true);
-  const ScreenImage *img = route.kind == Route::kF32Screened ? corpus_screen_image(h, s) : nullptr;
-  if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
-  const size_t ws_need = route.total;
-  size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
-  void *base;
-  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
-  char *b = (char *)base;
-  if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 4, s))) return rc;
-  rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.data, dp, h->n, h->d, k, metric,
-                            0u, (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need,
-                            s, dev, shard_norms(x), false, img);
-  if (rc) return rc;
-  if ((rc = remap_lists(h, (uint32_t *)(b + off_i), m, k, s))) return rc;
-  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+  return corpus_topk(h, PMM_DTYPE_F32, q, m, k, metric, out_idx, out_score,
+                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, float **os) -> int {
+    const int64_t dp = h->dp;
+    // The screened route when the shape asks for it (screen_wanted, as the
+    // device entry's) and the handle has, or can now build, its ScreenImage;
+    // else the f32 kernel on the cached norms, as for every other metric.
+    TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, true, true, true);
+    const ScreenImage *img = route.kind == Route::kF32Screened ? corpus_screen_image(h, s) : nullptr;
+    if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
+    const size_t ws_need = route.total;
+    size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
+    size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
+    void *base;
+    if (int rc = arena(dev, s, off_w + ws_need, &base)) return rc;
+    char *b = (char *)base;
+    if (int rc = upload_padded(b + off_q, q, m, h->d, dp, 4, s)) return rc;
+    *oi = (uint32_t *)(b + off_i);
+    *os = (float *)(b + off_s);
+    return topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.rows_as<float>(), dp, h->n, h->d, k, metric,
+                                0u, *oi, *os, b + off_w, ws_need, s, dev, shard_norms<float>(h, x, metric), false, img);
+  });
 }
 
 int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,
@@ -3450,133 +3423,42 @@ int pmm_round_bf16_device(const float *a, int64_t ld, int64_t rows, int64_t d, u
 }
 
 int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **out) {
-  if (!out) return fail(PMM_ERR_ARG, "null argument");
-  *out = nullptr;
-  int rc = validate_sizes(0, n, d, 0, false);
-  if (rc) return rc;
-  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
-  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
-  if (!c) return fail(PMM_ERR_ARG, "null argument");
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  // sharded over a device list exactly as pmm_corpus_create_f32
-  std::vector<int> devs = devices_snapshot();
-  if (devs.size() <= 1) devs.assign(1, dev);
-  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-  pmm_corpus *h = new pmm_corpus();
-  h->n = n;
-  h->d = d;
-  h->dp = cdiv(d, kBf16DAlign) * kBf16DAlign;  // pmm_topk_bf16_device's stride rule
-  h->dtype = PMM_DTYPE_BF16;
-  h->shards.resize(G);
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    x.device = devs[g];
-    x.lo = shard_lo(n, G, g);
-    x.n = shard_lo(n, G, g + 1) - x.lo;
-  }
-  for (int g = 0; g < G; g++) {
-    CorpusShard &x = h->shards[g];
-    hipStream_t s;
-    hipError_t e = hipSetDevice(x.device);
-    if (e == hipSuccess && (rc = thread_stream(x.device, &s))) {
-      pmm_corpus_destroy(h);
-      return rc;
-    }
-    // the f32 rows only pass through: a staging buffer of the shard's own,
-    // freed below (the arena would keep it for the thread's lifetime)
-    float *stage = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&x.data16, (size_t)x.n * h->dp * 2);
-    if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)x.n * 4 * 4);
-    if (e == hipSuccess) e = hipMalloc(&stage, (size_t)x.n * d * 4);
-    if (e != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus allocation failed on device %d: %s", x.device, hipGetErrorString(e));
-    }
-    hipError_t e1, e2;
-    {
-      Timed t("h2d", s);
-      e1 = hipMemcpyAsync(stage, c + x.lo * d, (size_t)x.n * d * 4, hipMemcpyHostToDevice, s);
-    }
-    {
-      // rows and the norms of both metrics in one pass over the f32 rows
-      Timed t("round_norms_bf16", s);
-      e2 = launch_round_norms_bf16(stage, x.n, d, d, x.data16, h->dp, x.norms, x.norms + x.n, x.norms + 2 * x.n,
-                                   x.norms + 3 * x.n, s);
-    }
-    hipError_t e3 = hipStreamSynchronize(s);
-    (void)hipFree(stage);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-      pmm_corpus_destroy(h);
-      return fail(PMM_ERR_HIP, "corpus rounding failed");
-    }
-  }
-  (void)hipSetDevice(dev);
-  *out = h;
-  return PMM_OK;
+  return corpus_create(PMM_DTYPE_BF16, c, n, d, out);
 }
 
 int pmm_topk_bf16_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric, uint32_t *out_idx,
                          float *out_score) {
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->dtype != PMM_DTYPE_BF16) return wrong_handle(h);
-  int rc = validate_sizes(m, h->n, h->d, k, true);
-  if (rc) return rc;
-  if ((rc = check_metric(metric))) return rc;
-  if (m == 0 || k == 0) return PMM_OK;
-  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  // which of a shard's norm arrays this metric reads (none for dot)
-  auto shard_norms = [&](const CorpusShard &x) -> const float * {
-    return metric == kMetricCosine ? x.norms : metric == kMetricEuclidean ? x.norms + 2 * x.n : nullptr;
-  };
-  if (h->shards.size() > 1 && k <= kFusedMaxK) {
-    std::vector<ShardSrc> sh(h->shards.size());
-    for (size_t g = 0; g < sh.size(); g++) {
-      const CorpusShard &x = h->shards[g];
-      sh[g] = ShardSrc{x.device, x.lo, x.n, nullptr, nullptr, shard_norms(x), x.data16};
+  return corpus_topk(h, PMM_DTYPE_BF16, q, m, k, metric, out_idx, out_score,
+                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, float **os) -> int {
+    const int64_t d = h->d, db = h->dp, n = h->n;
+    // the route pmm_topk_f32_ex's bf16 branch asks for, so the same kernels run
+    const TopkRoute route = route_topk(m, n, d, k, metric, PMM_COMPUTE_BF16, g_dev[dev].cus, true, true);
+    const size_t ws_need = route.total;
+    // query norms sit outside the route's workspace (topk_bf16_native zeroes its top)
+    size_t off_qf = 0, off_qb = al256((size_t)m * d * 4), off_qn = off_qb + al256((size_t)m * db * 2);
+    size_t off_i = off_qn + al256((size_t)m * 4), off_s = off_i + al256((size_t)m * k * 4);
+    size_t off_w = off_s + al256((size_t)m * k * 4);
+    void *base;
+    if (int rc = arena(dev, s, off_w + ws_need, &base)) return rc;
+    char *b = (char *)base;
+    {
+      Timed t("h2d", s);
+      HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
     }
-    return topk_sharded(q, m, h->d, k, metric, PMM_COMPUTE_BF16, sh, out_idx, out_score);
-  }
-  if (h->shards.size() > 1)
-    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
-                (long long)k);
-  const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t d = h->d, db = h->dp, n = h->n;
-  // the route pmm_topk_f32_ex's bf16 branch asks for, so the same kernels run
-  const TopkRoute route = route_topk(m, n, d, k, metric, PMM_COMPUTE_BF16, g_dev[dev].cus, true, true);
-  const size_t ws_need = route.total;
-  // query norms sit outside the route's workspace (topk_bf16_native zeroes its top)
-  size_t off_qf = 0, off_qb = al256((size_t)m * d * 4), off_qn = off_qb + al256((size_t)m * db * 2);
-  size_t off_i = off_qn + al256((size_t)m * 4), off_s = off_i + al256((size_t)m * k * 4);
-  size_t off_w = off_s + al256((size_t)m * k * 4);
-  void *base;
-  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
-  char *b = (char *)base;
-  {
-    Timed t("h2d", s);
-    HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
-  }
-  // the native route reads the metric's query norms; the widened one computes
-  // its own from the widened rows
-  float *qn = (metric != kMetricDot && route.kind == Route::kBf16Native) ? (float *)(b + off_qn) : nullptr;
-  {
-    Timed t("round_norms_bf16", s);
-    HIP_TRY(launch_round_norms_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db,
-                                    metric == kMetricCosine ? qn : nullptr, nullptr,
-                                    metric == kMetricEuclidean ? qn : nullptr, nullptr, s));
-  }
-  rc = topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, x.data16, db, n, d, k, metric, 0u,
-                             (uint32_t *)(b + off_i), (float *)(b + off_s), b + off_w, ws_need, s, dev, qn,
-                             shard_norms(x));
-  if (rc) return rc;
-  if ((rc = remap_lists(h, (uint32_t *)(b + off_i), m, k, s))) return rc;
-  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+    // the native route reads the metric's query norms; the widened one computes
+    // its own from the widened rows
+    float *qn = (metric != kMetricDot && route.kind == Route::kBf16Native) ? (float *)(b + off_qn) : nullptr;
+    {
+      Timed t("round_norms_bf16", s);
+      HIP_TRY(launch_round_norms_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db,
+                                      metric == kMetricCosine ? qn : nullptr, nullptr,
+                                      metric == kMetricEuclidean ? qn : nullptr, nullptr, s));
+    }
+    *oi = (uint32_t *)(b + off_i);
+    *os = (float *)(b + off_s);
+    return topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, x.rows_as<uint16_t>(), db, n, d, k, metric,
+                                 0u, *oi, *os, b + off_w, ws_need, s, dev, qn, shard_norms<float>(h, x, metric));
+  });
 }
 
 int pmm_timing_enable(int enable) {
