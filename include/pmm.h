@@ -407,6 +407,79 @@ int pmm_corpus_subset_mask(const pmm_corpus *parent, const uint8_t *bitmap, int6
  * not derived: *s = 0.  No reference counterpart. */
 int pmm_corpus_index_map(const pmm_corpus *corpus, uint32_t *ids, int64_t cap, int64_t *s);
 
+/* ---------------------------------------------------------------------------
+ * Grouped search: every query row is searched only among the corpus rows that
+ * carry its own label (Polars' over() / group_by on a search).  A label is a
+ * uint32 in [0, G); PMM_NO_GROUP marks a row that is in no group.  No
+ * reference counterpart (the reference has one filter per call, on the host).
+ * ------------------------------------------------------------------------- */
+#define PMM_NO_GROUP 0xFFFFFFFFu
+
+/* The plan of a partition: a stable counting sort of the row numbers 0..n-1
+ * by label.  Host only -- it touches no device and runs without one.
+ * labels[i] is in [0, G) or PMM_NO_GROUP (the row is dropped); any other
+ * value is PMM_ERR_ARG naming the first offending position.  perm (room for n
+ * entries) takes the kept rows group by group, strictly ascending inside a
+ * group; offsets (G + 1 entries) the groups' bounds in perm -- group g is
+ * perm[offsets[g] .. offsets[g + 1]); *kept = offsets[G].  G >= 0,
+ * n < 2^32 - 1. */
+int pmm_partition_plan(const uint32_t *labels, int64_t n, int64_t G, uint32_t *perm, int64_t *offsets,
+                       int64_t *kept);
+
+/* A handle derived on the device from a resident handle whose rows are stored
+ * grouped by label: pmm_partition_plan on the host (labels: n entries, one per
+ * parent row; G >= 1), the permutation uploaded as the handle's index map, the
+ * rows and the parent's norm arrays gathered by pmm_corpus_subset_ids' kernel
+ * (f32, f64 and bf16 parents alike; no row crosses PCIe, no norm is
+ * recomputed), and the groups' offsets kept on the host and on the device
+ * (pmm_corpus_bytes counts them).  The parent limits are pmm_corpus_subset_ids':
+ * one shard (else PMM_ERR_UNSUPPORTED), not itself derived or partitioned
+ * (PMM_ERR_ARG).  Every row dropped: PMM_ERR_ARG.  No screen image is gathered
+ * and the handle never screens.  Its index map ascends only inside a group,
+ * so an ungrouped search would break the tie order: pmm_topk_*_corpus and
+ * pmm_corpus_subset_* on a partitioned handle return PMM_ERR_ARG and say so.
+ * An f32 handle serves pmm_topk_f32_grouped, an f64 handle
+ * pmm_topk_f64_grouped; a bf16 handle can be partitioned but has no grouped
+ * entry here (the Python layer searches bf16 corpora per label instead).
+ * Independent of the parent (pmm_corpus_destroy frees it); synchronises
+ * before it returns. */
+int pmm_corpus_partition(const pmm_corpus *parent, const uint32_t *labels, int64_t G, pmm_corpus **out);
+
+/* A partitioned handle's groups, the read-back counterpart of
+ * pmm_corpus_index_map (which returns its permutation): *G takes the number
+ * of groups and offsets (may be NULL when cap is 0) the first min(cap, G + 1)
+ * segment bounds.  A handle that is not partitioned: *G = 0. */
+int pmm_corpus_groups(const pmm_corpus *corpus, int64_t *G, int64_t *offsets, int64_t cap);
+
+/* Grouped top-k against a partitioned f32 handle (host queries in, host
+ * results out; any k >= 0).  Query row i is searched only against the segment
+ * of group qlabels[i] (in [0, G), or PMM_NO_GROUP; another value is
+ * PMM_ERR_ARG).  out_len[i] = min(k, rows of that segment), 0 for
+ * PMM_NO_GROUP or an empty segment.  The first out_len[i] slots of row i
+ * (row stride k in out_idx / out_score) are the exact top-k among that
+ * group's rows -- the PARENT's row numbers, best first, the total order of
+ * every pmm_topk_* entry (inside a group ascending partition row is ascending
+ * parent row, so ties break as a search of the group's rows alone breaks
+ * them); the remaining slots hold index 0xFFFFFFFF and score 0.  Indices and
+ * score bits equal pmm_topk_f32 on the group's rows.
+ * The queries are uploaded once, grouped by label on the device and cut into
+ * (query range, segment) pairs.  Pairs with k <= 128, roundup(d, 32) <= 1024
+ * and a segment of at most PMM_GROUPED_SEG_MAX rows (read per call) all run
+ * in ONE launch of the grouped kernel; the others run one after another
+ * through the route pmm_topk_f32_corpus takes for the pair's shape, unscreened.
+ * PMM_GROUPED=kernel | loop (per call) forces a path where its limits allow.
+ * One more launch maps the lists to the parent's numbering and the caller's
+ * query order.  A handle that is not partitioned, or holds other rows:
+ * PMM_ERR_ARG; a bf16 handle: PMM_ERR_UNSUPPORTED. */
+int pmm_topk_f32_grouped(const pmm_corpus *corpus, const float *q, int64_t m, const uint32_t *qlabels, int64_t k,
+                         int metric, uint32_t *out_idx, float *out_score, uint32_t *out_len);
+
+/* The same against a partitioned f64 handle: every pair runs through
+ * pmm_topk_f64_corpus' paths (there is no grouped f64 kernel), exact against
+ * pmm_topk_f64 on the group's rows. */
+int pmm_topk_f64_grouped(const pmm_corpus *corpus, const double *q, int64_t m, const uint32_t *qlabels, int64_t k,
+                         int metric, uint32_t *out_idx, double *out_score, uint32_t *out_len);
+
 /* pmm_topk_f32 against a device-resident corpus (host queries in, host
  * results out; 0 <= k <= n).  Results are pmm_topk_f32's bit for bit.
  *

@@ -1000,7 +1000,9 @@ int rerun_rows(const void *q, int64_t ld_bytes, int64_t row_bytes, const int *ro
 // zero-padded up to dp.
 // c_norms: optional precomputed corpus norms for `metric` laid out as
 // [n norms | n pre-filter factors] (a pmm_corpus handle's cache); NULL =
-// compute them in this call.
+// compute them in this call.  c_pre (with c_norms): the pre-filter factors
+// when they do not follow the norms at c_norms + n (a slice of a handle's
+// arrays: one group's segment of a partitioned handle).
 // keep_gthr: the workspace's shared per-row thresholds already hold a lower
 // bound of the rows' k-th best from earlier corpus chunks (see
 // topk_f32_host_chunked); they are kept instead of zeroed, so this chunk
@@ -1008,7 +1010,8 @@ int rerun_rows(const void *q, int64_t ld_bytes, int64_t row_bytes, const int *ro
 // the rest are empty slots, which the chunk merge skips).
 int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc, int64_t n,
                    int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, float *out_score,
-                   char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr) {
+                   char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr,
+                   const float *c_pre = nullptr) {
   const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   float *qn = (float *)(w + p.off_qn), *cn = (float *)(w + p.off_cn);
   if (c_norms) cn = const_cast<float *>(c_norms);
@@ -1043,7 +1046,7 @@ int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const 
   a.c = c;
   a.qn = qn;
   a.cn = cn;
-  a.cpre = cn + n;
+  a.cpre = c_pre ? c_pre : cn + n;
   a.ldq = ldq;
   a.ldc = ldc;
   // Seeded small problems: one prologue launch (seed + norms + fills).
@@ -1279,9 +1282,10 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
 // materialised, or the widened bf16 path's inner search) over workspace w.
 int topk_f32_unscreened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
                         int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
-                        float *out_score, char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr) {
+                        float *out_score, char *w, hipStream_t s, int cus, const float *c_norms, bool keep_gthr,
+                        const float *c_pre = nullptr) {
   return r.fused ? topk_f32_fused(r.p, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w, s, cus,
-                                  c_norms, keep_gthr)
+                                  c_norms, keep_gthr, c_pre)
                  : topk_f32_materialised(r.mp, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, w,
                                          s, cus, c_norms);
 }
@@ -1292,7 +1296,7 @@ int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, in
                          int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *out_idx,
                          float *out_score, void *ws, size_t ws_bytes, hipStream_t s, int dev,
                          const float *c_norms = nullptr, bool keep_gthr = false,
-                         const ScreenImage *img = nullptr) {
+                         const ScreenImage *img = nullptr, const float *c_pre = nullptr) {
   const int cus = g_dev[dev].cus;
   const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   // What the screen asks of a call and route_topk cannot see (row strides and
@@ -1314,7 +1318,7 @@ int topk_f32_device_impl(const TopkRoute &route, const float *q, int64_t ldq, in
                      ? topk_f32_screened(*r, q, ldq, m, c, ldc, n, d, k, index_base, out_idx, out_score, W.w, s, cus,
                                          img, c_norms)
                      : topk_f32_unscreened(*r, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score,
-                                           W.w, s, cus, c_norms, keep_gthr);
+                                           W.w, s, cus, c_norms, keep_gthr, c_pre);
   return rc ? rc : W.done();
 }
 
@@ -2382,6 +2386,15 @@ struct pmm_corpus {
   // parent's row map[i], ascending (n entries on shard 0's device); the top-k
   // entries return map[i].  NULL: not derived.
   uint32_t *map = nullptr;
+  // A partitioned handle (pmm_corpus_partition): the rows are
+  // stored group by group, group g in rows [offsets[g], offsets[g + 1]), in
+  // ascending parent order inside a group; `map` is then ascending only
+  // inside a group, so the handle serves the grouped entries alone.
+  // offsets: G + 1 entries on the host, d_offsets their copy on shard 0's
+  // device.  Empty: not partitioned.
+  std::vector<int64_t> offsets;
+  int64_t *d_offsets = nullptr;
+  bool partitioned() const { return !offsets.empty(); }
 };
 
 static void free_screen_image(const ScreenImage *img) {
@@ -2479,6 +2492,9 @@ static int check_subset_parent(const pmm_corpus *p, pmm_corpus **out) {
   if (!out) return fail(PMM_ERR_ARG, "null argument");
   *out = nullptr;
   if (!p) return fail(PMM_ERR_ARG, "null corpus");
+  if (p->partitioned())
+    return fail(PMM_ERR_ARG, "the parent is a partitioned handle (pmm_corpus_partition): its rows are stored group by "
+                             "group, so it has no subsets and no partitions; derive from its parent");
   if (p->map)
     return fail(PMM_ERR_ARG, "the parent is itself a derived handle: compose the selections and derive from its parent");
   if (p->shards.size() != 1)
@@ -2494,7 +2510,7 @@ static int check_subset_parent(const pmm_corpus *p, pmm_corpus **out) {
 // more when p has an image; `flag` is a device word for the gathered flags.
 // Synchronises st before it returns.
 static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned *flag, hipStream_t st,
-                        pmm_corpus **out) {
+                        pmm_corpus **out, bool with_image = true) {
   const CorpusShard &px = p->shards[0];
   pmm_corpus *h = new pmm_corpus();
   h->n = s;
@@ -2523,7 +2539,9 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
   // The parent's image, read once: its rows gathered too when they fit in
   // half of the free HBM (else, or when an allocation fails, the derived
   // handle starts without one and builds its own on its first screened call).
-  const ScreenImage *pimg = p->dtype == PMM_DTYPE_F32 ? p->screen.load(std::memory_order_acquire) : nullptr;
+  // (with_image = false, a partitioned handle: no image is gathered)
+  const ScreenImage *pimg =
+      (with_image && p->dtype == PMM_DTYPE_F32) ? p->screen.load(std::memory_order_acquire) : nullptr;
   ScreenImage *ni = nullptr;
   unsigned hflag = 0u;
   if (e == hipSuccess && pimg && (ni = alloc_screen_image(s, p->d))) {
@@ -2659,6 +2677,10 @@ template <typename Score, typename OneShard>
 static int corpus_topk(const pmm_corpus *h, int dtype, const Score *q, int64_t m, int64_t k, int metric,
                        uint32_t *out_idx, Score *out_score, OneShard one_shard) {
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (h->partitioned())
+    return fail(PMM_ERR_ARG, "the corpus handle is partitioned (pmm_corpus_partition): its index map ascends only "
+                             "inside a group, so an ungrouped search would break the tie order; use pmm_topk_%s_grouped",
+                h->dtype == PMM_DTYPE_F64 ? "f64" : "f32");
   if (h->dtype != dtype) return wrong_handle(h);
   int rc = validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
@@ -2693,6 +2715,244 @@ static int corpus_topk(const pmm_corpus *h, int dtype, const Score *q, int64_t m
   if ((rc = one_shard(x, dev, s, &oi, &os))) return rc;
   if ((rc = remap_lists(h, oi, m, k, s))) return rc;
   return download_lists(out_idx, out_score, oi, os, m, k, s);
+}
+
+// ---------------------------------------------------------------------------
+// Grouped search: every query row is searched inside its own
+// group's segment of a partitioned handle.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kNoGroup = 0xFFFFFFFFu;
+// Segments of at most this many rows go to the grouped kernel (one launch for
+// all of them), larger ones to the per-pair loop over the existing executors.
+// PMM_GROUPED_SEG_MAX overrides it per call.  The largest measured segment at
+// which the kernel beats the loop (16 queries per group, d = 768: 1.78 against
+// 8.03 ms at 64 groups of 16384 rows, 6.17 against 3.65 ms at 16 groups of
+// 65536; tools/measure_grouped.py, profiles/grouped/README.md).
+constexpr int64_t kGroupedSegMax = 16384;
+
+// Stable counting sort of the row numbers 0 .. n-1 by label (host only, no
+// device): perm = the kept rows group by group, ascending inside a group;
+// offsets[g] .. offsets[g + 1] = group g's positions in perm.
+static int partition_plan(const uint32_t *labels, int64_t n, int64_t G, uint32_t *perm, int64_t *offsets,
+                          int64_t *kept) {
+  if (n < 0 || G < 0 || n > (int64_t)UINT32_MAX - 1)
+    return fail(PMM_ERR_ARG, "partition sizes out of range (n=%lld G=%lld)", (long long)n, (long long)G);
+  if (!offsets || !kept || (n > 0 && (!labels || !perm))) return fail(PMM_ERR_ARG, "null argument");
+  for (int64_t g = 0; g <= G; g++) offsets[g] = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const uint32_t l = labels[i];
+    if (l == kNoGroup) continue;
+    if ((int64_t)l >= G)
+      return fail(PMM_ERR_ARG, "labels[%lld] = %u is not a group (G=%lld) and not the none label 0xFFFFFFFF",
+                  (long long)i, l, (long long)G);
+    offsets[l + 1]++;
+  }
+  for (int64_t g = 0; g < G; g++) offsets[g + 1] += offsets[g];
+  *kept = offsets[G];
+  std::vector<int64_t> next(offsets, offsets + G);
+  for (int64_t i = 0; i < n; i++)
+    if (labels[i] != kNoGroup) perm[next[labels[i]]++] = (uint32_t)i;
+  return PMM_OK;
+}
+
+// One (query range, segment range) pair of a grouped call: rows [q0, q0 + mq)
+// of the label-grouped queries against partition rows [c0, c0 + ng).
+struct GroupedPair {
+  int64_t q0, mq, c0, ng;
+  bool kernel;
+};
+
+template <typename Score>
+static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const uint32_t *qlabels, int64_t k,
+                        int metric, uint32_t *out_idx, Score *out_score, uint32_t *out_len) {
+  constexpr bool f64 = std::is_same<Score, double>::value;
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!h->partitioned())
+    return fail(PMM_ERR_ARG, "the corpus handle is not partitioned: pmm_corpus_partition derives one");
+  if (h->dtype == PMM_DTYPE_BF16)
+    return fail(PMM_ERR_UNSUPPORTED, "a bf16 handle has no grouped entry: search it per label (pmm_corpus_subset_*)");
+  if (h->dtype != (f64 ? PMM_DTYPE_F64 : PMM_DTYPE_F32))
+    return fail(PMM_ERR_ARG, "the partitioned handle holds %s rows: use pmm_topk_%s_grouped", f64 ? "f32" : "f64",
+                f64 ? "f32" : "f64");
+  int rc = validate_sizes(m, h->n, h->d, 0, false);
+  if (rc) return rc;
+  if (k < 0 || k > INT32_MAX) return fail(PMM_ERR_ARG, "k must be in [0, 2^31) (got %lld)", (long long)k);
+  if ((rc = check_metric(metric))) return rc;
+  if (m == 0) return PMM_OK;
+  if ((rc = need_buffers(q, qlabels, out_len))) return rc;
+  if (k > 0 && (rc = need_buffers(out_idx, out_score))) return rc;
+  const int64_t G = (int64_t)h->offsets.size() - 1, d = h->d, dp = h->dp;
+  const std::vector<int64_t> &off = h->offsets;
+  // The queries grouped by label on the host: a label with no corpus rows
+  // counts as the none label (an empty list), so every kept query has a pair.
+  std::vector<uint32_t> eff((size_t)m), qperm((size_t)m);
+  for (int64_t i = 0; i < m; i++) {
+    const uint32_t l = qlabels[i];
+    if (l != kNoGroup && (int64_t)l >= G)
+      return fail(PMM_ERR_ARG, "qlabels[%lld] = %u is not a group (G=%lld) and not the none label 0xFFFFFFFF",
+                  (long long)i, l, (long long)G);
+    eff[i] = (l == kNoGroup || off[l + 1] == off[l]) ? kNoGroup : l;
+  }
+  std::vector<int64_t> qoff((size_t)G + 1);
+  int64_t mk = 0;
+  if ((rc = partition_plan(eff.data(), m, G, qperm.data(), qoff.data(), &mk))) return rc;
+  if (k == 0 || mk == 0) {  // nothing to search: empty lists, no device work
+    for (int64_t i = 0; i < m; i++) out_len[i] = 0u;
+    for (int64_t t = 0; t < m * k; t++) {
+      out_idx[t] = kNoGroup;
+      out_score[t] = (Score)0;
+    }
+    return PMM_OK;
+  }
+  // Dispatch (PMM_GROUPED, PMM_GROUPED_SEG_MAX: read per call).
+  const char *ge = getenv("PMM_GROUPED");
+  const bool force_kernel = ge && !strcmp(ge, "kernel"), force_loop = ge && !strcmp(ge, "loop");
+  int64_t seg_max = kGroupedSegMax;
+  if (const char *se = getenv("PMM_GROUPED_SEG_MAX")) seg_max = atoll(se);
+  const bool kernel_ok = !f64 && k <= kGroupedMaxK && dp <= kGroupedMaxDp && !force_loop;
+  std::vector<GroupedPair> pairs;
+  std::vector<GroupedUnit> units;
+  std::vector<uint32_t> glen((size_t)mk);
+  for (int64_t g = 0; g < G; g++) {
+    if (qoff[g + 1] == qoff[g]) continue;
+    GroupedPair p{qoff[g], qoff[g + 1] - qoff[g], off[g], off[g + 1] - off[g], false};
+    p.kernel = kernel_ok && (force_kernel || p.ng <= seg_max);
+    pairs.push_back(p);
+    for (int64_t i = 0; i < p.mq; i++) glen[p.q0 + i] = (uint32_t)std::min<int64_t>(k, p.ng);
+    if (p.kernel)
+      for (int64_t r0 = 0; r0 < p.mq; r0 += kGroupedRows)
+        units.push_back(GroupedUnit{(uint32_t)p.c0, (uint32_t)p.ng, (uint32_t)(p.q0 + r0),
+                                    (uint32_t)std::min<int64_t>(kGroupedRows, p.mq - r0)});
+  }
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  const int cus = g_dev[dev].cus;
+  // The loop pairs' routes and the largest workspace and short-list staging among them.
+  std::vector<TopkRoute> routes;
+  size_t ws_need = 0, tmp_entries = 0;
+  for (const GroupedPair &p : pairs) {
+    if (p.kernel) continue;
+    const int64_t kg = std::min<int64_t>(k, p.ng);
+    if constexpr (f64) {
+      ws_need = std::max(ws_need, f64_workspace_bytes(p.mq, p.ng, kg, f64_use_fused(p.mq, p.ng, kg)));
+    } else {
+      routes.push_back(route_topk(p.mq, p.ng, d, kg, metric, PMM_COMPUTE_F32, cus, false, false));
+      ws_need = std::max(ws_need, routes.back().total);
+    }
+    if (kg < k) tmp_entries = std::max(tmp_entries, (size_t)(p.mq * kg));
+  }
+  constexpr size_t E = sizeof(Score);
+  const size_t tab_words = (size_t)2 * mk + units.size() * 4;
+  const size_t off_qu = 0, off_qg = al256((size_t)m * dp * E), off_qn = off_qg + al256((size_t)mk * dp * E);
+  const size_t off_tab = off_qn + al256((size_t)mk * 4), off_gi = off_tab + al256(tab_words * 4);
+  const size_t off_gs = off_gi + al256((size_t)mk * k * 4), off_oi = off_gs + al256((size_t)mk * k * E);
+  const size_t off_os = off_oi + al256((size_t)m * k * 4), off_ol = off_os + al256((size_t)m * k * E);
+  const size_t off_ti = off_ol + al256((size_t)m * 4), off_ts = off_ti + al256(tmp_entries * 4);
+  const size_t off_w = off_ts + al256(tmp_entries * E);
+  void *base;
+  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
+  char *b = (char *)base;
+  const Score *qg = (const Score *)(b + off_qg);
+  float *qn = (float *)(b + off_qn);
+  uint32_t *tab = (uint32_t *)(b + off_tab);
+  const uint32_t *d_qperm = tab, *d_glen = tab + mk;
+  const GroupedUnit *d_units = (const GroupedUnit *)(tab + 2 * mk);
+  uint32_t *gi = (uint32_t *)(b + off_gi), *oi = (uint32_t *)(b + off_oi), *ol = (uint32_t *)(b + off_ol);
+  uint32_t *ti = (uint32_t *)(b + off_ti);
+  Score *gs = (Score *)(b + off_gs), *os = (Score *)(b + off_os), *ts = (Score *)(b + off_ts);
+  // the queries, once; the tables; the padding every list starts from
+  if ((rc = upload_padded(b + off_qu, q, m, d, dp, E, s))) return rc;
+  std::vector<uint32_t> htab(tab_words);
+  memcpy(htab.data(), qperm.data(), (size_t)mk * 4);
+  memcpy(htab.data() + mk, glen.data(), (size_t)mk * 4);
+  if (!units.empty()) memcpy(htab.data() + 2 * mk, units.data(), units.size() * sizeof(GroupedUnit));
+  // (from here on a failure waits for the stream: the uploads read this frame's vectors)
+  auto run = [&]() -> int {
+    {
+      Timed t("h2d", s);
+      HIP_TRY(hipMemcpyAsync(tab, htab.data(), tab_words * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(oi, 0xFF, (size_t)m * k * 4, s));
+    HIP_TRY(hipMemsetAsync(os, 0, (size_t)m * k * E, s));
+    HIP_TRY(hipMemsetAsync(ol, 0, (size_t)m * 4, s));
+    {
+      Timed t("grouped_gather_queries", s);
+      HIP_TRY(launch_gather_rows(b + off_qu, (int64_t)(dp * E / 16), (const int *)d_qperm, (int)mk, (int)(dp * E / 16),
+                                 b + off_qg, s));
+    }
+    if constexpr (!f64) {
+      // (the kernel's query norms, and the sign-of-zero pass's; the loop's
+      // executors compute their own, the same values)
+      if (metric != kMetricDot && (!units.empty() || metric == kMetricCosine)) {
+        Timed t("norms_f32", s);
+        HIP_TRY(launch_norms_f32((const float *)qg, mk, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+      }
+    }
+    // the loop path: the existing executor on each pair's slices, one after another
+    size_t ri = 0;
+    for (const GroupedPair &p : pairs) {
+      if (p.kernel) continue;
+      const int64_t kg = std::min<int64_t>(k, p.ng);
+      uint32_t *di = kg == k ? gi + p.q0 * k : ti;
+      Score *ds = kg == k ? gs + p.q0 * k : ts;
+      if constexpr (f64) {
+        const double *cn = shard_norms<double>(h, x, metric);
+        if (int r2 = topk_f64_device_impl(qg + p.q0 * dp, dp, p.mq, x.rows_as<double>() + p.c0 * dp, dp, p.ng, d, kg,
+                                          metric, (uint32_t)p.c0, di, ds, b + off_w, s,
+                                          f64_use_fused(p.mq, p.ng, kg), cn ? cn + p.c0 : nullptr))
+          return r2;
+      } else {
+        const float *cn = shard_norms<float>(h, x, metric);  // [norms n | pre-filter factors n]
+        if (int r2 = topk_f32_device_impl(routes[ri++], qg + p.q0 * dp, dp, p.mq, x.rows_as<float>() + p.c0 * dp, dp,
+                                          p.ng, d, kg, metric, (uint32_t)p.c0, di, ds, b + off_w, ws_need, s, dev,
+                                          cn ? cn + p.c0 : nullptr, false, nullptr, cn ? cn + h->n + p.c0 : nullptr))
+          return r2;
+      }
+      if (kg < k) {
+        Timed t("grouped_pad", s);
+        HIP_TRY(launch_grouped_pad(di, ds, (int)p.mq, (int)kg, (int)k, gi + p.q0 * k, gs + p.q0 * k, f64, s));
+      }
+    }
+    if constexpr (!f64) {
+      if (!units.empty()) {
+        GroupedArgs a{};
+        a.q = (const float *)qg;
+        a.c = x.rows_as<float>();
+        a.qn = qn;
+        a.cn = shard_norms<float>(h, x, metric);
+        a.ldq = dp;
+        a.ldc = dp;
+        a.dp = (int)dp;
+        a.k = (int)k;
+        a.units = d_units;
+        a.out_idx = gi;
+        a.out_score = (float *)gs;
+        Timed t("grouped_topk_f32", s);
+        HIP_TRY(launch_grouped_topk_f32(a, (int)units.size(), metric, s));
+      }
+      // the sign of zero scores, while the lists still number the partition's rows
+      if (metric == kMetricCosine)
+        HIP_TRY(launch_zero_sign_cosine((const float *)qg, dp, x.rows_as<float>(), dp, qn,
+                                        shard_norms<float>(h, x, metric), (int)mk, h->n, (int)d, (int)k, 0u, gi,
+                                        (float *)gs, s));
+    }
+    {
+      Timed t("grouped_scatter", s);
+      HIP_TRY(launch_grouped_scatter(gi, gs, d_qperm, d_glen, mk, (int)k, h->map, (uint32_t)h->n, oi, os, ol, f64, s));
+    }
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_len, ol, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    }
+    return download_lists(out_idx, out_score, oi, os, m, k, s);
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(s);
+  return rc;
 }
 
 // ===========================================================================
@@ -3199,6 +3459,7 @@ int pmm_corpus_destroy(pmm_corpus *h) {
     if (&x == &h->shards[0]) {
       free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
       if (h->map) (void)hipFree(h->map);
+      if (h->d_offsets) (void)hipFree(h->d_offsets);
     }
   }
   (void)hipSetDevice(cur);
@@ -3213,6 +3474,7 @@ int pmm_corpus_bytes(const pmm_corpus *h, size_t *bytes) {
   for (const auto &x : h->shards) b += (size_t)x.n * (h->dp * rk.elem + rk.norm_arrays * rk.norm_elem);
   if (h->screen.load(std::memory_order_acquire)) b += screen_image_bytes(h->n, h->d);
   if (h->map) b += (size_t)h->n * 4;
+  if (h->d_offsets) b += h->offsets.size() * 8;
   *bytes = b;
   return PMM_OK;
 }
@@ -3339,6 +3601,81 @@ int pmm_corpus_index_map(const pmm_corpus *h, uint32_t *ids, int64_t cap, int64_
   if ((rc = ensure_device(&dev, &scope, h->shards[0].device))) return rc;
   HIP_TRY(hipMemcpy(ids, h->map, (size_t)take * 4, hipMemcpyDeviceToHost));
   return PMM_OK;
+}
+
+int pmm_partition_plan(const uint32_t *labels, int64_t n, int64_t G, uint32_t *perm, int64_t *offsets,
+                       int64_t *kept) {
+  return partition_plan(labels, n, G, perm, offsets, kept);
+}
+
+int pmm_corpus_partition(const pmm_corpus *p, const uint32_t *labels, int64_t G, pmm_corpus **out) {
+  int rc = check_subset_parent(p, out);
+  if (rc) return rc;
+  if (!labels) return fail(PMM_ERR_ARG, "null argument");
+  if (G < 1) return fail(PMM_ERR_ARG, "a partition has G >= 1 groups (got %lld)", (long long)G);
+  std::vector<uint32_t> perm((size_t)p->n);
+  std::vector<int64_t> off((size_t)G + 1);
+  int64_t kept = 0;
+  if ((rc = partition_plan(labels, p->n, G, perm.data(), off.data(), &kept))) return rc;
+  if (kept == 0)
+    return fail(PMM_ERR_ARG, "empty partition: every one of the %lld rows carries the none label", (long long)p->n);
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, p->shards[0].device))) return rc;
+  hipStream_t st;
+  if ((rc = thread_stream(dev, &st))) return rc;
+  void *flag;
+  if ((rc = arena(dev, st, 256, &flag))) return rc;
+  uint32_t *map = nullptr;
+  int64_t *doff = nullptr;
+  hipError_t e = hipMalloc(&map, (size_t)kept * 4);
+  if (e == hipSuccess) e = hipMalloc(&doff, off.size() * 8);
+  if (e != hipSuccess) {
+    if (map) (void)hipFree(map);
+    return fail(PMM_ERR_HIP, "partition allocation failed on device %d: %s", dev, hipGetErrorString(e));
+  }
+  {
+    Timed t("h2d", st);
+    e = hipMemcpyAsync(map, perm.data(), (size_t)kept * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(doff, off.data(), off.size() * 8, hipMemcpyHostToDevice, st);
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(map);
+    (void)hipFree(doff);
+    return fail(PMM_ERR_HIP, "partition upload failed: %s", hipGetErrorString(e));
+  }
+  // (subset_build waits for the stream: the uploads above read this frame's vectors)
+  if ((rc = subset_build(p, map, kept, (unsigned *)flag, st, out, false))) {
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(doff);
+    return rc;
+  }
+  pmm_corpus *h = *out;
+  h->offsets = std::move(off);
+  h->d_offsets = doff;
+  h->screen_never.store(true, std::memory_order_release);
+  return PMM_OK;
+}
+
+int pmm_corpus_groups(const pmm_corpus *h, int64_t *G, int64_t *offsets, int64_t cap) {
+  if (!h || !G) return fail(PMM_ERR_ARG, "null argument");
+  *G = h->partitioned() ? (int64_t)h->offsets.size() - 1 : 0;
+  const int64_t take = h->partitioned() ? std::min<int64_t>(cap, (int64_t)h->offsets.size()) : 0;
+  if (take <= 0) return PMM_OK;
+  if (!offsets) return fail(PMM_ERR_ARG, "null argument");
+  memcpy(offsets, h->offsets.data(), (size_t)take * 8);
+  return PMM_OK;
+}
+
+int pmm_topk_f32_grouped(const pmm_corpus *h, const float *q, int64_t m, const uint32_t *qlabels, int64_t k,
+                         int metric, uint32_t *out_idx, float *out_score, uint32_t *out_len) {
+  return topk_grouped<float>(h, q, m, qlabels, k, metric, out_idx, out_score, out_len);
+}
+
+int pmm_topk_f64_grouped(const pmm_corpus *h, const double *q, int64_t m, const uint32_t *qlabels, int64_t k,
+                         int metric, uint32_t *out_idx, double *out_score, uint32_t *out_len) {
+  return topk_grouped<double>(h, q, m, qlabels, k, metric, out_idx, out_score, out_len);
 }
 
 int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **out) {

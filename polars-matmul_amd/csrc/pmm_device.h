@@ -232,6 +232,77 @@ __device__ inline int wave_keep_ge(const u64 (&x)[E], u64 t, Store st, int lane)
   return base;
 }
 
+// Bitonic sort, best first, of 128 keys held two per lane in registers (key
+// i: lane i & 63, y0 for i < 64, y1 above): the merge's register sort
+// (pmm_kernels.hip describes the network and its measurements) and the
+// grouped top-k kernel's (pmm_grouped.hip).
+// (every permutation used here gives every lane a valid source, so
+// bound_ctrl costs nothing and spares update_dpp's copy of an old value:
+// kway_merge_kernel 85 -> 78 VGPRs)
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
+}
+template <int S>
+__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t v, int lane) {
+  if constexpr (S == 1) return dpp_mov<0xB1>(v);                    // quad_perm [1,0,3,2]
+  else if constexpr (S == 2) return dpp_mov<0x4E>(v);               // quad_perm [2,3,0,1]
+  else if constexpr (S == 4) return dpp_mov<0x1B>(dpp_mov<0x141>(v));  // half mirror, quad reverse
+  else if constexpr (S == 8) return dpp_mov<0x141>(dpp_mov<0x140>(v)); // row mirror, half mirror
+  else if constexpr (S == 16) return (uint32_t)__shfl_xor((int)v, 16);
+  else {
+    // lanes 32-63 of the first operand swap with lanes 0-31 of the second:
+    // r[0] = both halves' low half, r[1] = both halves' high half
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return lane < 32 ? r[1] : r[0];
+  }
+}
+// element i keeps the larger of (i, i ^ S) iff (i is the pair's lower) ==
+// (i's SIZE-block sorts descending: i & SIZE == 0); i = lane + 64 r.  As a
+// compile-time lane mask per register: one compare into a lane mask, one
+// scalar xor with it, two selects per key (against two selects per max and
+// per min and a third pair to choose between them).
+template <int SIZE, int S, int R>
+constexpr unsigned long long sort128_keepmax() {
+  unsigned long long m = 0;
+  for (int l = 0; l < 64; l++) {
+    const bool lower = (l & S) == 0;
+    const bool d = SIZE > 64 ? true : (SIZE == 64 ? R == 0 : (l & SIZE) == 0);
+    if (lower == d) m |= 1ull << l;
+  }
+  return m;
+}
+template <int SIZE, int S>
+__device__ __forceinline__ void sort128_step(u64 &y0, u64 &y1, int lane) {
+  auto px = [&](u64 v) __attribute__((always_inline)) {
+    return ((u64)lane_xor_u32<S>((uint32_t)(v >> 32), lane) << 32) | (u64)lane_xor_u32<S>((uint32_t)v, lane);
+  };
+  const u64 p0 = px(y0), p1 = px(y1);
+  // take the partner's key where (mine is larger) != (I keep the larger)
+  const u64 t0 = __ballot(y0 > p0) ^ sort128_keepmax<SIZE, S, 0>();
+  const u64 t1 = __ballot(y1 > p1) ^ sort128_keepmax<SIZE, S, 1>();
+  y0 = __builtin_amdgcn_inverse_ballot_w64(t0) ? p0 : y0;
+  y1 = __builtin_amdgcn_inverse_ballot_w64(t1) ? p1 : y1;
+}
+template <int SIZE, int S>
+__device__ __forceinline__ void sort128_merge(u64 &y0, u64 &y1, int lane) {
+  sort128_step<SIZE, S>(y0, y1, lane);
+  if constexpr (S > 1) sort128_merge<SIZE, S / 2>(y0, y1, lane);
+}
+__device__ inline void wave_sort128_desc(u64 &y0, u64 &y1, int lane) {
+  sort128_merge<2, 1>(y0, y1, lane);
+  sort128_merge<4, 2>(y0, y1, lane);
+  sort128_merge<8, 4>(y0, y1, lane);
+  sort128_merge<16, 8>(y0, y1, lane);
+  sort128_merge<32, 16>(y0, y1, lane);
+  sort128_merge<64, 32>(y0, y1, lane);
+  // size 128: (i, i + 64) inside the lane, then distances 32 .. 1, all descending
+  const u64 mx = y0 > y1 ? y0 : y1, mn = y0 > y1 ? y1 : y0;
+  y0 = mx;
+  y1 = mn;
+  sort128_merge<128, 32>(y0, y1, lane);
+}
+
 // 16-byte entry for the materialised (row-select) path: f64 keys need all
 // 64 bits, so the index rides alongside.
 struct __attribute__((aligned(16))) Ent {

@@ -277,6 +277,37 @@ hipError_t launch_subset_gather(const void *src, const uint32_t *ids, int64_t s,
                                 int flag_arr, unsigned *any, hipStream_t st);
 // idx[t] = map[idx[t]] for t < count; entries at or above s (the empty slot 0xFFFFFFFF) stay
 hipError_t launch_remap_index(uint32_t *idx, int64_t count, const uint32_t *map, int64_t s, hipStream_t st);
+// ---- grouped search (pmm_grouped.hip) ----
+// The grouped f32 kernel's limits: list length, padded dimension (its 16 query
+// rows and a row's candidate keys live in LDS), query rows per work unit.
+constexpr int kGroupedMaxK = 128;
+constexpr int kGroupedMaxDp = 1024;
+constexpr int kGroupedRows = 16;
+// One work unit = one workgroup: partition rows [c0, c0 + ng) of one group
+// against rows [q0, q0 + mq) of the label-grouped queries, 1 <= mq <= kGroupedRows.
+struct GroupedUnit {
+  uint32_t c0, ng, q0, mq;
+};
+struct GroupedArgs {
+  const float *q;            // the queries grouped by label (row stride ldq, zero-padded to dp)
+  const float *c;            // the partitioned handle's rows (row stride ldc)
+  const float *qn, *cn;      // cosine: norms, euclidean: squared norms (per grouped query / partition row); dot: unused
+  int64_t ldq, ldc;
+  int dp, k;                 // dp % 32 == 0, dp <= kGroupedMaxDp; 1 <= k <= kGroupedMaxK
+  const GroupedUnit *units;  // device table, one entry per workgroup
+  uint32_t *out_idx;         // [grouped rows][k]: partition-row numbers, best first, padded
+  float *out_score;
+};
+size_t grouped_lds_bytes(int dp);
+hipError_t launch_grouped_topk_f32(const GroupedArgs &a, int units, int metric, hipStream_t s);
+// di / ds rows of k entries = the dense rows x kg lists si / ss, padded (index 0xFFFFFFFF, score 0)
+hipError_t launch_grouped_pad(const uint32_t *si, const void *ss, int rows, int kg, int k, uint32_t *di, void *ds,
+                              bool f64, hipStream_t s);
+// out row qrow[i] = grouped row i's list with its indices (< n) mapped through
+// `map` and the slots past glen[i] padded; out_len[qrow[i]] = glen[i]
+hipError_t launch_grouped_scatter(const uint32_t *gi, const void *gs, const uint32_t *qrow, const uint32_t *glen,
+                                  int64_t rows, int k, const uint32_t *map, uint32_t n, uint32_t *out_idx,
+                                  void *out_score, uint32_t *out_len, bool f64, hipStream_t s);
 hipError_t launch_gemm_f64_store(const double *q, int64_t ldq, const double *c, int64_t ldc,
                                  const double *qn, const double *cn, int M, int N, int D,
                                  int metric, int store_metric, double *out, int64_t ldo,

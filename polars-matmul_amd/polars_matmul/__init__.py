@@ -11,7 +11,10 @@ f32 and searches them on the bf16 MFMA path; the corpus stays on the device
 as a bf16 handle (half an f32 handle's HBM) while its Series is reused.
 ``subset=`` (an extension, on all three) searches only the selected corpus rows
 -- a Boolean mask Series or integer row ids -- from a handle derived on the
-device, and returns indices that number the full corpus.  The numerics run on MI355X through hand-written HIP
+device, and returns indices that number the full corpus.  ``groups=`` (an
+extension; ``by=`` / ``corpus_by=`` on the namespace) searches every query row
+only among the corpus rows that carry its own label, all labels in one call
+against a handle whose rows are stored group by group.  The numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
 Usage:
@@ -37,6 +40,7 @@ import numpy as np
 
 from polars_matmul._polars_matmul import (  # noqa: F401
     PanicException,
+    _check_groups,
     _check_subset,
     _matmul,
     _topk,
@@ -58,7 +62,7 @@ except Exception:  # polars is optional (not installable in this image)
 
 
 def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosine",
-         compute: Compute = "f32", subset=None):
+         compute: Compute = "f32", subset=None, groups=None):
     """numpy-level top-k: returns (indices uint32 [m, k'], scores float64 [m, k'])
     with k' = min(k, len(corpus)); f32 compute iff both inputs are float32
     (src/matmul.rs:427), scores widened to f64 (src/matmul.rs:447).
@@ -68,10 +72,20 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     rows widened to f32 beyond).
     subset (an extension): a bool mask of len(corpus) or integer row ids; only
     those rows are searched (taken on the host: a numpy corpus has no cached
-    handle), k' = min(k, rows selected), and the indices number ``corpus``."""
+    handle), k' = min(k, rows selected), and the indices number ``corpus``.
+    groups (an extension): ``(query_labels, corpus_labels)``, one label per
+    row; every query is searched only among the corpus rows of its own label
+    (per label on the host rows: a numpy corpus has no cached handle).
+    k' = min(k, largest searched segment); a row whose segment is shorter (or
+    empty: a null or unseen label) ends in unused slots -- index 0xFFFFFFFF,
+    score NaN.  Not together with ``subset``."""
     q = np.asarray(queries)
     c = np.asarray(corpus)
     _native.check_compute(compute)
+    if groups is not None:
+        if subset is not None:
+            raise ValueError("groups= and subset= cannot be combined: give the rows to leave out a null label")
+        grp = _check_groups(groups, q.shape[0], c.shape[0])
     dt = np.float32 if (q.dtype == np.float32 and c.dtype == np.float32) else np.float64
     if compute == "bf16":
         dt = np.float32
@@ -82,6 +96,16 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
             f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
             f"right has {c.shape[1]} dimensional vectors"
         )
+    if groups is not None:
+        from polars_matmul._polars_matmul import _topk_grouped
+
+        kk = min(int(k), grp.searched_max())
+        if kk == 0:
+            return np.zeros((q.shape[0], 0), dtype=np.uint32), np.zeros((q.shape[0], 0), dtype=np.float64)
+        idx, sc, lens = _topk_grouped(q, c, None, c, grp, kk, _native.metric_from_str(metric), compute)
+        sc = sc.astype(np.float64)
+        sc[np.arange(kk)[None, :] >= lens[:, None].astype(np.int64)] = np.nan
+        return idx, sc
     ids = _check_subset(subset, c.shape[0]).row_ids() if subset is not None else None
     if ids is not None:
         c = np.ascontiguousarray(c[ids])
@@ -112,7 +136,8 @@ if pl is not None:
             self._expr = expr
 
         def topk(self, corpus: "pl.Series", k: int, metric: Metric = "cosine",
-                 compute: Compute = "f32", subset: "pl.Series | None" = None) -> "pl.Expr":
+                 compute: Compute = "f32", subset: "pl.Series | None" = None,
+                 by: "pl.Expr | str | None" = None, corpus_by: "pl.Series | None" = None) -> "pl.Expr":
             """Top-k matches per embedding: List[Struct{index: u32, score: f64}].
             compute="bf16" (an extension): both columns read as f32 and
             searched on the bf16 MFMA path, the corpus kept on the device as a
@@ -120,7 +145,12 @@ if pl is not None:
             subset (an extension): a Boolean Series of len(corpus) (nulls count
             as false) or a Series of integer row ids; only those corpus rows
             are searched, ``index`` still numbers ``corpus``, and k clips to
-            the number of selected rows."""
+            the number of selected rows.
+            by / corpus_by (an extension, both or neither): ``by`` an
+            expression or column name of the query frame, ``corpus_by`` a
+            Series aligned with ``corpus``.  Every row is searched only among
+            the corpus rows whose ``corpus_by`` equals its ``by`` (null matches
+            nothing); the lists are ragged, min(k, rows of that label) long."""
             if isinstance(corpus, pl.Expr):
                 raise TypeError(
                     "corpus must be a Polars Series, not an Expression. "
@@ -131,11 +161,29 @@ if pl is not None:
                     "subset must be a Polars Series, not an Expression. "
                     "Use frame['column_name'] or frame.get_column('column_name')."
                 )
+            if isinstance(corpus_by, pl.Expr):
+                raise TypeError(
+                    "corpus_by must be a Polars Series, not an Expression. "
+                    "Use frame['column_name'] or frame.get_column('column_name')."
+                )
+            if (by is None) != (corpus_by is None):
+                raise ValueError("by= and corpus_by= go together: the query rows' labels and the corpus rows' labels")
             _native.check_compute(compute)
             # (the default stays the reference's four-argument call)
             extra = {} if compute == "f32" else {"compute": compute}
             if subset is not None:
                 extra["subset"] = subset
+            if by is not None:
+                # the embedding and its label travel as one struct column: rows
+                # are independent, so the batches stay elementwise
+                by_expr = pl.col(by) if isinstance(by, str) else by
+                packed = pl.struct(self._expr.alias("embedding"), by_expr.alias("by"))
+                return packed.map_batches(
+                    lambda s: _topk(s.struct.field("embedding"), corpus, k, metric,
+                                    groups=(s.struct.field("by"), corpus_by), **extra),
+                    is_elementwise=True,
+                    return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+                )
             return self._expr.map_batches(
                 lambda s: _topk(s, corpus, k, metric, **extra),
                 is_elementwise=True,

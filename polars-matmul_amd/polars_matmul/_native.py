@@ -80,6 +80,11 @@ EXPORTED_SYMBOLS = (
     "pmm_corpus_subset_ids",
     "pmm_corpus_subset_mask",
     "pmm_corpus_index_map",
+    "pmm_partition_plan",
+    "pmm_corpus_partition",
+    "pmm_corpus_groups",
+    "pmm_topk_f32_grouped",
+    "pmm_topk_f64_grouped",
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
@@ -179,6 +184,11 @@ _SIGS = {
     "pmm_corpus_subset_ids": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_subset_mask": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_corpus_index_map": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_partition_plan": ([_vp, _i64, _i64, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_corpus_partition": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_groups": ([_vp, ctypes.POINTER(ctypes.c_int64), _vp, _i64], _i32),
+    "pmm_topk_f32_grouped": ([_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
+    "pmm_topk_f64_grouped": ([_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
@@ -593,6 +603,28 @@ def subset_device_bytes(s: int, d: int, dtype=np.float32, compute: str = "f32", 
     return corpus_device_bytes(s, d, dtype, compute, screen) + 4 * s
 
 
+def partitioned_device_bytes(s: int, d: int, G: int, dtype=np.float32, compute: str = "f32") -> int:
+    """HBM a partitioned handle of s kept rows in G groups holds
+    (``DeviceCorpus.partition``): ``subset_device_bytes`` without a screen
+    image (a partitioned handle never has one) plus its G + 1 int64 offsets."""
+    return subset_device_bytes(s, d, dtype, compute) + 8 * (G + 1)
+
+
+NO_GROUP = 0xFFFFFFFF  # the label of a row that is in no group (PMM_NO_GROUP)
+
+
+def partition_plan(labels, G: int):
+    """(perm uint32 [kept], offsets int64 [G + 1]) of pmm_partition_plan: the
+    rows whose label is in [0, G) group by group, ascending inside a group;
+    rows labelled ``NO_GROUP`` are dropped.  Host only: runs without a GPU."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    perm = np.empty(labels.size, dtype=np.uint32)
+    offsets = np.empty(int(G) + 1, dtype=np.int64)
+    kept = ctypes.c_int64(0)
+    check(_lib.pmm_partition_plan(ptr(labels), labels.size, int(G), ptr(perm), ptr(offsets), ctypes.byref(kept)))
+    return perm[:kept.value], offsets
+
+
 def ascending_ids(ids, n: int) -> np.ndarray:
     """Row ids as the subset entries take them: uint32, ascending, unique.
     An id outside [0, n) raises ValueError."""
@@ -744,6 +776,63 @@ class DeviceCorpus:
             return self._derived(h)
         finally:
             self.release()
+
+    def partition(self, labels, G: int) -> "DeviceCorpus":
+        """A handle derived on the device whose rows are stored grouped by
+        label (pmm_corpus_partition): ``labels`` holds one uint32 per row of
+        this handle, in [0, G) or ``NO_GROUP`` (the row is dropped).  It
+        serves ``topk_grouped`` only; ``topk`` and ``subset`` on it raise."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        if labels.shape != (self.n,):
+            raise ValueError(f"a partition labels each of {self.n} rows, got shape {labels.shape}")
+        h = ctypes.c_void_p()
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_partition(self._h, ptr(labels), int(G), ctypes.byref(h)))
+            dc = self._derived(h)
+            dc._nbytes0 = partitioned_device_bytes(dc.n, dc.d, int(G), dc.dtype, dc.compute)
+            return dc
+        finally:
+            self.release()
+
+    def group_offsets(self):
+        """A partitioned handle's segment bounds (int64, G + 1 entries); None
+        for a handle that is not partitioned (pmm_corpus_groups)."""
+        G = ctypes.c_int64(0)
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_groups(self._h, ctypes.byref(G), None, 0))
+            if G.value == 0:
+                return None
+            off = np.empty(G.value + 1, dtype=np.int64)
+            check(_lib.pmm_corpus_groups(self._h, ctypes.byref(G), ptr(off), off.size))
+            return off
+        finally:
+            self.release()
+
+    def topk_grouped(self, q: np.ndarray, qlabels, k: int, metric: int):
+        """(idx uint32 (m, k), scores (m, k) in the corpus dtype, lens uint32
+        (m,)) of pmm_topk_f32_grouped / pmm_topk_f64_grouped on a partitioned
+        handle: row i searched inside group ``qlabels[i]`` only; its first
+        ``lens[i]`` slots are the exact top-k there in the PARENT's numbering,
+        the rest hold index 0xFFFFFFFF and score 0."""
+        q = np.ascontiguousarray(q, dtype=self.dtype)
+        if q.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        m = q.shape[0]
+        qlabels = np.ascontiguousarray(qlabels, dtype=np.uint32)
+        if qlabels.shape != (m,):
+            raise ValueError(f"one label per query row: {m} rows, labels of shape {qlabels.shape}")
+        idx = np.empty((m, k), dtype=np.uint32)
+        sc = np.empty((m, k), dtype=self.dtype)
+        lens = np.empty(m, dtype=np.uint32)
+        fn = _lib.pmm_topk_f64_grouped if self.dtype == np.float64 else _lib.pmm_topk_f32_grouped
+        self.acquire()
+        try:
+            check(fn(self._h, ptr(q), m, ptr(qlabels), k, metric, ptr(idx), ptr(sc), ptr(lens)))
+        finally:
+            self.release()
+        return idx, sc, lens
 
     def index_map(self):
         """A derived handle's parent row numbers (uint32, ascending), one per

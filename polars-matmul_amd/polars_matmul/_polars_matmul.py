@@ -442,6 +442,171 @@ def _topk_subset(q, c, original, rv, sel: _Selection, kk: int, metric_id: int, c
 
 
 # ---------------------------------------------------------------------------
+# groups=: search every query row among the corpus rows of its own label (an
+# extension: Polars' over() / group_by on a search; with subset= it takes one
+# derived handle, three launches and one Python iteration per distinct label).
+# The labels of both sides are encoded on the host, the corpus' labels become
+# a handle derived on the device from the cached parent whose rows are stored
+# group by group (DeviceCorpus.partition), cached beside it under the parent's
+# key plus the label array's buffers, and one call searches every query in its
+# group's segment (DeviceCorpus.topk_grouped).
+# ---------------------------------------------------------------------------
+class _Groups:
+    """A checked ``groups=`` argument: uint32 labels of the query rows and of
+    the corpus rows in [0, G) (``_native.NO_GROUP``: matches nothing), the
+    corpus rows per label, and -- when the corpus labels' buffers persist
+    across calls -- their ``_arrow_key`` with the array that keeps them alive."""
+
+    __slots__ = ("qlabels", "clabels", "G", "sizes", "key", "keep")
+
+    def __init__(self, qlabels, clabels, G, key, keep):
+        self.qlabels, self.clabels, self.G, self.key, self.keep = qlabels, clabels, G, key, keep
+        self.sizes = np.bincount(clabels[clabels != _native.NO_GROUP], minlength=G).astype(np.int64)
+
+    def searched_max(self) -> int:
+        """Rows of the largest segment some query searches (0: none does)."""
+        ql = self.qlabels[self.qlabels != _native.NO_GROUP]
+        return int(self.sizes[ql].max()) if ql.size else 0
+
+
+def _label_array(obj, what: str):
+    """(the labels as one Arrow array of a plain hashable type, the array
+    whose buffers the caller passed)."""
+    if _is_polars_series(obj):
+        obj = obj.rechunk().to_arrow()
+    if isinstance(obj, pa.ChunkedArray):
+        obj = obj.combine_chunks() if obj.num_chunks != 1 else obj.chunk(0)
+    if isinstance(obj, np.ndarray):
+        if obj.ndim != 1:
+            raise ValueError(f"{what} labels must be 1-D, got shape {obj.shape}")
+        obj = pa.array(obj)
+    elif isinstance(obj, (list, tuple)):
+        obj = pa.array(obj)
+    if not isinstance(obj, pa.Array):
+        raise TypeError(f"{what} labels must be a Series or array, got {type(obj).__name__}")
+    arr = obj
+    if pa.types.is_dictionary(arr.type):  # a categorical: compared by value
+        arr = arr.dictionary_decode()
+    t = arr.type
+    if pa.types.is_string(t) or (hasattr(pa.types, "is_string_view") and pa.types.is_string_view(t)):
+        arr = pc.cast(arr, pa.large_string())
+    elif pa.types.is_binary(t):
+        arr = pc.cast(arr, pa.large_binary())
+    t = arr.type
+    if pa.types.is_nested(t) or pa.types.is_floating(t) or pa.types.is_null(t):
+        raise TypeError(f"{what} labels must be of a hashable type (integers, strings, categoricals), got {t}")
+    return arr, obj
+
+
+def _check_groups(groups, m: int, n: int) -> _Groups:
+    """TypeError for labels of the wrong kind or of two different types,
+    ValueError for a wrong length: all before any device work.  The corpus
+    labels are dictionary-encoded, the query labels looked up in that
+    dictionary; a null on either side matches nothing, and a query label the
+    corpus does not have searches nothing."""
+    if not isinstance(groups, (tuple, list)) or len(groups) != 2:
+        raise TypeError("groups must be a pair (left_labels, right_labels)")
+    right_original = groups[1]
+    left, _ = _label_array(groups[0], "left")
+    right, right_arrow = _label_array(groups[1], "right")
+    if left.type != right.type:
+        raise TypeError(f"groups labels must have one type, got {left.type} (left) and {right.type} (right)")
+    if len(left) != m:
+        raise ValueError(f"left labels have {len(left)} rows, the queries have {m}")
+    if len(right) != n:
+        raise ValueError(f"right labels have {len(right)} rows, the corpus has {n}")
+    enc = right.dictionary_encode()
+    none = pa.scalar(_native.NO_GROUP, type=pa.uint32())
+    clabels = pc.fill_null(pc.cast(enc.indices, pa.uint32()), none).to_numpy(zero_copy_only=False)
+    qlabels = pc.fill_null(pc.cast(pc.index_in(left, value_set=enc.dictionary), pa.uint32()), none)
+    qlabels = qlabels.to_numpy(zero_copy_only=False)
+    return _Groups(np.ascontiguousarray(qlabels, dtype=np.uint32), np.ascontiguousarray(clabels, dtype=np.uint32),
+                   len(enc.dictionary), _persistent_key(right_original, right_arrow), right_arrow)
+
+
+def _cached_partition(parent, parent_key, grp: _Groups, c: np.ndarray, compute: str):
+    """(an ACQUIRED partitioned DeviceCorpus of the cached ``parent`` for the
+    corpus labels of ``grp``, transient) as ``_cached_subset``, or (None,
+    False) when it would not fit in half of the free HBM."""
+    key = None if grp.key is None else parent_key + ("groups", grp.key)
+    need = _native.partitioned_device_bytes(int(grp.sizes.sum()), c.shape[1], grp.G, c.dtype, compute)
+    with _cache_lock:
+        hit = _cache.get(key) if key is not None else None
+        if hit is not None:
+            _cache.move_to_end(key)
+            return hit[1].acquire(), False
+        if not _fits_device(need):
+            return None, False
+        dc = parent.partition(grp.clabels, grp.G)
+        if key is None or need > _CACHE_BYTES:
+            return dc.acquire(), True
+        _cache[key] = (grp.keep, dc)  # the entry keeps the label array's buffers alive
+        total = sum(v[1].nbytes for v in _cache.values())
+        while total > _CACHE_BYTES and len(_cache) > 1:
+            _, (_, old) = _cache.popitem(last=False)
+            total -= old.nbytes
+            old.close()  # freed now, or by its last in-flight user
+        return dc.acquire(), False
+
+
+def _topk_grouped(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, compute: str):
+    """(idx (m, kk), scores (m, kk), lens (m,)): row i's first lens[i] slots
+    are its top-kk among the corpus rows of its label, indices numbering c.  On
+    the device from a partitioned handle of the cached corpus when there is
+    one (one GPU, f32 or f64 rows); else the host fallback: one uncached
+    search per distinct label on that label's rows, mapped back."""
+    dc, transient = None, False
+    if len(_native.get_devices()) <= 1 and compute != "bf16" and grp.sizes.sum() > 0:
+        parent_key = _corpus_key(original, rv, c, compute)
+        parent = _cached_corpus(original, rv, c, compute) if parent_key is not None else None
+        if parent is not None:
+            try:
+                if parent.shards == 1:
+                    dc, transient = _cached_partition(parent, parent_key, grp, c, compute)
+            finally:
+                parent.release()
+    if dc is not None:
+        try:
+            idx, sc, lens = dc.topk_grouped(q, grp.qlabels, kk, metric_id)
+            if not transient:
+                _reaccount_cache(dc)
+        finally:
+            dc.release()
+            if transient:
+                dc.close()
+        return idx, sc, lens
+    m = q.shape[0]
+    idx = np.full((m, kk), 0xFFFFFFFF, dtype=np.uint32)
+    sc = np.zeros((m, kk), dtype=q.dtype)
+    lens = np.zeros(m, dtype=np.uint32)
+    mode = _native.COMPUTE_BF16 if compute == "bf16" else _native.COMPUTE_F32
+    for g in np.unique(grp.qlabels[grp.qlabels != _native.NO_GROUP]):
+        ids = np.flatnonzero(grp.clabels == g).astype(np.uint32)
+        if ids.size == 0:
+            continue
+        rows = np.flatnonzero(grp.qlabels == g)
+        kg = min(kk, int(ids.size))
+        gi, gs = _native.topk_host(np.ascontiguousarray(q[rows]), np.ascontiguousarray(c[ids]), kg, metric_id,
+                                   compute=mode)
+        idx[rows, :kg] = ids[gi]
+        sc[rows, :kg] = gs
+        lens[rows] = kg
+    return idx, sc, lens
+
+
+def _ragged_topk_arrow(idx: np.ndarray, scores: np.ndarray, lens: np.ndarray) -> pa.Array:
+    """The lists' first lens[i] entries as LargeList<Struct>: no padding reaches Arrow."""
+    keep = np.arange(idx.shape[1], dtype=np.int64)[None, :] < lens.astype(np.int64)[:, None]
+    struct = pa.StructArray.from_arrays(
+        [pa.array(idx[keep], type=pa.uint32()), pa.array(scores[keep].astype(np.float64, copy=False), type=pa.float64())],
+        fields=list(_TOPK_STRUCT),
+    )
+    offsets = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    return pa.LargeListArray.from_arrays(pa.array(offsets, type=pa.int64()), struct)
+
+
+# ---------------------------------------------------------------------------
 # Device list (multi-GPU through the drop-in: include/pmm.h pmm_set_devices).
 # PMM_DEVICES = "all" or a comma list is applied on the first top-k call (not
 # at import: counting devices initialises the HIP runtime).
@@ -504,7 +669,7 @@ def _wrap(arrow_arr: pa.Array, name: str, polars_out: bool):
 # ---------------------------------------------------------------------------
 # Public extension functions
 # ---------------------------------------------------------------------------
-def _topk(left, right, k, metric, compute="f32", subset=None):
+def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
     """src/lib.rs:33-55 -> src/matmul.rs:473-519 topk_impl.  compute="bf16"
     (an extension): both columns are read as f32 whatever their dtype and
     searched on the bf16 path (the numpy-level ``topk``'s compute="bf16").
@@ -513,7 +678,14 @@ def _topk(left, right, k, metric, compute="f32", subset=None):
     false) or integer row ids (sorted and de-duplicated here).  The returned
     ``index`` values number ``right``, k clips to the number of selected rows
     (the reference's clip-to-n rule on the searched rows), and an empty
-    selection raises what an empty corpus raises."""
+    selection raises what an empty corpus raises.
+    groups (an extension): ``(left_labels, right_labels)`` -- Series, Arrow
+    arrays or numpy arrays of one hashable type (integers, strings,
+    categoricals), one label per row of ``left`` and of ``right``.  Every query
+    row is searched only among the corpus rows with its own label; a null label
+    on either side matches nothing.  The lists are ragged: row i holds
+    min(k, corpus rows of its label) entries, none when the corpus has no such
+    label.  Not together with ``subset``."""
     k = _as_usize(k)
     if not isinstance(metric, str):
         raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
@@ -522,7 +694,10 @@ def _topk(left, right, k, metric, compute="f32", subset=None):
     t = time.perf_counter()
     lv = _to_arrow(left)
     rv = _to_arrow(right)
+    if groups is not None and subset is not None:
+        raise ValueError("groups= and subset= cannot be combined: give the rows to leave out a null label")
     sel = _check_subset(subset, _nrows(rv)) if subset is not None else None
+    grp = _check_groups(groups, _nrows(lv), _nrows(rv)) if groups is not None else None
     if _nrows(lv) == 0:  # src/matmul.rs:480-487
         empty = pa.array([], type=pa.large_list(_TOPK_STRUCT))
         return _wrap(empty, "topk", polars_out)
@@ -539,6 +714,18 @@ def _topk(left, right, k, metric, compute="f32", subset=None):
         raise _dim_mismatch(q.shape[1], c.shape[1])
     kk = min(k, c.shape[0] if sel is None else sel.count)  # src/matmul.rs:443
     m = q.shape[0]
+    if grp is not None:
+        kk = min(k, grp.searched_max())  # the clip-to-n rule on the largest searched segment
+        if kk == 0:
+            idx, sc = np.zeros((m, 0), dtype=np.uint32), np.zeros((m, 0), dtype=np.float64)
+            lens = np.zeros(m, dtype=np.uint32)
+        else:
+            _apply_devices_env()
+            idx, sc, lens = _topk_grouped(q, c, right, rv, grp, kk, metric_id, compute)
+            t = _lap("device", t)
+        out = _wrap(_ragged_topk_arrow(idx, sc, lens), "topk", polars_out)
+        _lap("assemble", t)
+        return out
     if kk == 0:
         idx = np.zeros((m, 0), dtype=np.uint32)
         sc = np.zeros((m, 0), dtype=np.float64)
