@@ -523,6 +523,46 @@ int pmm_topk_f64_corpus(const pmm_corpus *corpus, const double *q, int64_t m, in
 int pmm_topk_bf16_corpus(const pmm_corpus *corpus, const float *q, int64_t m, int64_t k,
                          int metric, uint32_t *out_idx, float *out_score);
 
+/* Range search: every corpus row whose score passes a threshold, for each
+ * query row (host queries in, host results out).  Corpus row j is a hit of
+ * query row i iff its score s -- the exact f32 score, the bits pmm_topk_f32
+ * returns -- satisfies s >= threshold (cosine, dot) or s <= threshold
+ * (euclidean): IEEE comparisons, so -0.0 and +0.0 are the same threshold and
+ * a NaN score is never a hit.  A NaN threshold is PMM_ERR_ARG; +-inf are legal.
+ * The result is CSR: out_offsets (m + 1 entries) always takes the exact
+ * bounds -- out_offsets[i + 1] - out_offsets[i] is the hit count of row i --
+ * and *total = out_offsets[m].  When total <= cap (the entries out_idx and
+ * out_score have room for), row i's hits fill out_idx / out_score
+ * [out_offsets[i], out_offsets[i + 1]), best first in the total order of every
+ * pmm_topk_* entry (score, then lower index): the first count_i entries of row
+ * i of pmm_topk_f32_corpus with k = n, indices and score bits.  When total >
+ * cap the call still returns PMM_OK and writes nothing to out_idx / out_score:
+ * call again with room.  cap = 0 with null out_idx / out_score is the
+ * count-only form.
+ * One pass of the f32 top-k kernel's tiles, staging and K-ordered chain (the
+ * 128 x 128 or 256 x 256 variant by the problem's size; PMM_GEMM_VARIANT = 0
+ * or 3, per call, chooses) emits each element that passes a conservative
+ * per-row bound and then the exact comparison as a record (ordered key |
+ * column, query row) through one global cursor; the hit counts are read back
+ * (the call's one wait before the lists), the keys are binned by row, each
+ * row's segment sorted -- up to 128 keys in a wave, up to PMM_RANGE_SORT_MAX
+ * (8192; read per call, can only be lowered) in a workgroup's LDS, longer
+ * ones through pmm_topk_f32_corpus with k = the count -- and decoded.  The
+ * keys of a row are unique, so the lists do not depend on the order the
+ * records arrived in.  The screen image is never used.
+ * Serves an f32 handle of one shard, plain or derived by pmm_corpus_subset_*
+ * (a derived handle returns the PARENT's row numbers; its ascending map keeps
+ * the tie order).  A sharded handle: PMM_ERR_UNSUPPORTED; a partitioned
+ * handle: PMM_ERR_ARG (the text of pmm_topk_f32_corpus); an f64 or bf16
+ * handle: PMM_ERR_ARG.  Null corpus, q, out_offsets or total, negative m or
+ * cap, a bad metric: PMM_ERR_ARG before any device call.  m = 0: PMM_OK with
+ * out_offsets[0] = 0.  Thread-safe like the other handle entries (the calling
+ * thread's stream and arena); synchronises before it returns.  No reference
+ * counterpart. */
+int pmm_range_f32_corpus(const pmm_corpus *corpus, const float *q, int64_t m, float threshold, int metric,
+                         int64_t cap, int64_t *out_offsets /* m + 1 */, uint32_t *out_idx, float *out_score,
+                         int64_t *total);
+
 /* Per-kernel timing on the launch stream (hipEvents around each launch).
  * enable=1 starts recording; pmm_timing_read returns the summed milliseconds
  * and launch count of kernels whose name contains `kernel` since the last

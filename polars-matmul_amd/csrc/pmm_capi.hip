@@ -2477,6 +2477,13 @@ static int wrong_handle(const pmm_corpus *h) {
   return fail(PMM_ERR_ARG, "the corpus handle holds %s rows: use %s", kRows[h->dtype], kEntry[h->dtype]);
 }
 
+// What every ungrouped search (top-k, range) answers on a partitioned handle.
+static int partitioned_handle(const pmm_corpus *h) {
+  return fail(PMM_ERR_ARG, "the corpus handle is partitioned (pmm_corpus_partition): its index map ascends only "
+                           "inside a group, so an ungrouped search would break the tie order; use pmm_topk_%s_grouped",
+              h->dtype == PMM_DTYPE_F64 ? "f64" : "f32");
+}
+
 // A derived handle's lists leave in the parent's numbering: one launch over
 // the m x k device index buffer between the executor and the download.  A
 // handle without a map launches nothing.
@@ -2677,10 +2684,7 @@ template <typename Score, typename OneShard>
 static int corpus_topk(const pmm_corpus *h, int dtype, const Score *q, int64_t m, int64_t k, int metric,
                        uint32_t *out_idx, Score *out_score, OneShard one_shard) {
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->partitioned())
-    return fail(PMM_ERR_ARG, "the corpus handle is partitioned (pmm_corpus_partition): its index map ascends only "
-                             "inside a group, so an ungrouped search would break the tie order; use pmm_topk_%s_grouped",
-                h->dtype == PMM_DTYPE_F64 ? "f64" : "f32");
+  if (h->partitioned()) return partitioned_handle(h);
   if (h->dtype != dtype) return wrong_handle(h);
   int rc = validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
@@ -3724,6 +3728,240 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
     return topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.rows_as<float>(), dp, h->n, h->d, k, metric,
                                 0u, *oi, *os, b + off_w, ws_need, s, dev, shard_norms<float>(h, x, metric), false, img);
   });
+}
+
+// Range search.  The tile variant of the emit pass: the ones
+// the range mode is instantiated for, PMM_GEMM_VARIANT (per call) choosing
+// among them, else choose_variant's size rule between 128 x 128 and 256 x 256.
+static int range_variant(int64_t m, int64_t n, int cus) {
+  const char *ev = getenv("PMM_GEMM_VARIANT");
+  const int env = ev ? atoi(ev) : -1;
+  if (env >= 0 && gemm_f32_range_variant(env)) return env;
+  return cdiv(m, 256) * cdiv(n, 256) < 4 * (int64_t)cus ? 0 : 3;
+}
+
+// The longest segment the in-LDS sort takes: kRangeSortMax, or a lower
+// PMM_RANGE_SORT_MAX (per call; at least the wave tier's 128) so that a test
+// reaches the any-k route with a small corpus.
+static int64_t range_sort_max() {
+  const char *e = getenv("PMM_RANGE_SORT_MAX");
+  const int64_t v = e ? atoll(e) : 0;
+  return (v >= kRangeWaveMax && v < kRangeSortMax) ? v : kRangeSortMax;
+}
+
+int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
+                         int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!q || !out_offsets || !total) return fail(PMM_ERR_ARG, "null argument");
+  if (m < 0 || cap < 0)
+    return fail(PMM_ERR_ARG, "negative size (m=%lld cap=%lld)", (long long)m, (long long)cap);
+  if (cap > 0 && (!out_idx || !out_score))
+    return fail(PMM_ERR_ARG, "null argument: cap > 0 needs out_idx and out_score (cap = 0 is the count-only form)");
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
+  if (h->partitioned()) return partitioned_handle(h);
+  if (h->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16"};
+    return fail(PMM_ERR_ARG, "range search takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
+  }
+  if (h->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no range search: use a handle of one shard",
+                (int)h->shards.size());
+  if ((rc = validate_sizes(m, h->n, h->d, 0, false))) return rc;
+  *total = 0;
+  out_offsets[0] = 0;
+  if (m == 0) return PMM_OK;
+
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  const int64_t n = h->n, d = h->d, dp = h->dp;
+  const int cus = g_dev[dev].cus;
+  Plan p;
+  p.variant = range_variant(m, n, cus);
+  const int bn = gemm_f32_bn(p.variant);
+  plan_units(m, n, gemm_f32_bm(p.variant), bn, cus, 0.5, 1 << 20, p);
+  // the record arena never needs more than m x n records
+  const uint64_t rcap = (uint64_t)std::min<int64_t>(cap, m * n);
+
+  // arena: queries | [work counter, cursor | hit counts | bin cursors] (one
+  // fill) | query norms | offsets | row list | survivor queues | records (key,
+  // row) | binned keys; the decoded lists reuse the record keys' bytes
+  size_t off = al256((size_t)m * dp * 4);
+  const size_t off_ctl = off;
+  off += 256;
+  const size_t off_hits = off;
+  off += al256((size_t)m * 4);
+  const size_t off_cur = off;
+  off += al256((size_t)m * 4);
+  const size_t off_qn = off;
+  off += al256((size_t)m * 4);
+  const size_t off_offs = off;
+  off += al256((size_t)(m + 1) * 8);
+  const size_t off_rows = off;
+  off += al256((size_t)m * 4);
+  const size_t off_wq = off;
+  off += al256((size_t)p.grid * gemm_f32_nw(p.variant) * 32 * bn * 8);
+  const size_t off_rkey = off;
+  off += al256((size_t)rcap * 8);
+  const size_t off_rrow = off;
+  off += al256((size_t)rcap * 4);
+  const size_t off_keys = off;
+  off += al256((size_t)rcap * 8);
+  void *base;
+  if ((rc = arena(dev, s, off, &base))) return rc;
+  char *b = (char *)base;
+  const float *dq = (const float *)b;
+  if ((rc = upload_padded(b, q, m, d, dp, 4, s))) return rc;
+  HIP_TRY(hipMemsetAsync(b + off_ctl, 0, off_qn - off_ctl, s));
+  float *qn = (float *)(b + off_qn);
+  if (metric != kMetricDot) {
+    Timed t("norms_f32", s);
+    HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+  }
+  // the threshold's composite: okey32 of its ranking value (-0 folds onto +0,
+  // so both zeros compare alike), index part 0 -- at or above it is a hit
+  const float rank = metric == kMetricEuclidean ? -threshold : threshold;
+  uint32_t tu;
+  memcpy(&tu, &rank, 4);
+  if ((tu << 1) == 0u) tu = 0u;
+  const uint32_t tkey = (tu & 0x80000000u) ? ~tu : (tu | 0x80000000u);
+
+  GemmF32Args a{};
+  a.q = dq;
+  a.c = x.rows_as<float>();
+  a.qn = qn;
+  a.cn = shard_norms<float>(h, x, metric);
+  a.cpre = a.cn ? a.cn + n : nullptr;
+  a.ldq = dp;
+  a.ldc = dp;
+  a.M = (int)m;
+  a.N = (int)n;
+  a.D = (int)dp;
+  a.metric = metric;
+  a.QB = p.QB;
+  a.S = p.S;
+  a.tps = p.tps;
+  a.ntiles = p.T;
+  a.units = p.units;
+  a.counter = (unsigned *)(b + off_ctl);
+  a.wq = (unsigned long long *)(b + off_wq);
+  a.rthr = (unsigned long long)tkey << 32;
+  a.rcur = (unsigned long long *)(b + off_ctl + 8);
+  a.rhits = (unsigned *)(b + off_hits);
+  a.rkey = (unsigned long long *)(b + off_rkey);
+  a.rrow = (uint32_t *)(b + off_rrow);
+  a.rcap = rcap;
+  {
+    Timed t("gemm_f32_range", s);
+    HIP_TRY(launch_gemm_f32_range(a, p.variant, p.grid, s));
+  }
+  // the count: the rows' hits and the cursor, the call's one wait before the lists
+  std::vector<uint32_t> hits((size_t)m);
+  unsigned long long cursor = 0;
+  {
+    Timed t("d2h", s);
+    HIP_TRY(hipMemcpyAsync(hits.data(), a.rhits, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&cursor, a.rcur, 8, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < m; i++) out_offsets[i + 1] = out_offsets[i] + (int64_t)hits[(size_t)i];
+  const int64_t tot = out_offsets[m];
+  if ((unsigned long long)tot != cursor)
+    return fail(PMM_ERR_HIP, "range search: the rows' counts (%lld) and the record cursor (%llu) disagree",
+                (long long)tot, cursor);
+  *total = tot;
+  if (tot > cap || tot == 0) return PMM_OK;
+
+  // rows by sort tier: (128, smax] in a workgroup's LDS, longer ones by the
+  // handle's ordinary top-k at the end
+  const int64_t smax = range_sort_max();
+  std::vector<int> mid, longr;
+  int64_t mid_max = 0;
+  for (int64_t i = 0; i < m; i++) {
+    const int64_t c = (int64_t)hits[(size_t)i];
+    if (c > smax) longr.push_back((int)i);
+    else if (c > kRangeWaveMax) {
+      mid.push_back((int)i);
+      mid_max = std::max(mid_max, c);
+    }
+  }
+  int64_t *d_offs = (int64_t *)(b + off_offs);
+  unsigned long long *keys = (unsigned long long *)(b + off_keys);
+  HIP_TRY(hipMemcpyAsync(d_offs, out_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+  {
+    Timed t("range_bin", s);
+    HIP_TRY(launch_range_bin(a.rkey, a.rrow, tot, d_offs, (unsigned *)(b + off_cur), keys, s));
+  }
+  {
+    Timed t("range_sort_wave", s);
+    HIP_TRY(launch_range_sort_wave(keys, d_offs, (int)m, s));
+  }
+  if (!mid.empty()) {
+    HIP_TRY(hipMemcpyAsync(b + off_rows, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, s));
+    Timed t("range_sort_block", s);
+    HIP_TRY(launch_range_sort_block(keys, d_offs, (const int *)(b + off_rows), (int)mid.size(),
+                                    next_pow2((int)mid_max), s));
+  }
+  RangeDecodeArgs da{};
+  da.keys = keys;
+  da.total = tot;
+  da.offsets = d_offs;
+  da.m = (int)m;
+  da.metric = metric;
+  da.d = (int)d;
+  da.map = h->map;
+  da.q = dq;
+  da.c = a.c;
+  da.qn = qn;
+  da.cn = a.cn;
+  da.ldq = dp;
+  da.ldc = dp;
+  da.out_idx = (uint32_t *)(b + off_rkey);  // (the records are binned: their bytes are free)
+  da.out_score = (float *)(b + off_rkey + (size_t)tot * 4);
+  {
+    Timed t("range_decode", s);
+    HIP_TRY(launch_range_decode(da, s));
+  }
+  {
+    Timed t("d2h", s);
+    HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // Segments past the in-LDS sort: the row's list is the first count entries
+  // of its top-k list with k = count (the defining property), so those rows go
+  // through pmm_topk_f32_corpus, a batch of at most 2^26 list entries at a time.
+  for (size_t i0 = 0; i0 < longr.size();) {
+    size_t i1 = i0;
+    int64_t kmax = 0;
+    while (i1 < longr.size()) {
+      const int64_t k2 = std::max<int64_t>(kmax, hits[(size_t)longr[i1]]);
+      if (i1 > i0 && (int64_t)(i1 - i0 + 1) * k2 > (int64_t(1) << 26)) break;
+      kmax = k2;
+      i1++;
+    }
+    const size_t r = i1 - i0;
+    std::vector<float> qb(r * (size_t)d);
+    for (size_t j = 0; j < r; j++) memcpy(&qb[j * (size_t)d], q + (size_t)longr[i0 + j] * d, (size_t)d * 4);
+    std::vector<uint32_t> ti(r * (size_t)kmax);
+    std::vector<float> ts(r * (size_t)kmax);
+    if ((rc = pmm_topk_f32_corpus(h, qb.data(), (int64_t)r, kmax, metric, ti.data(), ts.data()))) return rc;
+    for (size_t j = 0; j < r; j++) {
+      const int row = longr[i0 + j];
+      const size_t c = hits[(size_t)row];
+      memcpy(out_idx + out_offsets[row], &ti[j * (size_t)kmax], c * 4);
+      memcpy(out_score + out_offsets[row], &ts[j * (size_t)kmax], c * 4);
+    }
+    i0 = i1;
+  }
+  return PMM_OK;
 }
 
 int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,

@@ -75,6 +75,17 @@ struct GemmF32Args {
   // flags set when a row's kept band outgrew its candidate segment
   const float *eps;
   unsigned *ovf;
+  // range mode (f32 kernel, mode 2): the threshold as a composite (okey32 of
+  // its ranking value << 32; an element hits iff its composite is at or above
+  // it), the record arena -- rcap records as key (okey32(rank value) << 32 |
+  // ~column) and query row, filled through the cursor *rcur, which counts
+  // every hit, stored or not -- and the rows' hit counts (zeroed per call)
+  unsigned long long rthr;
+  unsigned long long *rcur;
+  unsigned *rhits;
+  unsigned long long *rkey;
+  uint32_t *rrow;
+  unsigned long long rcap;
 };
 
 struct MergeArgs {
@@ -125,13 +136,48 @@ hipError_t launch_norms_f64(const double *a, int64_t rows, int64_t d, int64_t ld
 // Tile-shape variant of the f32 GEMM (see pmm_kernels.hip): 0 = 128x128,
 // 1 = 128x256, 2 = 256x128 (2 waves/SIMD), 3 = 256x256 (2 waves/SIMD),
 // 4 = 128x64, 5 = 128x64 column-split (2 waves/SIMD, fused top-k only).
-// mode 0 = fused top-k, 1 = store.  grid = number of persistent workgroups.
+// mode 0 = fused top-k, 1 = store (2 = range: launch_gemm_f32_range).  grid =
+// number of persistent workgroups.
 hipError_t launch_gemm_f32(const GemmF32Args &a, int variant, int mode, int grid, hipStream_t s);
 int gemm_f32_bm(int variant);   // query rows per workgroup
 int gemm_f32_bn(int variant);   // corpus columns per tile
 int gemm_f32_nw(int variant);   // waves per workgroup
 int gemm_f32_segs(int variant); // candidate segments per (row, corpus split): 2 for the column split
 size_t gemm_f32_lds_bytes(int variant, int mode, int capg);
+// mode 2 = range (GemmF32Args::rthr ..): the same tiles, staging and chain,
+// every element at or above the threshold emitted as a record.  Instantiated
+// for the variants gemm_f32_range_variant names (0 and 3).
+bool gemm_f32_range_variant(int variant);
+hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hipStream_t s);
+// ---- range search: records -> per-row best-first lists (pmm_range.hip) ----
+// Segments of up to kRangeWaveMax keys sort in one wave's registers, up to
+// kRangeSortMax in one workgroup's LDS (64 KiB of keys).
+constexpr int kRangeWaveMax = 128;
+constexpr int kRangeSortMax = 8192;
+// keys[offsets[row] + (the row's next free place)] = rkey[i], row = rrow[i],
+// i < total; cur (m words, zeroed by the caller) holds the rows' places
+hipError_t launch_range_bin(const unsigned long long *rkey, const uint32_t *rrow, int64_t total,
+                            const int64_t *offsets, unsigned *cur, unsigned long long *keys, hipStream_t s);
+// every row's segment of 2 .. kRangeWaveMax keys sorted best first, one wave per row
+hipError_t launch_range_sort_wave(unsigned long long *keys, const int64_t *offsets, int m, hipStream_t s);
+// the segments of rows[0 .. r) (each of at most pmax <= kRangeSortMax keys,
+// pmax a power of two) sorted best first, one workgroup per row
+hipError_t launch_range_sort_block(unsigned long long *keys, const int64_t *offsets, const int *rows, int r,
+                                   int pmax, hipStream_t s);
+struct RangeDecodeArgs {
+  const unsigned long long *keys;  // binned, sorted
+  int64_t total;
+  const int64_t *offsets;          // m + 1 segment bounds (device)
+  int m, metric, d;
+  const uint32_t *map;             // a derived handle's index map, or null
+  // cosine: what a +0.0 score's sign is recomputed from (see zero_sign_kernel)
+  const float *q, *c, *qn, *cn;
+  int64_t ldq, ldc;
+  uint32_t *out_idx;
+  float *out_score;
+};
+// keys -> (index, score) by the top-k epilogue's rules
+hipError_t launch_range_decode(const RangeDecodeArgs &a, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, int loader, hipStream_t s);
 // Threshold seeding: gthr[row] = (k-th best composite of the row's ns
 // materialised scores S[row][0..ns)) - 1, one wave per row; ns <= kSeedMaxNs.

@@ -315,6 +315,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         lo_w[lane] = prefilter_bound<METRIC>(t, qv);
         cnt_w[lane] = 0u;
       }
+      if (MODE == 2) {
+        // range mode: the call's threshold composite for every row (its key is
+        // never 0 or ~0, prefilter_bound's reserved values); the bound is fixed
+        // for the unit, cnt_w counts the row's hits of this unit
+        const u64 t = (grow < a.M) ? a.rthr : ~0ull;
+        thr_w[lane] = t;
+        lo_w[lane] = prefilter_bound<METRIC>(t, qv);
+        cnt_w[lane] = 0u;
+      }
     }
     wave_sync();
 
@@ -342,7 +351,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
 #pragma unroll
       for (int i = 0; i < BP; i++)
         if (AS + i >= lo && AS + i < hi) dma(rb, st + G::A_IN_STAGE + (i * NW + wid) * BPIECE, b_voff[i], BDW);
-      if (MODE == 0 && XFORM && ks == 0 && wid == 0 && lo == 0) {
+      if (MODE != 1 && XFORM && ks == 0 && wid == 0 && lo == 0) {
         // the tile's pre-filter column factors ride with its first K step
         const int col0 = tile * G::BN;
         const __amdgpu_buffer_rsrc_t rc =
@@ -545,7 +554,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
 #pragma unroll
       for (int e = 0; e < 16; e++) {
         rv[e] = qex_w[acc_row(e, h)];
-        lo[e] = (MODE == 0) ? lo_w[acc_row(e, h)] : 0.0f;
+        lo[e] = (MODE != 1) ? lo_w[acc_row(e, h)] : 0.0f;
       }
       if (MODE == 1) {
         // ---- store epilogue (.pmm.matmul, or materialised scores) ----
@@ -709,7 +718,51 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
           n_surv += (uint64_t)qlen;
         }
         if (PMM_ABL(a.ablate) == 2) qlen = 0;  // ablation: pre-filter only
-        if (qlen) {
+        if (MODE == 2) {
+          // ---- range epilogue, pass 2: every queued element re-scored exactly
+          // and compared with the threshold composite (at or above it: a hit;
+          // a NaN score's key 0 is below every threshold's).  The wave's hits
+          // of a batch take consecutive record slots from one add on the global
+          // cursor; a slot at or past the arena's capacity is counted, not
+          // stored.  The rows' counts gather in LDS until the unit ends.
+          if (qlen) {
+            if (!G::CNL || qlen > a.qcap) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (G::CNL) wave_sync();
+            for (int base = 0; base < qlen; base += 64) {
+              const int i = base + lane;
+              bool hit = false;
+              u64 comp = 0ull;
+              int rl = 0;
+              if (i < qlen) {
+                const u64 it = (G::CNL && i < a.qcap) ? lq[i]
+                                                      : __hip_atomic_load(gq + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const float v = __uint_as_float((uint32_t)it);
+                rl = (int)((it >> 32) & 31u);
+                const int tc = (int)(it >> 37);
+                const int gcol = col0 + tc;
+                const float sc =
+                    exact_score<METRIC>(v, XFORM ? qex_w[rl] : 0.0f, XFORM ? (G::CNL ? cnt_t[tc] : a.cn[gcol]) : 0.0f);
+                const uint32_t key = okey32(METRIC == kMetricEuclidean ? -sc : sc);
+                comp = ((u64)key << 32) | (u64)(~(uint32_t)gcol);
+                hit = comp >= thr_w[rl];
+              }
+              const u64 hm = __ballot(hit);
+              if (hm) {
+                u64 slot0 = 0ull;
+                if (lane == 0) slot0 = atomicAdd(a.rcur, (u64)__popcll(hm));
+                slot0 = wave_uniform_u64(slot0);
+                if (hit) {
+                  atomicAdd(&cnt_w[rl], 1u);
+                  const u64 slot = slot0 + (u64)lanes_below(hm);
+                  if (slot < a.rcap) {
+                    a.rkey[slot] = comp;
+                    a.rrow[slot] = (uint32_t)(wrow0 + rl);
+                  }
+                }
+              }
+            }
+          }
+        } else if (qlen) {
           // queue entries past the LDS part: their stores reached L2
           if (!G::CNL || qlen > a.qcap) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           if (G::CNL) wave_sync();  // every lane's LDS queue entries written
@@ -761,6 +814,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         if (grow < a.M) a.cnt[(int64_t)grow * a.S + seg] = cnt_w[lane];
       }
     }
+    if (MODE == 2) {
+      // one add per row this unit touched
+      wave_sync();
+      if (lane < 32) {
+        const int grow = wrow0 + lane;
+        const unsigned nh = cnt_w[lane];
+        if (grow < a.M && nh) atomicAdd(a.rhits + grow, nh);
+      }
+    }
   }
   if (timing && lane == 0) {
     atomicAdd(a.stats + 0, (u64)(stamp() - t_start));
@@ -784,7 +846,7 @@ static hipError_t launch_gemm_f32_t(const GemmF32Args &a_in, int grid, size_t ld
   GemmF32Args a = a_in;
   a.qcap = 0;
   static const bool lq_on = !(getenv("PMM_F32_QCAP") && atoi(getenv("PMM_F32_QCAP")) == 0);
-  if (MODE == 0 && GemmShape<NB, NW, AK>::CNL && lq_on && lds < 160 * 1024) {
+  if (MODE != 1 && GemmShape<NB, NW, AK>::CNL && lq_on && lds < 160 * 1024) {
     const size_t per = (160 * 1024 - lds) / (NW * 8);
     a.qcap = (int)(std::min<size_t>(per, 32 * 32 * NB) / 64 * 64);
     lds += (size_t)NW * a.qcap * 8;
@@ -839,6 +901,25 @@ hipError_t launch_gemm_f32(const GemmF32Args &a, int variant, int mode, int grid
     case 5: return mode == 0 ? launch_gemm_f32_small<2, 8>(a, variant, mode, grid, s) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
+}
+
+// Range mode (MODE 2; pmm_range_f32_corpus): the 128 x 128 and 256 x 256
+// variants, every metric.
+template <int NB, int NW, bool AK>
+static hipError_t launch_gemm_f32_range_v(const GemmF32Args &a, int grid, size_t lds, hipStream_t s) {
+  if (a.metric == kMetricCosine) return launch_gemm_f32_t<NB, NW, 2, kMetricCosine, AK>(a, grid, lds, s);
+  if (a.metric == kMetricDot) return launch_gemm_f32_t<NB, NW, 2, kMetricDot, AK>(a, grid, lds, s);
+  return launch_gemm_f32_t<NB, NW, 2, kMetricEuclidean, AK>(a, grid, lds, s);
+}
+bool gemm_f32_range_variant(int variant) { return variant == 0 || variant == 3; }
+hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
+  if (variant == 3) return launch_gemm_f32_range_v<8, 8, false>(a, grid, gemm_f32_lds_bytes(3, 2, 0), s);
+  if (variant != 0) return hipErrorInvalidValue;
+  // (resident query rows as launch_gemm_f32_small decides them)
+  const size_t ak = gemm_f32_lds_bytes_ak(0, 2, 0, a.D >> 5);
+  static const int ak_env = getenv("PMM_F32_AK") ? atoi(getenv("PMM_F32_AK")) : PMM_F32_AK;
+  if (ak_env && a.tps > 1 && ak <= 160 * 1024) return launch_gemm_f32_range_v<4, 4, true>(a, grid, ak, s);
+  return launch_gemm_f32_range_v<4, 4, false>(a, grid, gemm_f32_lds_bytes(0, 2, 0), s);
 }
 
 // ===========================================================================

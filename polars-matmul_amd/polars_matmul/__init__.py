@@ -14,7 +14,10 @@ as a bf16 handle (half an f32 handle's HBM) while its Series is reused.
 device, and returns indices that number the full corpus.  ``groups=`` (an
 extension; ``by=`` / ``corpus_by=`` on the namespace) searches every query row
 only among the corpus rows that carry its own label, all labels in one call
-against a handle whose rows are stored group by group.  The numerics run on MI355X through hand-written HIP
+against a handle whose rows are stored group by group.  ``.pmm.within(corpus,
+threshold, metric)`` (an extension; ``within`` / ``_within`` without Polars) is
+range search: every corpus row whose score passes the threshold, as ragged
+lists, on Float32 columns.  The numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
 Usage:
@@ -44,13 +47,14 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     _check_subset,
     _matmul,
     _topk,
+    _within,
     get_devices,
     set_devices,
 )
 from polars_matmul import _native
 
 __version__ = "0.1.4"
-__all__ = ["PmmNamespace", "topk", "matmul", "set_devices", "get_devices"]
+__all__ = ["PmmNamespace", "topk", "within", "matmul", "set_devices", "get_devices"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
 Compute = Literal["f32", "bf16"]
@@ -115,6 +119,53 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     if ids is not None:
         idx = ids[idx]
     return idx, sc.astype(np.float64, copy=False)
+
+
+def within(queries: np.ndarray, corpus: np.ndarray, threshold: float, metric: Metric = "cosine", subset=None,
+           compute: Compute = "f32"):
+    """numpy-level range search (an extension): every corpus row whose score
+    is >= ``threshold`` (cosine, dot) or <= ``threshold`` (euclidean), per query
+    row.  Returns CSR arrays (offsets int64 [m + 1], indices uint32 [total],
+    scores float64 [total]): row i's hits are entries [offsets[i],
+    offsets[i + 1]), best first, the f32 scores widened as ``topk``'s.
+    Float32 matrices only (Float64 input and compute="bf16" raise TypeError).
+    The corpus goes through the corpus cache: a C-contiguous float32 matrix of
+    at least 1 MiB is uploaded once and found again by its address while the
+    cache holds it (do not write to it in place meanwhile;
+    ``_polars_matmul.clear_corpus_cache()`` forgets it).
+    subset: a bool mask of len(corpus) or integer row ids; only those rows are
+    searched, from a handle derived on the device, and the indices number
+    ``corpus``."""
+    from polars_matmul._polars_matmul import _within_device, _within_f32_only
+
+    q = np.asarray(queries)
+    c = np.asarray(corpus)
+    if _native.check_compute(compute) == "bf16":
+        raise _within_f32_only('compute="bf16" has no range search')
+    if q.dtype != np.float32 or c.dtype != np.float32:
+        raise _within_f32_only(f"got {q.dtype} queries and a {c.dtype} corpus")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    if q.ndim != 2 or c.ndim != 2:
+        raise TypeError(f"expected 2-D arrays of embeddings, got shapes {q.shape} and {c.shape}")
+    if q.shape[1] != c.shape[1]:
+        raise RuntimeError(
+            f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
+            f"right has {c.shape[1]} dimensional vectors"
+        )
+    sel = _check_subset(subset, c.shape[0]) if subset is not None else None
+    metric_id = _native.metric_from_str(metric)
+    if q.shape[0] == 0:
+        return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float64)
+    if c.shape[0] == 0:
+        raise RuntimeError("Empty series")
+    cc = np.ascontiguousarray(c)
+    # (cached only when the caller's own matrix is what is uploaded: a copy
+    # made here would never be found again)
+    offsets, idx, sc = _within_device(np.ascontiguousarray(q), cc, cc, cc, sel, threshold, metric_id,
+                                      numpy_ok=cc is corpus)
+    return offsets, idx, sc.astype(np.float64)
 
 
 def matmul(queries: np.ndarray, corpus: np.ndarray) -> np.ndarray:
@@ -186,6 +237,35 @@ if pl is not None:
                 )
             return self._expr.map_batches(
                 lambda s: _topk(s, corpus, k, metric, **extra),
+                is_elementwise=True,
+                return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def within(self, corpus: "pl.Series", threshold: float, metric: Metric = "cosine",
+                   subset: "pl.Series | None" = None, compute: Compute = "f32") -> "pl.Expr":
+            """Range search (an extension): every corpus row whose score is
+            >= ``threshold`` (cosine, dot) or <= ``threshold`` (euclidean), per
+            embedding: List[Struct{index: u32, score: f64}], best first, as
+            long as the row has hits.  Float32 columns only: a Float64 column
+            (cast it: ``pl.col(...).cast(pl.List(pl.Float32))``) and
+            compute="bf16" raise TypeError.  ``subset`` as in ``topk``."""
+            if isinstance(corpus, pl.Expr):
+                raise TypeError(
+                    "corpus must be a Polars Series, not an Expression. "
+                    "Use corpus['column_name'] or corpus.get_column('column_name')."
+                )
+            if isinstance(subset, pl.Expr):
+                raise TypeError(
+                    "subset must be a Polars Series, not an Expression. "
+                    "Use frame['column_name'] or frame.get_column('column_name')."
+                )
+            if _native.check_compute(compute) == "bf16":
+                from polars_matmul._polars_matmul import _within_f32_only
+
+                raise _within_f32_only('compute="bf16" has no range search')
+            extra = {} if subset is None else {"subset": subset}
+            return self._expr.map_batches(
+                lambda s: _within(s, corpus, threshold, metric, **extra),
                 is_elementwise=True,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
             )

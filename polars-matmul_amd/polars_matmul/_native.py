@@ -88,6 +88,7 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
+    "pmm_range_f32_corpus",
     "pmm_timing_enable",
     "pmm_timing_reset",
     "pmm_timing_read",
@@ -192,6 +193,8 @@ _SIGS = {
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
+    "pmm_range_f32_corpus": ([_vp, _vp, _i64, ctypes.c_float, _i32, _i64, _vp, _vp, _vp,
+                              ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_timing_enable": ([_i32], _i32),
     "pmm_timing_reset": ([], _i32),
     "pmm_timing_read": (
@@ -712,6 +715,47 @@ class DeviceCorpus:
         finally:
             self.release()
         return idx, sc
+
+    # The first call's capacity when ``range`` is given none: 64 hits per query
+    # row and at least 65536 entries.  A guess, not a measurement: a near-
+    # duplicate or "above 0.9 cosine" search returns a handful of rows per
+    # query; a call that finds more pays one more pass with the exact total.
+    RANGE_CAP_PER_ROW = 64
+    RANGE_CAP_MIN = 1 << 16
+
+    def range(self, q: np.ndarray, threshold: float, metric: int, cap=None):
+        """(offsets int64 (m + 1,), idx uint32 (total,), scores float32
+        (total,)) of pmm_range_f32_corpus: row i's hits -- every corpus row
+        whose score is >= ``threshold`` (cosine, dot) or <= ``threshold``
+        (euclidean) -- are entries [offsets[i], offsets[i + 1]), best first.
+        An f32 handle of one shard, plain or derived (a derived handle returns
+        its parent's row numbers).  ``cap``: the entries the first call has
+        room for (default: ``RANGE_CAP_PER_ROW`` per query row, at least
+        ``RANGE_CAP_MIN``); when the hits outnumber it the call is repeated
+        once with the exact total, so the result does not depend on it."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        m = q.shape[0]
+        if cap is None:
+            cap = max(self.RANGE_CAP_MIN, self.RANGE_CAP_PER_ROW * m)
+        cap = max(0, min(int(cap), m * self.n))
+        offsets = np.empty(m + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        self.acquire()
+        try:
+            while True:
+                idx = np.empty(cap, dtype=np.uint32)
+                sc = np.empty(cap, dtype=np.float32)
+                check(_lib.pmm_range_f32_corpus(self._h, ptr(q), m, float(threshold), metric, cap, ptr(offsets),
+                                                ptr(idx) if cap else None, ptr(sc) if cap else None,
+                                                ctypes.byref(total)))
+                if total.value <= cap:
+                    break
+                cap = total.value  # too small: once more, with room
+        finally:
+            self.release()
+        return offsets, idx[:total.value], sc[:total.value]
 
     def _derived(self, h: ctypes.c_void_p) -> "DeviceCorpus":
         """The DeviceCorpus of a handle the library derived from this one."""

@@ -246,9 +246,15 @@ def _persistent_key(original, arrow):
     return _arrow_key(arrow)
 
 
-def _corpus_key(original, rv, c: np.ndarray, compute: str):
-    """The cache key of this corpus, or None when it is not cacheable."""
+def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = False):
+    """The cache key of this corpus, or None when it is not cacheable.
+    numpy_ok (the numpy-level ``within``): a numpy matrix that is searched as
+    it is (C-contiguous, already of the compute dtype) is keyed by its address
+    and shape while the cache holds a reference to it; a caller that writes to
+    it in place gets stale results, as with Arrow buffers (above)."""
     key = _persistent_key(original, rv)
+    if key is None and numpy_ok and isinstance(original, np.ndarray) and c is original:
+        key = ("ndarray", c.ctypes.data, c.shape)
     if key is not None:
         # the compute dtype: an f32 column searched by f64 queries runs the
         # f64 branch (src/matmul.rs:427) on an f64 copy of the same buffers;
@@ -261,10 +267,10 @@ def _corpus_key(original, rv, c: np.ndarray, compute: str):
     return key
 
 
-def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32"):
+def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: bool = False):
     """An ACQUIRED DeviceCorpus for this corpus (the caller releases it), or
     None when the corpus is not cacheable."""
-    key = _corpus_key(original, rv, c, compute)
+    key = _corpus_key(original, rv, c, compute, numpy_ok)
     if key is None:
         return None
     dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
@@ -757,6 +763,100 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
     return out
 
 
+# ---------------------------------------------------------------------------
+# within: range search (an extension; no reference counterpart).  Every corpus
+# row whose score passes a threshold, per query row: ragged lists, best first.
+# It runs on f32 handles only (include/pmm.h pmm_range_f32_corpus) -- the
+# cached handle of the corpus, a derived one for ``subset=``, or a handle made
+# for the call when the corpus is not cacheable.  There is no host path.
+# ---------------------------------------------------------------------------
+def _within_f32_only(what: str) -> TypeError:
+    return TypeError(
+        f"range search runs on Float32 columns ({what}); cast the embeddings first, e.g. "
+        "pl.col('embedding').cast(pl.List(pl.Float32)) or array.astype(numpy.float32)"
+    )
+
+
+def _csr_arrow(offsets: np.ndarray, idx: np.ndarray, scores: np.ndarray) -> pa.Array:
+    """LargeList<Struct{index: u32, score: f64}> straight from CSR arrays: row i
+    is entries [offsets[i], offsets[i + 1]); the scores widen to f64 as ``_topk``'s."""
+    struct = pa.StructArray.from_arrays(
+        [pa.array(np.asarray(idx), type=pa.uint32()),
+         pa.array(np.asarray(scores).astype(np.float64, copy=False), type=pa.float64())],
+        fields=list(_TOPK_STRUCT),
+    )
+    return pa.LargeListArray.from_arrays(pa.array(np.asarray(offsets, dtype=np.int64), type=pa.int64()), struct)
+
+
+def _within_device(q, c, original, rv, sel, threshold: float, metric_id: int, numpy_ok: bool = False):
+    """(offsets, idx, scores f32) of the range search of q against c (both
+    f32), or against its selected rows, indices numbering c.  With a device
+    list the handle is sharded and the library's unsupported error surfaces."""
+    parent_key = _corpus_key(original, rv, c, "f32", numpy_ok)
+    parent = _cached_corpus(original, rv, c, "f32", numpy_ok) if parent_key is not None else None
+    own_parent = parent is None
+    if own_parent:
+        parent = _native.DeviceCorpus(c).acquire()
+    dc, transient = parent, False
+    try:
+        if sel is not None:
+            if own_parent:
+                dc, transient = parent.subset(sel.mask if sel.mask is not None else sel.ids).acquire(), True
+            else:
+                dc, transient = _cached_subset(parent, parent_key, sel, c, "f32")
+                if dc is None:
+                    raise _compute_error("the selected corpus rows do not fit in half of the free device memory")
+        try:
+            return dc.range(q, threshold, metric_id)
+        finally:
+            if dc is not parent:
+                dc.release()
+                if transient:
+                    dc.close()
+    finally:
+        parent.release()
+        if own_parent:
+            parent.close()
+
+
+def _within(left, right, threshold, metric, subset=None, compute="f32"):
+    """Range search (an extension): for every row of ``left`` the rows of
+    ``right`` whose score is >= ``threshold`` (cosine, dot) or <= ``threshold``
+    (euclidean), as List[Struct{index: UInt32, score: Float64}] named "within",
+    best first, ragged (a row without hits is an empty list).  The extraction,
+    null and dimension rules and error texts are ``_topk``'s; ``subset`` as
+    there.  Float32 columns only: Float64 columns and compute="bf16" raise
+    TypeError."""
+    if not isinstance(metric, str):
+        raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise TypeError(f"threshold must be a number, not {type(threshold).__name__}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    if _native.check_compute(compute) == "bf16":
+        raise _within_f32_only('compute="bf16" has no range search')
+    polars_out = _is_polars_series(left)
+    lv = _to_arrow(left)
+    rv = _to_arrow(right)
+    if not (_is_f32(lv) and _is_f32(rv)):
+        raise _within_f32_only("got a column of another type")
+    sel = _check_subset(subset, _nrows(rv)) if subset is not None else None
+    if _nrows(lv) == 0:
+        return _wrap(pa.array([], type=pa.large_list(_TOPK_STRUCT)), "within", polars_out)
+    try:
+        metric_id = _native.metric_from_str(metric)
+    except _native.PmmError as e:  # src/metrics.rs:25 text
+        raise _compute_error(str(e)) from None
+    q = _series_to_matrix(lv, np.float32)
+    c = _series_to_matrix(rv, np.float32)
+    if q.shape[1] != c.shape[1]:
+        raise _dim_mismatch(q.shape[1], c.shape[1])
+    _apply_devices_env()
+    offsets, idx, sc = _within_device(q, c, right, rv, sel, threshold, metric_id)
+    return _wrap(_csr_arrow(offsets, idx, sc), "within", polars_out)
+
+
 def _matmul(left, right):
     """src/lib.rs:15-30 -> src/matmul.rs:295-417 matmul_impl."""
     polars_out = _is_polars_series(left)
@@ -782,4 +882,4 @@ def _matmul(left, right):
     return res
 
 
-__all__ = ["_matmul", "_topk", "PanicException", "clear_corpus_cache", "set_devices", "get_devices"]
+__all__ = ["_matmul", "_topk", "_within", "PanicException", "clear_corpus_cache", "set_devices", "get_devices"]
