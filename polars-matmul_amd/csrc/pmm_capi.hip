@@ -1089,10 +1089,11 @@ int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const 
     }
   }
   HIP_TRY(run_fused_f32(a, p, index_base, out_idx, out_score, s));
-  // (not under a keep_gthr chunk merge: its loader re-keys the scores)
-  if (metric == kMetricCosine && !keep_gthr)
-    HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
-                                    out_score, s));
+  // (under a keep_gthr chunk merge too: the merge folds the zeros again and
+  // takes them back from these lists, launch_zero_sign_lists; an empty slot is
+  // skipped)
+  HIP_TRY(launch_zero_sign_f32(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, metric, index_base, out_idx,
+                               out_score, s));
   return PMM_OK;
 }
 
@@ -1134,6 +1135,9 @@ int topk_f32_materialised(const MatPlan &p, const float *q, int64_t ldq, int64_t
                                     (int)k, index_base, out_idx + r0 * k, out_score + r0 * k, s));
     }
   }
+  // (the row select's keys fold the zeros, and the stored scores ran over the padded dimension)
+  HIP_TRY(launch_zero_sign_f32(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, metric, index_base, out_idx,
+                               out_score, s));
   return PMM_OK;
 }
 
@@ -1233,8 +1237,8 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     Timed t("merge_topk", s);
     HIP_TRY(launch_merge(merge_cand_args(a, p, index_base, out_idx, out_score), 0, s));
   }
-  HIP_TRY(launch_zero_sign_cosine(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, index_base, out_idx,
-                                  out_score, s));
+  HIP_TRY(launch_zero_sign_f32(q, ldq, c, ldc, qn, cn, (int)m, n, (int)d, (int)k, metric, index_base, out_idx,
+                               out_score, s));
   // Rows the screen could not finish (unsafe, or a band that outgrew its
   // segment) and an unsafe corpus: one read-back, then the f32 kernel.
   HIP_TRY(launch_screen_collect(ovf, bad, (int)m, scal + 2, rows, s));
@@ -1659,6 +1663,10 @@ int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, 
   {
     Timed t("merge_chunks", s);
     CHUNK_TRY(launch_merge(ma, 1, s));
+    // (the chunks' zero scores carry their signs; the merge's keys fold them)
+    if (metric != kMetricEuclidean)
+      CHUNK_TRY(launch_zero_sign_lists(ma.in_idx, ma.in_score, kChunks, (int)k, k, 2 * m * k, (int)m, (int)k,
+                                       ma.out_idx, ma.out_score, s));
   }
   {
     Timed t("d2h", s);
@@ -1937,6 +1945,10 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
   {
     Timed t("merge_devices", rp.s);
     SH_TRY(launch_merge(ma, 1, rp.s));
+    // (the shards' zero scores carry their signs; the merge's keys fold them)
+    if (metric != kMetricEuclidean)
+      SH_TRY(launch_zero_sign_lists(ma.in_idx, ma.in_score, G, (int)k, k, 2 * m * k, (int)m, (int)k, ma.out_idx,
+                                    ma.out_score, rp.s));
   }
   SH_TRY(hipMemcpyAsync(out_idx, ma.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipMemcpyAsync(out_score, ma.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
@@ -2057,6 +2069,8 @@ int topk_f64_materialised(const double *dq, int64_t ldq, int64_t m, const double
                                     oi + r0 * k, os + r0 * k, s));
     }
   }
+  // the sign of zero scores (the f32 lists' pass, in f64)
+  HIP_TRY(launch_zero_sign_f64(dq, ldq, dc, ldc, qn, cn, (int)m, n, (int)d, (int)k, metric, index_base, oi, os, s));
   return PMM_OK;
 }
 
@@ -2152,6 +2166,8 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
       chunk = seen * g;
     }
   }
+  // the sign of zero scores (an overflowed call's lists are redone below, with theirs)
+  HIP_TRY(launch_zero_sign_f64(dq, ldq, dc, ldc, qn, cn, (int)m, n, (int)d, (int)k, metric, index_base, oi, os, s));
   if (flag_copy) {
     HIP_TRY(hipMemcpyAsync(flag_copy, flag, 4, hipMemcpyDeviceToDevice, s));
     return PMM_OK;
@@ -2197,7 +2213,7 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
   std::vector<int> slot(G);
   std::vector<int64_t> kg(G);
   std::vector<bool> fused(G);
-  std::vector<size_t> off_c(G), off_tmp(G), off_li(G), off_ls(G);
+  std::vector<size_t> off_c(G), off_tmp(G), off_tmps(G), off_li(G), off_ls(G);
   for (int g = 0; g < G; g++) {
     kg[g] = std::min<int64_t>(k, sh[g].rows);
     fused[g] = f64_use_fused(m, sh[g].rows, kg[g]);
@@ -2214,8 +2230,12 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
       p.ws_bytes = std::max(p.ws_bytes, f64_workspace_bytes(m, sh[g].rows, kg[g], fused[g]));
       off_c[g] = off;
       if (sh[g].host) off = al256(off + (size_t)sh[g].rows * dp * 8);
+      // (a short shard's compact list: index and score halves, each at an
+      // aligned offset of its own -- m * kg may be odd)
       off_tmp[g] = off;
-      if (kg[g] < k) off = al256(off + (size_t)m * kg[g] * 12);
+      if (kg[g] < k) off = al256(off + (size_t)m * kg[g] * 4);
+      off_tmps[g] = off;
+      if (kg[g] < k) off = al256(off + (size_t)m * kg[g] * 8);
       off_li[g] = off;
       off = al256(off + (size_t)m * k * 4);
       off_ls[g] = off;
@@ -2253,7 +2273,7 @@ int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metri
       // a shard shorter than k: its kg best into a compact list, then into
       // the [m][k] rows behind empty slots (idx 0xFFFFFFFF, score NaN)
       oi = (uint32_t *)(p.base + off_tmp[g]);
-      os = (double *)(oi + (size_t)m * kg[g]);
+      os = (double *)(p.base + off_tmps[g]);
       HIP_TRY(hipMemsetAsync(li, 0xFF, (size_t)m * k * 4, p.s));
       HIP_TRY(hipMemsetAsync(ls, 0xFF, (size_t)m * k * 8, p.s));  // (all-ones f64: a NaN)
     }
@@ -2939,10 +2959,9 @@ static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const ui
         HIP_TRY(launch_grouped_topk_f32(a, (int)units.size(), metric, s));
       }
       // the sign of zero scores, while the lists still number the partition's rows
-      if (metric == kMetricCosine)
-        HIP_TRY(launch_zero_sign_cosine((const float *)qg, dp, x.rows_as<float>(), dp, qn,
-                                        shard_norms<float>(h, x, metric), (int)mk, h->n, (int)d, (int)k, 0u, gi,
-                                        (float *)gs, s));
+      // (cosine and dot; the loop pairs' executors have restored theirs already)
+      HIP_TRY(launch_zero_sign_f32((const float *)qg, dp, x.rows_as<float>(), dp, qn, shard_norms<float>(h, x, metric),
+                                   (int)mk, h->n, (int)d, (int)k, metric, 0u, gi, (float *)gs, s));
     }
     {
       Timed t("grouped_scatter", s);
@@ -3334,6 +3353,11 @@ int pmm_matmul_f32(const float *q, int64_t m, const float *c, int64_t n, int64_t
     rc = gemm_store_f32(dq + r0 * dp, dp, rows, dc, dp, n, dp, kMetricDot, 0, nullptr, nullptr,
                         dout, n, (unsigned *)(b + off_cnt), g_dev[dev].cus, s);
     if (rc) return rc;
+    // (a padded dimension's +0 products turn a -0.0 sum into +0.0: the sign of
+    // a zero element from the chain over exactly d elements)
+    if (d < dp)
+      HIP_TRY(launch_zero_sign_f32(dq + r0 * dp, dp, dc, dp, nullptr, nullptr, (int)rows, n, (int)d, (int)n,
+                                   kMetricDot, 0u, nullptr, dout, s));
     HIP_TRY(hipMemcpyAsync(out + r0 * n, dout, (size_t)rows * n * 4, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -3370,6 +3394,9 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
       HIP_TRY(launch_gemm_f64_store(dq + r0 * dp, dp, dc, dp, nullptr, nullptr, (int)rows, (int)n,
                                     (int)dp, kMetricDot, 0, dout, n, s));
     }
+    if (d < dp)  // (as in pmm_matmul_f32)
+      HIP_TRY(launch_zero_sign_f64(dq + r0 * dp, dp, dc, dp, nullptr, nullptr, (int)rows, n, (int)d, (int)n,
+                                   kMetricDot, 0u, nullptr, dout, s));
     HIP_TRY(hipMemcpyAsync(out + r0 * n, dout, (size_t)rows * n * 8, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));

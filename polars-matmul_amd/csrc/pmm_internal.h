@@ -284,11 +284,20 @@ hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s);
 // rows[0 .. *count) = the rows with ovf[row] | bad[row] set; count[1] += the overflowed ones
 hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,
                                  hipStream_t s);
-// f32 cosine lists: +0.0 scores whose reference value is -0.0 get their sign
-// back (the selection keys fold the two zeros)
-hipError_t launch_zero_sign_cosine(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
-                                   const float *cn, int m, int64_t n, int d, int k, uint32_t index_base,
-                                   const uint32_t *out_idx, float *out_score, hipStream_t s);
+// cosine and dot lists: +0.0 scores whose reference value is -0.0 get their
+// sign back (the selection keys fold the two zeros); euclidean: nothing.  The
+// norms are read for cosine only.
+hipError_t launch_zero_sign_f32(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
+                                const float *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
+                                const uint32_t *out_idx, float *out_score, hipStream_t s);
+hipError_t launch_zero_sign_f64(const double *q, int64_t ldq, const double *c, int64_t ldc, const double *qn,
+                                const double *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
+                                const uint32_t *out_idx, double *out_score, hipStream_t s);
+// after a k-way merge of f32 lists (which folds the zeros again): a merged
+// +0.0 takes the zero its entry has in the input lists (strides as MergeArgs')
+hipError_t launch_zero_sign_lists(const uint32_t *in_idx, const float *in_score, int lists, int k_in,
+                                  int64_t row_stride, int64_t list_stride, int m, int k, const uint32_t *out_idx,
+                                  float *out_score, hipStream_t s);
 // ---- re-runs of listed rows (the screen's, the ff kernel's) ----
 // dst row i (units 16-byte units, dense) = src row rows[i] (row stride
 // ld_units 16-byte units); both 16-byte aligned

@@ -2613,38 +2613,98 @@ hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s) {
 // The selection keys fold -0 onto +0 (equal scores go to the lower index), so
 // a list's zero scores all come out as +0.0.  The reference keeps the sign: a
 // cosine of -0.0 where a negative dot is divided by an overflowed norm product
-// or underflows.  One thread per returned entry: a +0.0 score is recomputed
-// by the reference's arithmetic -- the fmaf chain over exactly d elements in
-// natural order, exact_score on the reference-order norms -- and rewritten
-// when that is a zero, with its sign.  Zero scores are rare; every other
-// entry costs its 4-byte read.
-__global__ __launch_bounds__(256) void zero_sign_kernel(const float *__restrict__ q, int64_t ldq,
-                                                        const float *__restrict__ c, int64_t ldc,
-                                                        const float *__restrict__ qn,
-                                                        const float *__restrict__ cn, int m, int64_t n, int d,
-                                                        int k, uint32_t index_base,
-                                                        const uint32_t *__restrict__ out_idx,
-                                                        float *__restrict__ out_score) {
+// or underflows, a dot product of -0.0 where the chain itself underflows from
+// below (f32 and f64 alike; a euclidean distance is never -0.0).  One thread
+// per returned entry: a +0.0 score is recomputed by the reference's arithmetic
+// -- the fma chain over exactly d elements in natural order (the padding's
+// +0 products would turn a -0.0 sum into +0.0), for cosine exact_score on the
+// reference-order norms -- and rewritten when that is a zero, with its sign.
+// Zero scores are rare; every other entry costs the read of its score.
+__device__ __forceinline__ bool is_pos_zero(float v) { return __float_as_uint(v) == 0u; }
+__device__ __forceinline__ bool is_pos_zero(double v) { return __double_as_longlong(v) == 0ll; }
+__device__ __forceinline__ float fma_chain_step(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double fma_chain_step(double a, double b, double c) { return __fma_rn(a, b, c); }
+__device__ __forceinline__ float cosine_of(float dot, float qv, float cv) {
+  return exact_score<kMetricCosine>(dot, qv, cv);
+}
+__device__ __forceinline__ double cosine_of(double dot, double qv, double cv) {
+  return exact_score_f64<kMetricCosine>(dot, qv, cv);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void zero_sign_kernel(const T *__restrict__ q, int64_t ldq,
+                                                        const T *__restrict__ c, int64_t ldc,
+                                                        const T *__restrict__ qn, const T *__restrict__ cn,
+                                                        int m, int64_t n, int d, int k, int metric,
+                                                        uint32_t index_base, const uint32_t *__restrict__ out_idx,
+                                                        T *__restrict__ out_score) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)m * k) return;
+  if (!is_pos_zero(out_score[t])) return;
+  // (no index array: a dense m x k score matrix, entry t is column t % k)
+  const uint32_t id = out_idx ? out_idx[t] : (uint32_t)(t % k) + index_base;
+  if (id == 0xFFFFFFFFu) return;
+  const int64_t col = (int64_t)(uint32_t)(id - index_base);
+  if (col >= n) return;
+  const int row = (int)(t / k);
+  const T *qr = q + (int64_t)row * ldq, *cr = c + col * ldc;
+  T acc = (T)0;
+  for (int i = 0; i < d; i++) acc = fma_chain_step(qr[i], cr[i], acc);
+  // (a dot product is its chain: no norms are read)
+  const T sc = metric == kMetricDot ? acc : cosine_of(acc, qn[row], cn[col]);
+  if (sc == (T)0) out_score[t] = sc;
+}
+// metric: cosine or dot (euclidean: nothing to do).  qn, cn: the rows' norms
+// for cosine, unread for dot.  out_idx holds index_base + the row of c; NULL:
+// out_score is the dense m x k matrix of Q C^T over c's first k rows (k = n).
+hipError_t launch_zero_sign_f32(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
+                                const float *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
+                                const uint32_t *out_idx, float *out_score, hipStream_t s) {
+  if (m <= 0 || k <= 0 || metric == kMetricEuclidean) return hipSuccess;
+  zero_sign_kernel<float><<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(
+      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score);
+  return hipGetLastError();
+}
+hipError_t launch_zero_sign_f64(const double *q, int64_t ldq, const double *c, int64_t ldc, const double *qn,
+                                const double *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
+                                const uint32_t *out_idx, double *out_score, hipStream_t s) {
+  if (m <= 0 || k <= 0 || metric == kMetricEuclidean) return hipSuccess;
+  zero_sign_kernel<double><<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(
+      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score);
+  return hipGetLastError();
+}
+
+// A k-way merge of f32 lists (merge_kernel's list loader) re-keys the lists'
+// scores, so the zeros a shard's or a chunk's sign pass restored leave it as
+// +0.0 again; the merging device may not hold the rows to recompute them from.
+// One thread per merged entry: a +0.0 score looks its index up in the row's
+// input lists (distinct across the lists) and takes that entry's zero.
+__global__ __launch_bounds__(256) void zero_sign_lists_kernel(const uint32_t *__restrict__ in_idx,
+                                                              const float *__restrict__ in_score, int lists,
+                                                              int k_in, int64_t row_stride, int64_t list_stride,
+                                                              int m, int k, const uint32_t *__restrict__ out_idx,
+                                                              float *__restrict__ out_score) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)m * k) return;
   if (__float_as_uint(out_score[t]) != 0u) return;
   const uint32_t id = out_idx[t];
   if (id == 0xFFFFFFFFu) return;
-  const int64_t col = (int64_t)(uint32_t)(id - index_base);
-  if (col >= n) return;
-  const int row = (int)(t / k);
-  const float *qr = q + (int64_t)row * ldq, *cr = c + col * ldc;
-  float acc = 0.0f;
-  for (int i = 0; i < d; i++) acc = fmaf(qr[i], cr[i], acc);
-  const float sc = exact_score<kMetricCosine>(acc, qn[row], cn[col]);
-  if (sc == 0.0f) out_score[t] = sc;
+  const int64_t row = t / k;
+  for (int g = 0; g < lists; g++) {
+    const int64_t base = (int64_t)g * list_stride + row * row_stride;
+    for (int j = 0; j < k_in; j++) {
+      if (in_idx[base + j] != id) continue;
+      const float sc = in_score[base + j];
+      if (sc == 0.0f) out_score[t] = sc;
+      return;
+    }
+  }
 }
-hipError_t launch_zero_sign_cosine(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
-                                   const float *cn, int m, int64_t n, int d, int k, uint32_t index_base,
-                                   const uint32_t *out_idx, float *out_score, hipStream_t s) {
-  if (m <= 0 || k <= 0) return hipSuccess;
-  zero_sign_kernel<<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(q, ldq, c, ldc, qn, cn, m, n, d, k,
-                                                                           index_base, out_idx, out_score);
+hipError_t launch_zero_sign_lists(const uint32_t *in_idx, const float *in_score, int lists, int k_in,
+                                  int64_t row_stride, int64_t list_stride, int m, int k, const uint32_t *out_idx,
+                                  float *out_score, hipStream_t s) {
+  if (m <= 0 || k <= 0 || lists <= 0) return hipSuccess;
+  zero_sign_lists_kernel<<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(
+      in_idx, in_score, lists, k_in, row_stride, list_stride, m, k, out_idx, out_score);
   return hipGetLastError();
 }
 

@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void range_sort_block_kernel(u64 *__restrict__
 }
 
 // One thread per list entry.  The score is the key's (a zero euclidean
-// distance leaves as +0.0); the keys fold -0 onto +0, so a +0.0 cosine is
-// recomputed by the reference's arithmetic and takes that zero's sign, as
+// distance leaves as +0.0); the keys fold -0 onto +0, so a +0.0 cosine or dot
+// product is recomputed by the reference's arithmetic and takes that zero's sign, as
 // zero_sign_kernel does for the top-k lists (its row found by bisection of
 // the offsets: zero scores are rare).  The index goes through the index map.
 __global__ __launch_bounds__(256) void range_decode_kernel(RangeDecodeArgs a) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void range_decode_kernel(RangeDecodeArgs a) {
     const uint32_t col = ~(uint32_t)key;
     const float v = dekey32((uint32_t)(key >> 32));
     float sc = a.metric == kMetricEuclidean ? 0.0f - v : v;
-    if (a.metric == kMetricCosine && __float_as_uint(sc) == 0u) {
+    if (a.metric != kMetricEuclidean && __float_as_uint(sc) == 0u) {
       int lo = 0, hi = a.m;  // offsets[lo] <= t < offsets[hi]
       while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -94,7 +94,8 @@ __global__ __launch_bounds__(256) void range_decode_kernel(RangeDecodeArgs a) {
       const float *qr = a.q + (int64_t)lo * a.ldq, *cr = a.c + (int64_t)col * a.ldc;
       float acc = 0.0f;
       for (int i = 0; i < a.d; i++) acc = fmaf(qr[i], cr[i], acc);
-      const float ex = exact_score<kMetricCosine>(acc, a.qn[lo], a.cn[col]);
+      // (a dot product is its chain: no norms are read)
+      const float ex = a.metric == kMetricDot ? acc : exact_score<kMetricCosine>(acc, a.qn[lo], a.cn[col]);
       if (ex == 0.0f) sc = ex;
     }
     a.out_idx[t] = a.map ? a.map[col] : col;
