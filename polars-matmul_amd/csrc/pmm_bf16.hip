@@ -176,8 +176,9 @@ hipError_t launch_round_norms_bf16(const float *src, int64_t rows, int64_t d, in
 // Rows prepared for the f32 cosine screen in one read of the
 // f32 rows: the bf16 image, the EXACT cosine norm and pre-filter factor of the
 // unrounded row (norms_kernel<float, float>'s bits), the rounding residual
-// bound and the unsafe flag -- what norms_kernel + screen_round_kernel give in
-// two launches and 10 bytes of HBM traffic per element, in one and 6.
+// bound and the unsafe flag -- what norms_kernel and a rounding pass over the
+// rows gave in two launches and 10 bytes of HBM traffic per element, in one
+// and 6.  Handles and the device entry both prepare their operands with it.
 //
 // round_norms_bf16_kernel's shape: a band of kRnRows rows, kRnCols columns at
 // a time.  Every thread rounds groups of 8 columns (16-byte loads where the
@@ -189,7 +190,7 @@ hipError_t launch_round_norms_bf16(const float *src, int64_t rows, int64_t d, in
 // ---------------------------------------------------------------------------
 constexpr int kSpLd = kRnCols + 8;  // LDS row stride (f32): the 8 rows of a wave land 8 banks apart
 
-// round to nearest even, NaN stays NaN (screen_round_kernel's statement)
+// round to nearest even, NaN stays NaN
 __device__ __forceinline__ uint32_t screen_bf16_bits(float x) {
   const uint32_t u = __float_as_uint(x);
   return (x != x) ? ((u >> 16) | 0x40u) : ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);

@@ -1173,14 +1173,13 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     memcpy(&bits, &img->max_rel, 4);
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)scal, (int)bits, 1, s));
   } else {
-    // the exact norms and factors (norms_rows, as the unscreened path's), then
-    // the bf16 images with the rounding residuals and the unsafe flags
+    // per operand one read: the exact norms and factors (the unscreened path's
+    // bits), the bf16 image, the rounding residuals and the unsafe flags
     Timed t("norms_f32/round", s);
     float *wcn = (float *)(w + p.off_cn), *crel = (float *)(w + sp.off_crel);
-    HIP_TRY(launch_norms_pair_f32(q, m, ldq, qn, c, n, ldc, wcn, wcn + n, d, 0, s));
-    HIP_TRY(launch_screen_round(q, m, d, ldq, qn, qb, sp.dpb, rel, bad, nullptr, s));
-    HIP_TRY(launch_screen_round(c, n, d, ldc, wcn, (uint16_t *)(w + sp.off_cb), sp.dpb, crel,
-                                (unsigned *)(crel + n), scal, s));
+    HIP_TRY(launch_screen_prepare(q, m, d, ldq, qb, sp.dpb, qn, nullptr, rel, bad, nullptr, s));
+    HIP_TRY(launch_screen_prepare(c, n, d, ldc, (uint16_t *)(w + sp.off_cb), sp.dpb, wcn, wcn + n, crel,
+                                  (unsigned *)(crel + n), scal, s));
   }
   GemmF32Args a = fused_args(m, n, sp.dpb, k, metric, p, w);
   a.qb = qb;
@@ -1227,6 +1226,7 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     fa.dp = (int)sp.dp;
     fa.S = p.S;
     fa.capg = p.capg;
+    fa.k = (int)k;
     fa.cand = a.cand;
     fa.cnt = a.cnt;
     fa.gthr = a.gthr;
@@ -1255,9 +1255,9 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     memcpy(&rc, &h[0], 4);
     fprintf(stderr,
             "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
-            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u m=%lld handle=%d\n",
-            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], (long long)m,
-            img ? 1 : 0);
+            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u kept=%u m=%lld handle=%d\n",
+            p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], h[6],
+            (long long)m, img ? 1 : 0);
   }
   // The f32 kernel's runs never screen (k <= kScreenMaxK: always its fused
   // route); plan_screen reserved their workspace at off_f32.

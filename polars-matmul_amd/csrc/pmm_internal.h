@@ -247,20 +247,15 @@ hipError_t launch_norms_bf16(const uint16_t *a, int64_t rows, int64_t d, int64_t
                              float *out, float *inv, hipStream_t s);
 size_t merge_lds_bytes_per_wave(int P);
 // ---- screened f32 top-k (cosine): bf16 screen + exact f32 re-score ----
-// One pass over f32 rows: the bf16 image (RNE, row stride ldd, columns d..ldd-1
-// zero), per row an upper bound of ||x - bf16(x)|| / ||x|| in rel[] and an
-// "unsafe" flag in bad[] (non-finite or out-of-window element, or norm[row]
-// at or below the reference's 1e-6 rule).  With `scal`: scal[0] takes the
-// maximum rel over the safe rows (float bits), scal[1] is set when any row is
-// unsafe (the corpus form); both zeroed by the caller.
-hipError_t launch_screen_round(const float *src, int64_t rows, int64_t d, int64_t lds, const float *norm,
-                               uint16_t *dst, int64_t ldd, float *rel, unsigned *bad, unsigned *scal,
-                               hipStream_t s);
-// launch_screen_round's image, rel[], bad[] and scal AND the rows' exact cosine
-// norms and pre-filter factors (launch_norms_f32's bits, squared = 0) in one
-// read of the rows (pmm_bf16.hip).  A null array is skipped.  lds >= d (any
-// alignment; 16-byte loads when src and lds allow), ldd >= d a multiple of 8,
-// dst 16-byte aligned.
+// One pass over f32 rows (pmm_bf16.hip): the bf16 image (RNE, row stride ldd,
+// columns d..ldd-1 zero), per row an upper bound of ||x - bf16(x)|| / ||x|| in
+// rel[] and an "unsafe" flag in bad[] (non-finite or out-of-window element, or
+// a norm at or below the reference's 1e-6 rule), AND the rows' exact cosine
+// norms and pre-filter factors (launch_norms_f32's bits, squared = 0).  With
+// `scal`: scal[0] takes the maximum rel over the safe rows (float bits),
+// scal[1] is set when any row is unsafe (the corpus form); both zeroed by the
+// caller.  A null array is skipped.  lds >= d (any alignment; 16-byte loads
+// when src and lds allow), ldd >= d a multiple of 8, dst 16-byte aligned.
 hipError_t launch_screen_prepare(const float *src, int64_t rows, int64_t d, int64_t lds, uint16_t *dst, int64_t ldd,
                                  float *norm, float *inv_norm, float *rel, unsigned *bad, unsigned *scal,
                                  hipStream_t s);
@@ -272,14 +267,18 @@ struct ScreenFinishArgs {
   const float *q, *c;
   int64_t ldq, ldc;
   const float *qn, *cn, *eps;
-  int M, N, dp, S, capg;
+  int M, N, dp, S, capg, k;
   unsigned long long *cand;
   const unsigned *cnt;
   const unsigned long long *gthr;
-  unsigned *stat;  // optional: [0] += candidates re-scored, [1] = max per row
+  // optional: [0] += candidates re-scored (rows gathered), [1] = max per row,
+  // [2] += entries at or above the published bound - eps (one pass's gathers)
+  unsigned *stat;
 };
 // every kept candidate's approximate key replaced by its exact composite (the
-// f32 path's fmaf chain and epilogue); entries below the final bound dropped
+// f32 path's fmaf chain and epilogue); entries below the bound dropped -- the
+// published one lowered by eps, raised to (the exact k-th of the k best
+// approximate entries) - eps once those are scored
 hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s);
 // rows[0 .. *count) = the rows with ovf[row] | bad[row] set; count[1] += the overflowed ones
 hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,

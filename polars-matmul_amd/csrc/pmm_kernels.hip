@@ -2453,73 +2453,6 @@ hipError_t launch_rowsort_global(const void *scores, int64_t lds, int rows, int 
 // Screened f32 top-k (cosine), the passes around the bf16 screen kernel
 // (pmm_bf16_ws_kernel.h, SCREEN; the bound is screen_eps in pmm_device.h).
 // ===========================================================================
-// (the element window of a "safe" row: kScreenMinAbs / kScreenMaxAbs, pmm_device.h)
-// One wave per row, four elements per lane and step (16-byte loads, 8-byte
-// stores: rows 16-byte aligned, strides multiples of 4).
-__global__ __launch_bounds__(256) void screen_round_kernel(const float *__restrict__ src, int64_t rows, int64_t d,
-                                                           int64_t lds, const float *__restrict__ norm,
-                                                           uint16_t *__restrict__ dst, int64_t ldd,
-                                                           float *__restrict__ rel, unsigned *__restrict__ bad,
-                                                           unsigned *scal) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;  // whole wave
-  const float *p = src + row * lds;
-  uint16_t *o = dst + row * ldd;
-  const int64_t d4 = (d + 3) & ~(int64_t)3;  // (<= lds: readable)
-  float n2 = 0.0f, r2 = 0.0f;
-  bool ok = true;
-  for (int64_t i = 4 * lane; i < ldd; i += 256) {
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (i < d4) v = *(const f32x4 *)(p + i);
-    uint32_t b[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const float x = (i + j < d) ? v[j] : 0.0f;
-      const uint32_t u = __float_as_uint(x);
-      // round to nearest even; NaN stays NaN
-      b[j] = (x != x) ? ((u >> 16) | 0x40u) : ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-      const float r = x - __uint_as_float(b[j] << 16);  // (exact for a safe element)
-      n2 = fmaf(x, x, n2);
-      r2 = fmaf(r, r, r2);
-      const float ax = fabsf(x);
-      ok = ok && (ax == 0.0f || (ax >= kScreenMinAbs && ax <= kScreenMaxAbs));
-    }
-    *(uint2 *)(o + i) = make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    n2 += __shfl_xor(n2, off);
-    r2 += __shfl_xor(r2, off);
-  }
-  const bool all_ok = __ballot(!ok) == 0ull;
-  if (lane == 0) {
-    const bool unsafe = !all_ok || !(norm[row] > 1e-6f) || !(n2 > 0.0f);
-    // (the sums' and the square root's rounding: far inside the 2^-9 inflation;
-    // a safe row's true ratio is below 2^-8, bf16's half ulp)
-    const float rl = unsafe ? 0x1p-8f : fminf(__builtin_sqrtf(r2 / n2) * (1.0f + 0x1p-9f), 0x1p-8f);
-    rel[row] = rl;
-    bad[row] = unsafe ? 1u : 0u;
-    if (scal) {
-      if (unsafe) {
-        atomicOr(scal + 1, 1u);
-      } else if (__float_as_uint(rl) > __hip_atomic_load(scal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        atomicMax(scal, __float_as_uint(rl));  // (non-negative floats order as their bits)
-      }
-    }
-  }
-}
-hipError_t launch_screen_round(const float *src, int64_t rows, int64_t d, int64_t lds, const float *norm,
-                               uint16_t *dst, int64_t ldd, float *rel, unsigned *bad, unsigned *scal,
-                               hipStream_t s) {
-  if (rows <= 0) return hipSuccess;
-  if (lds % 4 != 0 || ldd % 4 != 0 || ldd < d || lds < ((d + 3) & ~(int64_t)3) || ((uintptr_t)src & 15) ||
-      ((uintptr_t)dst & 7))
-    return hipErrorInvalidValue;
-  screen_round_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(src, rows, d, lds, norm, dst, ldd, rel, bad, scal);
-  return hipGetLastError();
-}
-
 __global__ __launch_bounds__(256) void screen_prep_kernel(const float *__restrict__ rel,
                                                           const unsigned *__restrict__ scal, int m, int dp,
                                                           float *__restrict__ eps, u64 *gthr, int seeded) {
@@ -2538,75 +2471,238 @@ hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int
 }
 
 // Exact finish, first half: one workgroup per query row (staged in LDS, read
-// as broadcasts), one thread per kept candidate.  An entry whose approximate
-// key is below (the row's final bound) - eps cannot be in the top-k and is
-// emptied; every other entry's corpus row is gathered (16-byte loads, 128
-// bytes in flight per lane) and scored by the f32 path's arithmetic -- the
-// fmaf chain over the padded K in natural order from 0, exact_score on the
-// reference-order norms: seed_lds_block's, bit for bit the fused kernel's --
-// and its composite replaces the approximate one in place.  merge_kernel then
-// selects and orders the exact top-k as for the unscreened kernels.
-__global__ __launch_bounds__(256) void screen_rescore_kernel(ScreenFinishArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *qs = (float *)smem;
-  const int tid = threadIdx.x;
-  const int row = (int)blockIdx.x;
-  const float *qr = a.q + (int64_t)row * a.ldq;
-  for (int i = 4 * tid; i < a.dp; i += 1024) *(f32x4 *)(qs + i) = *(const f32x4 *)(qr + i);
-  __syncthreads();
-  const float qv = a.qn[row];
-  const u64 T = screen_lower(a.gthr[row], a.eps[row]);
-  const u64 T1 = T ? T : 1ull;
-  int mine = 0;
-  for (int s = 0; s < a.S; s++) {
-    const int n_s = min((int)a.cnt[(int64_t)row * a.S + s], a.capg);
-    u64 *seg = a.cand + ((int64_t)row * a.S + s) * a.capg;
-    for (int i = tid; i < n_s; i += 256) {
-      const u64 x = seg[i];
-      const uint32_t col = ~(uint32_t)x;
-      if (x < T1 || col >= (uint32_t)a.N) {
-        seg[i] = 0ull;
-        continue;
-      }
-      const float *cr = a.c + (int64_t)col * a.ldc;
-      mine++;
-      float acc = 0.0f;
-      for (int k0 = 0; k0 < a.dp; k0 += 32) {
-        f32x4 v[8];
+// as broadcasts).  A candidate's corpus row is gathered by one thread (16-byte
+// loads, 128 bytes in flight per lane) and scored by the f32 path's arithmetic
+// -- the fmaf chain over the padded K in natural order from 0, exact_score on
+// the reference-order norms: seed_lds_block's, bit for bit the fused kernel's
+// -- and its composite replaces the approximate one in place.  merge_kernel
+// then selects and orders the exact top-k as for the unscreened kernels.
+//
+// The kernel's time is the rows it gathers (whole rows from a buffer far
+// larger than the caches), so it gathers in two phases.  With T1 = (the row's
+// published bound) - eps, the entries with approximate composite x >= T1 and a
+// column below N are the row's n_r live entries (what a single pass gathers).
+//   0. select: P, the k-th largest live approximate composite, 8 bits per
+//      round from the top over a workgroup-wide histogram (at most 8 rounds,
+//      for distinct score keys at most 4), so exactly k live entries have
+//      x >= P.  n_r <= k: no P, phase 2 alone with T2 = T1, the single pass.
+//   1. the k entries x >= P are scored exactly; e_k is the least of their
+//      exact score keys, i.e. the k-th largest exact score known so far.
+//   2. T2 = max(T1, e_k - eps); every other entry with x < T2 is emptied,
+//      the rest are scored exactly.
+// Why nothing of the top-k is emptied: phase 1's k columns have exact scores
+// >= e_k, so the row's final exact k-th is >= e_k, a column of the final top-k
+// has an exact score >= e_k and, by the screen's bound, an approximate score
+// >= e_k - eps.  An emptied entry has an approximate score < e_k - eps, so an
+// exact score < e_k: strictly below k other candidates, whatever their
+// indices.  screen_lower carries the margin for its own rounding, and every
+// surviving entry gets the composite a single pass gives it, so the merged
+// lists are the same bits.
+//
+// Each phase first lists its entries in LDS and then scores the list with
+// consecutive threads, so the gathers run on full waves though the entries are
+// scattered over the segments.  A list that outgrows kRescoreList is scored in
+// several rounds (a crowded band; at most total / kRescoreList + 1 of them).
+// Until the end a scored entry is told from an approximate one by its index
+// part, written as col instead of ~col: columns are below N < 2^31, so bit 31
+// of an approximate entry's low word is set and a scored one's is clear; a
+// last walk over the entries restores ~col.  (A scored entry is never 0, the empty
+// mark: a kept row's exact score is not NaN.)  Rows whose result is discarded
+// (overflowed, unsafe, padding) take the same path: every index stays inside
+// the counted part of a segment and every loop has a bound fixed beforehand.
+constexpr int kRescoreList = 512;  // >= k (launch_screen_rescore checks)
+
+// f(p, *p) for every counted entry of the row this thread owns (entry i of a
+// segment: thread i mod blockDim).  segs: the row's non-empty segments in LDS,
+// (segment << 10) | count; the entries are loaded four at a time.  The walks
+// run while other workgroups' gathers saturate the memory system, so every
+// dependent load costs microseconds: per walk one or two here, not one per
+// segment and entry.
+template <typename F>
+__device__ __forceinline__ void rescore_each_entry(const ScreenFinishArgs &a, u64 *base, const unsigned *segs,
+                                                   int nseg, F &&f) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int t = 0; t < nseg; t++) {
+    const unsigned e = segs[t];
+    const int n = (int)(e & 1023u);
+    u64 *seg = base + (int64_t)(e >> 10) * a.capg;
+    for (int i0 = tid; i0 < n; i0 += 4 * nt) {
+      u64 x[4];
 #pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = *(const f32x4 *)(cr + k0 + 4 * j);
+      for (int j = 0; j < 4; j++) x[j] = i0 + j * nt < n ? seg[i0 + j * nt] : 0ull;
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const f32x4 q4 = *(const f32x4 *)(qs + k0 + 4 * j);
-          acc = fmaf(q4[0], v[j][0], acc);
-          acc = fmaf(q4[1], v[j][1], acc);
-          acc = fmaf(q4[2], v[j][2], acc);
-          acc = fmaf(q4[3], v[j][3], acc);
-        }
-      }
-      const float sc = exact_score<kMetricCosine>(acc, qv, a.cn[col]);
-      seg[i] = ((u64)okey32(sc) << 32) | (u64)(~col);
+      for (int j = 0; j < 4; j++)
+        if (i0 + j * nt < n) f(seg + i0 + j * nt, x[j]);
     }
   }
-  if (a.stat) {  // (diagnostics: PMM_SCREEN_DEBUG)
-    __shared__ unsigned kept;
-    __syncthreads();  // (every thread is past its reads of qs)
-    if (tid == 0) kept = 0u;
+}
+
+// (8 waves per SIMD, 64 registers: the gathers need the waves in flight)
+__global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ __attribute__((aligned(16))) unsigned hist[256];
+  __shared__ unsigned list[kRescoreList];
+  __shared__ unsigned res[4], ln, emin;
+  float *qs = (float *)smem;
+  unsigned *segs = (unsigned *)(qs + a.dp);  // S words
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int row = (int)blockIdx.x;
+  const float *qr = a.q + (int64_t)row * a.ldq;
+  for (int i = 4 * tid; i < a.dp; i += 4 * nt) *(f32x4 *)(qs + i) = *(const f32x4 *)(qr + i);
+  for (int i = tid; i < 256; i += nt) hist[i] = 0u;
+  if (tid == 0) emin = ~0u, ln = 0u;
+  __syncthreads();
+  for (int s = tid; s < a.S; s += nt) {
+    const unsigned n = min(a.cnt[(int64_t)row * a.S + s], (unsigned)a.capg);
+    if (n) segs[atomicAdd(&ln, 1u)] = ((unsigned)s << 10) | n;
+  }
+  __syncthreads();
+  const int nseg = (int)ln;
+  const float qv = a.qn[row];
+  const float eps = a.eps[row];
+  const u64 T = screen_lower(a.gthr[row], eps);
+  const u64 T1 = T ? T : 1ull;
+  u64 *base = a.cand + (int64_t)row * a.S * a.capg;
+
+  auto live = [&](u64 x) __attribute__((always_inline)) -> bool {
+    return x >= T1 && ~(uint32_t)x < (uint32_t)a.N;
+  };
+  // Phase 0.  P, the k-th largest live composite, built from the top byte
+  // down: per round a 256-bin histogram of the live entries that share the
+  // prefix so far, then the first wave finds the bin that holds the rank
+  // (bins 4 lane .. 4 lane + 3 per lane, a suffix sum across lanes).  `need`
+  // is the rank left inside the prefix; once the chosen bin holds exactly
+  // `need` entries the prefix (low bits zero) already has exactly k entries at
+  // or above it, and the rounds end -- for distinct score keys within the
+  // first four.  Fewer than k live entries: no bin is chosen (n_r tells).
+  u64 P = 0ull;
+  unsigned n_r = 0u, need = (unsigned)a.k;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    rescore_each_entry(a, base, segs, nseg, [&](u64 *, u64 x) __attribute__((always_inline)) {
+      if (live(x) && (shift == 56 || ((x ^ P) >> (shift + 8)) == 0ull))
+        atomicAdd(&hist[(unsigned)(x >> shift) & 255u], 1u);
+    });
     __syncthreads();
-    atomicAdd(&kept, (unsigned)mine);
+    if (tid < 64) {
+      const uint4 h = ((const uint4 *)hist)[tid];
+      ((uint4 *)hist)[tid] = make_uint4(0u, 0u, 0u, 0u);
+      const unsigned own = h.x + h.y + h.z + h.w;
+      unsigned suf = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_down(suf, o);
+        if (tid + o < 64) suf += t;
+      }
+      if (tid == 0) {
+        res[0] = res[1] = res[2] = 0u;
+        if (shift == 56) res[3] = suf;
+      }
+      unsigned above = suf - own;  // entries in the bins of higher lanes
+      if (above < need && suf >= need) {
+        unsigned b = 3u, in_bin = h.w;
+        if (above + in_bin < need) above += in_bin, in_bin = h.z, b = 2u;
+        if (above + in_bin < need) above += in_bin, in_bin = h.y, b = 1u;
+        if (above + in_bin < need) above += in_bin, in_bin = h.x, b = 0u;
+        res[0] = 4u * (unsigned)tid + b;
+        res[1] = need - above;
+        res[2] = in_bin;
+      }
+    }
+    __syncthreads();
+    P |= (u64)res[0] << shift;
+    need = res[1];
+    if (shift == 56) n_r = res[3];
+    if (res[2] == need) break;  // (the same for every thread)
+  }
+  // Phases 1 (x >= P) and 2 (x >= T2; it also empties the others): list the
+  // approximate entries at or above the phase's bound, then score the list.
+  const int max_rounds = (int)(((int64_t)a.S * a.capg + kRescoreList - 1) / kRescoreList) + 1;
+  unsigned done = 0u;
+  for (int ph = n_r > (unsigned)a.k ? 1 : 2; ph <= 2; ph++) {
+    const bool last = ph == 2;
+    u64 thr = P;
+    if (last) {
+      __syncthreads();  // (phase 1's e_k is complete; none ran: ~0, which lowers to 0)
+      const u64 E = screen_lower((u64)emin << 32, eps);
+      thr = E > T1 ? E : T1;
+    }
+    for (int r = 0; r < max_rounds; r++) {
+      __syncthreads();  // (the list and its count are free again)
+      if (tid == 0) ln = 0u;
+      __syncthreads();
+      rescore_each_entry(a, base, segs, nseg, [&](u64 *p, u64 x) __attribute__((always_inline)) {
+        if (x == 0ull) return;
+        const uint32_t lw = (uint32_t)x;
+        if (!(lw & 0x80000000u)) return;  // scored in an earlier round
+        if (x < thr || !live(x)) {
+          if (last) *p = 0ull;
+          return;
+        }
+        const unsigned pos = atomicAdd(&ln, 1u);
+        if (pos < (unsigned)kRescoreList) list[pos] = (unsigned)(p - base);
+      });
+      __syncthreads();
+      const unsigned n = ln;
+      const bool more = n > (unsigned)kRescoreList;
+      const int cnt = more ? kRescoreList : (int)n;
+      for (int t = tid; t < cnt; t += nt) {
+        u64 *p = base + list[t];
+        const uint32_t col = ~(uint32_t)*p;
+        const float *cr = a.c + (int64_t)col * a.ldc;
+        float acc = 0.0f;
+        for (int k0 = 0; k0 < a.dp; k0 += 32) {
+          f32x4 v[8];
+#pragma unroll
+          for (int j = 0; j < 8; j++) v[j] = *(const f32x4 *)(cr + k0 + 4 * j);
+#pragma unroll
+          for (int j = 0; j < 8; j++) {
+            const f32x4 q4 = *(const f32x4 *)(qs + k0 + 4 * j);
+            acc = fmaf(q4[0], v[j][0], acc);
+            acc = fmaf(q4[1], v[j][1], acc);
+            acc = fmaf(q4[2], v[j][2], acc);
+            acc = fmaf(q4[3], v[j][3], acc);
+          }
+        }
+        const uint32_t key = okey32(exact_score<kMetricCosine>(acc, qv, a.cn[col]));
+        if (!last) atomicMin(&emin, key);
+        *p = ((u64)key << 32) | (u64)col;
+        done++;
+      }
+      if (!more) break;
+    }
+  }
+  __syncthreads();
+  rescore_each_entry(a, base, segs, nseg, [&](u64 *p, u64 x) __attribute__((always_inline)) {
+    if (x != 0ull && !((uint32_t)x & 0x80000000u)) *p = (x & 0xFFFFFFFF00000000ull) | (u64)(~(uint32_t)x);
+  });
+  if (a.stat) {  // (diagnostics: PMM_SCREEN_DEBUG)
+    __syncthreads();
+    if (tid == 0) ln = 0u;
+    __syncthreads();
+    atomicAdd(&ln, done);
     __syncthreads();
     if (tid == 0) {
-      atomicAdd(a.stat, kept);
-      atomicMax(a.stat + 1, kept);
+      atomicAdd(a.stat, ln);
+      atomicMax(a.stat + 1, ln);
+      atomicAdd(a.stat + 2, n_r);
     }
   }
 }
 hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;
   if (a.dp % 32 != 0 || a.dp > 4096 || a.ldq % 4 != 0 || a.ldc % 4 != 0 || a.ldq < a.dp || a.ldc < a.dp ||
-      (((uintptr_t)a.q | (uintptr_t)a.c) & 15))
+      (((uintptr_t)a.q | (uintptr_t)a.c) & 15) || a.k < 1 || a.k > kRescoreList || a.capg > 1023 ||
+      ((int64_t)a.dp + a.S) * 4 > 64 * 1024)  // (the row and its segment list in LDS)
     return hipErrorInvalidValue;
-  screen_rescore_kernel<<<(unsigned)a.M, 256, (size_t)a.dp * 4, s>>>(a);
+  // PMM_RESCORE_BLOCK (experiment knob, read per call): threads per row.  One
+  // wave measured best at c3 (re-score 19.5 ms against 21.4 at 128 and 21.5 at
+  // 256, profiles/rescore_band/README.md): more rows in flight per CU.
+  int nt = 64;
+  if (const char *e = getenv("PMM_RESCORE_BLOCK")) {
+    const int v = atoi(e);
+    if (v == 64 || v == 128 || v == 256) nt = v;
+  }
+  screen_rescore_kernel<<<(unsigned)a.M, nt, ((size_t)a.dp + a.S) * 4, s>>>(a);
   return hipGetLastError();
 }
 
