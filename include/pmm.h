@@ -338,6 +338,7 @@ typedef struct pmm_corpus pmm_corpus;
 #define PMM_DTYPE_F32 0
 #define PMM_DTYPE_F64 1
 #define PMM_DTYPE_BF16 2
+#define PMM_DTYPE_I8 3
 
 int pmm_corpus_create_f32(const float *c, int64_t n, int64_t d, pmm_corpus **out);
 /* An f64 corpus: rows kept in f64 (stride roundup(d, 16), zero-padded) with
@@ -353,7 +354,16 @@ int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **ou
  * rows.  Sharded over a device list like an f32 corpus; the f32 creator's
  * argument errors and texts. */
 int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **out);
-/* PMM_DTYPE_F32, PMM_DTYPE_F64 or PMM_DTYPE_BF16. */
+/* An int8 corpus: rows of signed bytes kept as they are (stride roundup(d, 64)
+ * bytes, zero-padded) with each row's integer sum of squares (u32) and the f32
+ * factor 1 / sqrt(sum) (0 for a zero row): n * roundup(d, 64) + 8 n bytes, an
+ * eighth of the f64 handle the same column took before.  d < 65536, else
+ * PMM_ERR_UNSUPPORTED.  Never sharded: with pmm_set_devices in effect the
+ * handle lives on the list's first device.  pmm_corpus_subset_*,
+ * pmm_corpus_partition and pmm_range_f32_corpus refuse it with
+ * PMM_ERR_UNSUPPORTED. */
+int pmm_corpus_create_i8(const int8_t *c, int64_t n, int64_t d, pmm_corpus **out);
+/* PMM_DTYPE_F32, PMM_DTYPE_F64, PMM_DTYPE_BF16 or PMM_DTYPE_I8. */
 int pmm_corpus_dtype(const pmm_corpus *corpus, int *dtype);
 int pmm_corpus_destroy(pmm_corpus *corpus);
 int pmm_corpus_info(const pmm_corpus *corpus, int64_t *n, int64_t *d, int *device);
@@ -522,6 +532,52 @@ int pmm_topk_f64_corpus(const pmm_corpus *corpus, const double *q, int64_t m, in
  * way). */
 int pmm_topk_bf16_corpus(const pmm_corpus *corpus, const float *q, int64_t m, int64_t k,
                          int metric, uint32_t *out_idx, float *out_score);
+
+/* ---------------------------------------------------------------------------
+ * Rows of signed bytes (quantised embeddings; Polars Int8 columns).  The
+ * reference widens them to f64 (src/matmul.rs:13-19, :143, :179) and takes its
+ * f64 branch (:449-468); these entries return THAT answer -- the indices, the
+ * f64 score bits and the tie order of pmm_topk_f64 on the values cast to f64 --
+ * computed on the int8 MFMA (v_mfma_i32_16x16x64_i8).  An int8 dot product is
+ * exact in i32 and a row's sum of squares in u32, so every f64 score is the
+ * oracle's two or three correctly rounded operations on exact integers; a
+ * zero score is +0.0.
+ *   Limits.  d < 65536 (a sum of squares and a squared distance stay in u32,
+ * a dot in i32), else PMM_ERR_UNSUPPORTED.  The int8 scan takes
+ * roundup(d, 64) <= 2048 and k <= 1024; past either, both sides are widened to
+ * f64 on the device (exactly) and searched by the f64 path: the same bits at
+ * the f64 rate.  A query row whose candidate buffer overflows (many equal
+ * corpus rows at its k-th place) is searched again on the widened rows, the
+ * same bits again.  k = 0, m = 0 and k > n as pmm_topk_f64.  Under
+ * pmm_set_devices the host entry runs on the list's first device (int8 rows
+ * are not sharded).  Every entry synchronises the stream before it returns.
+ * ------------------------------------------------------------------------- */
+int pmm_topk_i8(const int8_t *q, int64_t m, const int8_t *c, int64_t n, int64_t d, int64_t k, int metric,
+                uint32_t *out_idx, double *out_score);
+
+/* pmm_topk_i8 against an int8 corpus handle (pmm_corpus_create_i8), bit-equal
+ * to it: host queries in, host results out, 0 <= k <= n.  A handle of other
+ * rows: PMM_ERR_ARG naming the entry that serves it (and pmm_topk_f32_corpus /
+ * pmm_topk_f64_corpus / pmm_topk_bf16_corpus refuse an int8 handle the same
+ * way, naming this entry). */
+int pmm_topk_i8_corpus(const pmm_corpus *corpus, const int8_t *q, int64_t m, int64_t k, int metric,
+                       uint32_t *out_idx, double *out_score);
+
+/* Bytes of workspace pmm_topk_i8_device needs for this problem: the one route
+ * decision (int8 scan or widened f64 search) the call then follows, with the
+ * environment as it is now.  Touches no device.  0 for an empty or refused
+ * problem. */
+size_t pmm_topk_i8_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int metric);
+
+/* The same top-k over device rows on the caller's stream: ldq / ldc are row
+ * strides in bytes, multiples of 16 and >= roundup(d, 64), columns past d
+ * zero-filled, 16-byte-aligned bases; out_idx / out_score device buffers of
+ * m * k entries, indices offset by index_base.  workspace: NULL (a per-thread
+ * cached buffer) or workspace_bytes >= pmm_topk_i8_workspace_bytes at a
+ * 256-byte-aligned address (an overflow re-run allocates for itself). */
+int pmm_topk_i8_device(const int8_t *q, int64_t ldq, int64_t m, const int8_t *c, int64_t ldc, int64_t n, int64_t d,
+                       int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, double *out_score,
+                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* Range search: every corpus row whose score passes a threshold, for each
  * query row (host queries in, host results out).  Corpus row j is a hit of

@@ -235,6 +235,8 @@ RowKind row_kind(int dtype) {
   switch (dtype) {
     case PMM_DTYPE_F64: return RowKind{8, 16, 8, 2, 1};
     case PMM_DTYPE_BF16: return RowKind{2, kBf16DAlign, 4, 4, 2};
+    // int8: [u32 sum of squares | f32 1 / sqrt(sum)]; the i8 entries read both by name
+    case PMM_DTYPE_I8: return RowKind{1, kI8DAlign, 4, 2, 0};
     default: return RowKind{4, 32, 4, 4, 2};
   }
 }
@@ -2360,6 +2362,234 @@ std::vector<int> devices_snapshot() {
 // pmm_set_device choice or the current device).  A one-entry list therefore
 // moves all host work to that device; work that is not sharded (f32 k > 1024,
 // .pmm.matmul) runs on the root of a longer list.
+// ---------------------------------------------------------------------------
+// int8 top-k (pmm_i8.hip; DESIGN.md §4d "Int8 rows"): the f64 branch's answer for rows of
+// signed bytes -- indices and f64 score bits -- from the int8 MFMA.  One route
+// per call, decided here: the workspace is sized by it and the executor
+// follows it.
+//   native   padded d <= kI8MaxD and k <= kFusedMaxK: the chunked int8 scan
+//            with an exact f64 finish; rows whose candidate buffer overflowed
+//            (many equal rows at the k-th place) are re-run widened;
+//   widened  otherwise: both sides widened to f64 in the workspace (exact) and
+//            searched by topk_f64_device_impl, the old route at the old rate.
+// ---------------------------------------------------------------------------
+struct I8Route {
+  bool native = false;
+  int cap = 0;
+  int64_t mc = 0;  // query rows per pass (candidate-buffer budget)
+  size_t off_count = 0, off_qs = 0, off_qf = 0, off_cs = 0, off_cf = 0, off_tkey = 0, off_tidx = 0, off_cnt = 0,
+         off_ovf = 0, off_rows = 0, off_cand = 0;
+  bool fused64 = false;  // widened: the f64 path's own route
+  int64_t dp64 = 0;
+  size_t off_q64 = 0, off_c64 = 0, off_w64 = 0;
+  size_t total = 0;
+};
+
+// The candidate-buffer capacity: the f64 scan's rule.  PMM_I8_CAP (per call;
+// a power of two from 64 up, below the rule's value) lowers it, so that a test
+// reaches the overflow re-run with a small corpus.
+int i8_cap(int64_t k) {
+  const int cap = std::min(4096, std::max(1024, next_pow2(4 * (int)std::min<int64_t>(k, kFusedMaxK) + 256)));
+  const char *e = getenv("PMM_I8_CAP");
+  const int v = e ? atoi(e) : 0;
+  return (v >= 64 && v < cap && (v & (v - 1)) == 0) ? v : cap;
+}
+
+I8Route route_i8(int64_t m, int64_t n, int64_t d, int64_t k) {
+  I8Route r;
+  const int64_t dp = padded_dim(PMM_DTYPE_I8, d);
+  r.native = dp <= kI8MaxD && k <= kFusedMaxK;
+  size_t off = 0;
+  if (!r.native) {
+    r.dp64 = padded_dim(PMM_DTYPE_F64, d);
+    r.fused64 = f64_use_fused(m, n, k);
+    r.off_q64 = off;
+    off = al256(off + (size_t)m * r.dp64 * 8);
+    r.off_c64 = off;
+    off = al256(off + (size_t)n * r.dp64 * 8);
+    r.off_w64 = off;
+    r.total = off + f64_workspace_bytes(m, n, k, r.fused64);
+    return r;
+  }
+  r.cap = i8_cap(k);
+  r.mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kF64CandBudget / ((size_t)r.cap * 16))));
+  r.off_count = off;
+  off += 256;
+  r.off_qs = off;
+  off = al256(off + (size_t)m * 4);
+  r.off_qf = off;
+  off = al256(off + (size_t)m * 4);
+  r.off_cs = off;
+  off = al256(off + (size_t)n * 4);
+  r.off_cf = off;
+  off = al256(off + (size_t)n * 4);
+  r.off_tkey = off;
+  off = al256(off + (size_t)r.mc * 4);
+  r.off_tidx = off;
+  off = al256(off + (size_t)r.mc * 4);
+  r.off_cnt = off;
+  off = al256(off + (size_t)r.mc * 4);
+  r.off_ovf = off;
+  off = al256(off + (size_t)r.mc * 4);
+  r.off_rows = off;
+  off = al256(off + (size_t)m * 4);
+  r.off_cand = off;
+  off = al256(off + (size_t)r.mc * r.cap * 16);
+  r.total = off;
+  return r;
+}
+
+// The listed query rows (device `rows`, r of them) searched again on the f64
+// path: they and the whole corpus widened into an allocation of the call's
+// own, the lists scattered to the rows' places.  Synchronises.
+int i8_rerun_rows(const int8_t *dq, int64_t ldq, const int *rows, int64_t r, const int8_t *dc, int64_t ldc, int64_t n,
+                  int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *oi, double *os, hipStream_t s) {
+  const int64_t dp64 = padded_dim(PMM_DTYPE_F64, d);
+  const bool fused = f64_use_fused(r, n, k);
+  const size_t o_c = al256((size_t)r * dp64 * 8), o_i = o_c + al256((size_t)n * dp64 * 8),
+               o_s = o_i + al256((size_t)r * k * 4), o_w = o_s + al256((size_t)r * k * 8);
+  char *tmp = nullptr;
+  hipError_t e = hipMalloc(&tmp, o_w + f64_workspace_bytes(r, n, k, fused));
+  if (e != hipSuccess) return fail(PMM_ERR_HIP, "int8 re-run allocation failed: %s", hipGetErrorString(e));
+  int rc = PMM_OK;
+  {
+    Timed t("widen_i8_f64", s);
+    e = launch_i8_widen(dq, ldq, rows, r, (int)d, (double *)tmp, dp64, s);
+    if (e == hipSuccess) e = launch_i8_widen(dc, ldc, nullptr, n, (int)d, (double *)(tmp + o_c), dp64, s);
+  }
+  if (e == hipSuccess)
+    rc = topk_f64_device_impl((const double *)tmp, dp64, r, (const double *)(tmp + o_c), dp64, n, d, k, metric,
+                              index_base, (uint32_t *)(tmp + o_i), (double *)(tmp + o_s), tmp + o_w, s, fused);
+  if (e == hipSuccess && rc == PMM_OK)
+    e = launch_i8_scatter((const uint32_t *)(tmp + o_i), (const double *)(tmp + o_s), rows, r, (int)k, oi, os, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffer is freed)
+  (void)hipFree(tmp);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(PMM_ERR_HIP, "int8 re-run failed: %s", hipGetErrorString(e));
+  return rc;
+}
+
+// The executor over the route's workspace w (route.total bytes).  dq / dc:
+// device rows of signed bytes, strides multiples of 16 and >= roundup(d, 64),
+// zero-padded.  cs_pre / cf_pre: the corpus rows' sums of squares and factors
+// already on the device (a handle's), else nullptr.  Synchronises the stream
+// (the overflow count is read back).
+int topk_i8_device_impl(const I8Route &r, const int8_t *dq, int64_t ldq, int64_t m, const int8_t *dc, int64_t ldc,
+                        int64_t n, int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *oi, double *os,
+                        char *w, hipStream_t s, const uint32_t *cs_pre = nullptr, const float *cf_pre = nullptr) {
+  if (!r.native) {
+    double *q64 = (double *)(w + r.off_q64), *c64 = (double *)(w + r.off_c64);
+    {
+      Timed t("widen_i8_f64", s);
+      HIP_TRY(launch_i8_widen(dq, ldq, nullptr, m, (int)d, q64, r.dp64, s));
+      HIP_TRY(launch_i8_widen(dc, ldc, nullptr, n, (int)d, c64, r.dp64, s));
+    }
+    if (int rc = topk_f64_device_impl(q64, r.dp64, m, c64, r.dp64, n, d, k, metric, index_base, oi, os, w + r.off_w64,
+                                      s, r.fused64))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  }
+  const int64_t dp = padded_dim(PMM_DTYPE_I8, d);
+  unsigned *count = (unsigned *)(w + r.off_count);
+  uint32_t *qs = (uint32_t *)(w + r.off_qs), *cs = (uint32_t *)(w + r.off_cs);
+  float *qf = (float *)(w + r.off_qf), *cf = (float *)(w + r.off_cf);
+  int *rows = (int *)(w + r.off_rows);
+  HIP_TRY(hipMemsetAsync(count, 0, 4, s));
+  {
+    Timed t("norms_i8", s);
+    HIP_TRY(launch_i8_norms(dq, m, ldq, (int)dp, qs, qf, s));
+    if (cs_pre) {
+      cs = (uint32_t *)cs_pre;
+      cf = (float *)cf_pre;
+    } else {
+      HIP_TRY(launch_i8_norms(dc, n, ldc, (int)dp, cs, cf, s));
+    }
+  }
+  // the f64 scan's chunk schedule (topk_f64_device_impl): the first chunk
+  // half a buffer, later ones g times the columns seen, g sized for the tail
+  const int64_t s0 = std::min<int64_t>(n, r.cap / 2);
+  const double tail = 23.0 + std::sqrt(529.0 + 46.0 * (double)k);
+  const int64_t g = std::max<int64_t>(1, (int64_t)((double)(r.cap - k) / ((double)k + tail)));
+  for (int64_t r0 = 0; r0 < m; r0 += r.mc) {
+    const int rws = (int)std::min<int64_t>(r.mc, m - r0);
+    uint32_t *tkey = (uint32_t *)(w + r.off_tkey), *tidx = (uint32_t *)(w + r.off_tidx);
+    unsigned *cnt = (unsigned *)(w + r.off_cnt), *ovf = (unsigned *)(w + r.off_ovf);
+    Ent *cand = (Ent *)(w + r.off_cand);
+    HIP_TRY(launch_i8_reset(tkey, tidx, cnt, ovf, rws, s));
+    I8TopkArgs a{};
+    a.q = dq + r0 * ldq;
+    a.c = dc;
+    a.qs = qs + r0;
+    a.cs = cs;
+    a.qf = qf + r0;
+    a.cf = cf;
+    a.ldq = ldq;
+    a.ldc = ldc;
+    a.M = rws;
+    a.D = (int)dp;
+    a.metric = metric;
+    a.tkey = tkey;
+    a.tidx = tidx;
+    a.cnt = cnt;
+    a.cand = cand;
+    a.cap = r.cap;
+    I8SelArgs sa{};
+    sa.cand = cand;
+    sa.cnt = cnt;
+    sa.cap = r.cap;
+    sa.M = rws;
+    sa.k = (int)k;
+    sa.P = r.cap;
+    sa.tkey = tkey;
+    sa.tidx = tidx;
+    sa.ovf = ovf;
+    sa.metric = metric;
+    sa.qs = qs + r0;
+    sa.cs = cs;
+    sa.index_base = index_base;
+    sa.out_idx = oi + r0 * k;
+    sa.out_score = os + r0 * k;
+    int64_t seen = 0, chunk = s0;
+    while (seen < n) {
+      const int64_t cc = std::min<int64_t>(chunk, n - seen);
+      a.col0 = (int)seen;
+      a.ncol = (int)cc;
+      {
+        Timed t("gemm_i8_topk", s);
+        HIP_TRY(launch_gemm_i8_topk(a, s));
+      }
+      seen += cc;
+      if (seen < n) {
+        Timed t("select_i8", s);
+        HIP_TRY(launch_i8_select(sa, s));
+      } else {
+        Timed t("i8_finish", s);
+        HIP_TRY(launch_i8_finish(sa, s));
+      }
+      chunk = seen * g;
+    }
+    HIP_TRY(launch_i8_collect(ovf, rws, (int)r0, count, rows, s));
+  }
+  // rows that dropped candidates: again, on the widened rows
+  unsigned nov = 0;
+  HIP_TRY(hipMemcpyAsync(&nov, count, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (nov) return i8_rerun_rows(dq, ldq, rows, nov, dc, ldc, n, d, k, metric, index_base, oi, os, s);
+  return PMM_OK;
+}
+
+// What every int8 entry checks before it touches a device.
+int validate_i8(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
+  int rc = validate_sizes(m, n, d, k, true);
+  if (rc) return rc;
+  if ((rc = check_metric(metric))) return rc;
+  if (d >= kI8DimLimit)
+    return fail(PMM_ERR_UNSUPPORTED, "int8 rows take d < %d (got %lld): a sum of squares must fit in 32 bits",
+                kI8DimLimit, (long long)d);
+  return PMM_OK;
+}
+
 int list_root() {
   std::lock_guard<std::mutex> lk(g_devs_mu);
   return g_devs.empty() ? -1 : g_devs[0];
@@ -2492,8 +2722,9 @@ static const ScreenImage *corpus_screen_image(const pmm_corpus *h, hipStream_t s
 // A handle serves the one top-k entry of its row type: the others refuse it
 // and name that entry.
 static int wrong_handle(const pmm_corpus *h) {
-  static const char *const kRows[] = {"f32", "f64", "bf16"};
-  static const char *const kEntry[] = {"pmm_topk_f32_corpus", "pmm_topk_f64_corpus", "pmm_topk_bf16_corpus"};
+  static const char *const kRows[] = {"f32", "f64", "bf16", "int8"};
+  static const char *const kEntry[] = {"pmm_topk_f32_corpus", "pmm_topk_f64_corpus", "pmm_topk_bf16_corpus",
+                                       "pmm_topk_i8_corpus"};
   return fail(PMM_ERR_ARG, "the corpus handle holds %s rows: use %s", kRows[h->dtype], kEntry[h->dtype]);
 }
 
@@ -2527,6 +2758,9 @@ static int check_subset_parent(const pmm_corpus *p, pmm_corpus **out) {
   if (p->shards.size() != 1)
     return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no subsets: derive from a handle of one shard",
                 (int)p->shards.size());
+  if (p->dtype == PMM_DTYPE_I8)
+    return fail(PMM_ERR_UNSUPPORTED, "an int8 corpus handle has no subsets and no partitions: pmm_topk_i8_corpus searches "
+                                     "all of its rows");
   return PMM_OK;
 }
 
@@ -2610,7 +2844,7 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
 // the thread's lifetime), rounded with the norms of both metrics in one pass.
 static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const void *c, float *stage, hipStream_t s) {
   const int64_t d = h->d, dp = h->dp, n = x.n;
-  const size_t elem = h->dtype == PMM_DTYPE_F64 ? 8 : 4;  // of the HOST rows
+  const size_t elem = h->dtype == PMM_DTYPE_F64 ? 8 : h->dtype == PMM_DTYPE_I8 ? 1 : 4;  // of the HOST rows
   const void *src = (const char *)c + (size_t)x.lo * d * elem;
   hipError_t e1, e2;
   if (h->dtype == PMM_DTYPE_BF16) {
@@ -2623,7 +2857,11 @@ static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const vo
     e2 = launch_round_norms_bf16(stage, n, d, d, (uint16_t *)x.rows, dp, nm, nm + n, nm + 2 * n, nm + 3 * n, s);
   } else {
     if (int rc = upload_padded(x.rows, src, n, d, dp, elem, s)) return rc;
-    if (h->dtype == PMM_DTYPE_F64) {
+    if (h->dtype == PMM_DTYPE_I8) {
+      Timed t("norms_i8", s);
+      e1 = launch_i8_norms(x.rows_as<int8_t>(), n, dp, (int)dp, (uint32_t *)x.norms, (float *)x.norms + n, s);
+      e2 = hipSuccess;
+    } else if (h->dtype == PMM_DTYPE_F64) {
       double *nm = (double *)x.norms;
       e1 = launch_norms_f64(x.rows_as<double>(), n, d, dp, 0, nm, s);
       e2 = launch_norms_f64(x.rows_as<double>(), n, d, dp, 1, nm + n, s);
@@ -2653,8 +2891,12 @@ static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_cor
   int dev;
   DevScope scope;
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
+  if (dtype == PMM_DTYPE_I8 && d >= kI8DimLimit)
+    return fail(PMM_ERR_UNSUPPORTED, "int8 rows take d < %d (got %lld): a sum of squares must fit in 32 bits",
+                kI8DimLimit, (long long)d);
   std::vector<int> devs = devices_snapshot();
-  if (devs.size() <= 1) devs.assign(1, dev);
+  // (an int8 handle is not sharded: it lives on the list's first device)
+  if (devs.size() <= 1 || dtype == PMM_DTYPE_I8) devs.assign(1, dev);
   const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
   const RowKind rk = row_kind(dtype);
   pmm_corpus *h = new pmm_corpus();
@@ -3789,6 +4031,8 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   if (rc) return rc;
   if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
   if (h->partitioned()) return partitioned_handle(h);
+  if (h->dtype == PMM_DTYPE_I8)
+    return fail(PMM_ERR_UNSUPPORTED, "range search takes an f32 handle: an int8 handle has no range search");
   if (h->dtype != PMM_DTYPE_F32) {
     static const char *const kRows[] = {"f32", "f64", "bf16"};
     return fail(PMM_ERR_ARG, "range search takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
@@ -4061,6 +4305,111 @@ int pmm_topk_bf16_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t
     return topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, x.rows_as<uint16_t>(), db, n, d, k, metric,
                                  0u, *oi, *os, b + off_w, ws_need, s, dev, qn, shard_norms<float>(h, x, metric));
   });
+}
+
+// ---- int8 rows (DESIGN.md §4d "Int8 rows") ----
+
+size_t pmm_topk_i8_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
+  (void)metric;  // (every metric keeps the same buffers)
+  if (m <= 0 || n <= 0 || d <= 0 || k <= 0 || d >= kI8DimLimit) return 0;
+  return route_i8(m, n, d, k).total;
+}
+
+int pmm_topk_i8_device(const int8_t *q, int64_t ldq, int64_t m, const int8_t *c, int64_t ldc, int64_t n, int64_t d,
+                       int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, double *out_score,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = validate_i8(m, n, d, k, metric);
+  if (rc) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
+  const int64_t dp = padded_dim(PMM_DTYPE_I8, d);
+  if (d == 0 || ldq < dp || ldc < dp || (ldq & 15) || (ldc & 15) || ((uintptr_t)q & 15) || ((uintptr_t)c & 15))
+    return fail(PMM_ERR_ARG,
+                "device int8 inputs need row strides >= roundup(d, 64) that are multiples of 16 (zero-padded) and "
+                "16-byte-aligned bases (d=%lld ldq=%lld ldc=%lld)",
+                (long long)d, (long long)ldq, (long long)ldc);
+  int dev;
+  if ((rc = ensure_device(&dev))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const I8Route route = route_i8(m, n, d, k);
+  void *w = workspace;
+  if (w) {
+    if (workspace_bytes < route.total || ((uintptr_t)w & 255))
+      return fail(PMM_ERR_ARG, "the int8 workspace needs %zu bytes at a 256-byte-aligned address (got %zu): size it "
+                               "with pmm_topk_i8_workspace_bytes", route.total, workspace_bytes);
+  } else if ((rc = arena(dev, s, route.total, &w))) {
+    return rc;
+  }
+  rc = topk_i8_device_impl(route, q, ldq, m, c, ldc, n, d, k, metric, index_base, out_idx, out_score, (char *)w, s);
+  if (rc) return rc;
+  return workspace ? PMM_OK : arena_record(dev, s);
+}
+
+int pmm_topk_i8(const int8_t *q, int64_t m, const int8_t *c, int64_t n, int64_t d, int64_t k, int metric,
+                uint32_t *out_idx, double *out_score) {
+  int rc = validate_i8(m, n, d, k, metric);
+  if (rc) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
+  if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
+  // (a device list does not shard int8 rows: the call runs on its first device)
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  const int64_t dp = padded_dim(PMM_DTYPE_I8, d);
+  const I8Route route = route_i8(m, n, d, k);
+  size_t off_q = 0, off_c = al256((size_t)m * dp), off_i = off_c + al256((size_t)n * dp);
+  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
+  void *base;
+  if ((rc = arena(dev, s, off_w + route.total, &base))) return rc;
+  char *b = (char *)base;
+  if ((rc = upload_padded(b + off_q, q, m, d, dp, 1, s))) return rc;
+  if ((rc = upload_padded(b + off_c, c, n, d, dp, 1, s))) return rc;
+  uint32_t *oi = (uint32_t *)(b + off_i);
+  double *os = (double *)(b + off_s);
+  if ((rc = topk_i8_device_impl(route, (const int8_t *)(b + off_q), dp, m, (const int8_t *)(b + off_c), dp, n, d, k,
+                                metric, 0u, oi, os, b + off_w, s)))
+    return rc;
+  return download_lists(out_idx, out_score, oi, os, m, k, s);
+}
+
+int pmm_corpus_create_i8(const int8_t *c, int64_t n, int64_t d, pmm_corpus **out) {
+  return corpus_create(PMM_DTYPE_I8, c, n, d, out);
+}
+
+int pmm_topk_i8_corpus(const pmm_corpus *h, const int8_t *q, int64_t m, int64_t k, int metric, uint32_t *out_idx,
+                       double *out_score) {
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (h->partitioned()) return partitioned_handle(h);
+  if (h->dtype != PMM_DTYPE_I8) return wrong_handle(h);
+  int rc = validate_i8(m, h->n, h->d, k, metric);
+  if (rc) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  const int64_t dp = h->dp, n = h->n;
+  const I8Route route = route_i8(m, n, h->d, k);
+  size_t off_q = 0, off_i = al256((size_t)m * dp);
+  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
+  void *base;
+  if ((rc = arena(dev, s, off_w + route.total, &base))) return rc;
+  char *b = (char *)base;
+  if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 1, s))) return rc;
+  uint32_t *oi = (uint32_t *)(b + off_i);
+  double *os = (double *)(b + off_s);
+  if ((rc = topk_i8_device_impl(route, (const int8_t *)(b + off_q), dp, m, x.rows_as<int8_t>(), dp, n, h->d, k, metric,
+                                0u, oi, os, b + off_w, s, (const uint32_t *)x.norms, (const float *)x.norms + n)))
+    return rc;
+  return download_lists(out_idx, out_score, oi, os, m, k, s);
 }
 
 int pmm_timing_enable(int enable) {

@@ -412,6 +412,60 @@ hipError_t launch_gemm_f64_topk(const F64TopkArgs &a, hipStream_t s);
 hipError_t launch_f64_select(const F64SelArgs &a, hipStream_t s);
 hipError_t launch_f64_reset(unsigned long long *tkey, uint32_t *tidx, unsigned *cnt, int m, unsigned cnt0,
                             hipStream_t s);
+// ---- int8 top-k (pmm_i8.hip) ----
+// Rows of signed bytes at a stride that is a multiple of kI8DAlign bytes,
+// zero-padded.  The int8 MFMA scan takes a padded d up to kI8MaxD (the range
+// its tests pin; its K loop has no register limit) and k up to kFusedMaxK (the
+// candidate buffers); past either the rows are widened to f64 on the device
+// and searched by the f64 path.  d < kI8DimLimit keeps a row's sum of squares
+// and a squared distance in u32 and a dot in i32.
+constexpr int kI8DAlign = 64;
+constexpr int kI8MaxD = 2048;
+constexpr int kI8DimLimit = 1 << 16;
+// The cosine key's distance from the f64 score (DESIGN.md §4d "Int8 rows"): five f32
+// roundings of a value of magnitude at most 1, 5.001 * 2^-24 < 2^-21.
+constexpr float kI8CosEps = 0x1p-21f;
+struct I8TopkArgs {
+  const int8_t *q;           // this launch's rows (row stride ldq bytes)
+  const int8_t *c;           // the whole corpus (row stride ldc bytes)
+  const uint32_t *qs, *cs;   // integer sums of squares (qs: this launch's rows)
+  const float *qf, *cf;      // f32(1 / sqrt(sum)), 0 for a zero row
+  int64_t ldq, ldc;
+  int M, D;                  // rows; padded K (a multiple of kI8DAlign)
+  int col0, ncol;            // corpus columns [col0, col0 + ncol) of this chunk
+  int metric;
+  const uint32_t *tkey;      // [M] row threshold: an element is appended iff (key, lower index)
+  const uint32_t *tidx;      // beats (tkey, tidx); (0, ~0) = accept all
+  unsigned *cnt;             // [M] buffer counts
+  Ent *cand;                 // [M][cap]: key << 32, corpus row, the exact dot in `pad`
+  int cap;
+};
+struct I8SelArgs {
+  Ent *cand;
+  unsigned *cnt;
+  int cap, M, k, P;          // P: LDS entries per wave, a power of two >= cap
+  uint32_t *tkey, *tidx;
+  unsigned *ovf;             // [M] set when a row's count exceeded cap (entries were dropped)
+  int metric;
+  // the finish
+  const uint32_t *qs, *cs;
+  uint32_t index_base;
+  uint32_t *out_idx;         // [M][k]
+  double *out_score;
+};
+hipError_t launch_i8_norms(const int8_t *a, int64_t rows, int64_t ld, int dp, uint32_t *sq, float *fac,
+                           hipStream_t s);
+hipError_t launch_gemm_i8_topk(const I8TopkArgs &a, hipStream_t s);
+hipError_t launch_i8_select(const I8SelArgs &a, hipStream_t s);
+hipError_t launch_i8_finish(const I8SelArgs &a, hipStream_t s);
+hipError_t launch_i8_reset(uint32_t *tkey, uint32_t *tidx, unsigned *cnt, unsigned *ovf, int m, hipStream_t s);
+// rows[old *count ..) = base + r for every r < m with ovf[r] set; *count grows by their number
+hipError_t launch_i8_collect(const unsigned *ovf, int m, int base, unsigned *count, int *rows, hipStream_t s);
+// dst row i (ldd doubles, columns d .. ldd - 1 zero) = src row (rows ? rows[i] : i), widened exactly
+hipError_t launch_i8_widen(const int8_t *src, int64_t ld, const int *rows, int64_t r, int d, double *dst,
+                           int64_t ldd, hipStream_t s);
+hipError_t launch_i8_scatter(const uint32_t *oi, const double *os, const int *rows, int64_t r, int k,
+                             uint32_t *out_idx, double *out_score, hipStream_t s);
 // full-row sort fallback for very large k
 hipError_t launch_rowsort_global(const void *scores, int64_t lds, int rows, int N, int is_f64,
                                  int metric, void *keys_ws, int P2, int k, uint32_t index_base,

@@ -90,6 +90,15 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
         if subset is not None:
             raise ValueError("groups= and subset= cannot be combined: give the rows to leave out a null label")
         grp = _check_groups(groups, q.shape[0], c.shape[0])
+    if (q.dtype == np.int8 and c.dtype == np.int8 and compute == "f32" and subset is None and groups is None
+            and q.ndim == 2 and c.ndim == 2 and len(_native.get_devices()) <= 1):
+        # signed bytes on both sides: the int8 MFMA, the f64 route's bits (pmm_topk_i8)
+        if q.shape[1] != c.shape[1]:
+            raise RuntimeError(
+                f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
+                f"right has {c.shape[1]} dimensional vectors"
+            )
+        return _native.topk_i8_host(q, c, min(int(k), c.shape[0]), _native.metric_from_str(metric))
     dt = np.float32 if (q.dtype == np.float32 and c.dtype == np.float32) else np.float64
     if compute == "bf16":
         dt = np.float32

@@ -89,6 +89,11 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
     "pmm_range_f32_corpus",
+    "pmm_topk_i8",
+    "pmm_topk_i8_corpus",
+    "pmm_topk_i8_device",
+    "pmm_topk_i8_workspace_bytes",
+    "pmm_corpus_create_i8",
     "pmm_timing_enable",
     "pmm_timing_reset",
     "pmm_timing_read",
@@ -195,6 +200,11 @@ _SIGS = {
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_range_f32_corpus": ([_vp, _vp, _i64, ctypes.c_float, _i32, _i64, _vp, _vp, _vp,
                               ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_topk_i8": ([_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
+    "pmm_topk_i8_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
+    "pmm_topk_i8_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
+    "pmm_topk_i8_workspace_bytes": ([_i64, _i64, _i64, _i64, _i32], _sz),
+    "pmm_corpus_create_i8": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
     "pmm_timing_enable": ([_i32], _i32),
     "pmm_timing_reset": ([], _i32),
     "pmm_timing_read": (
@@ -303,6 +313,32 @@ def topk_host(q: np.ndarray, c: np.ndarray, k: int, metric: int, compute: int = 
         rc = _lib.pmm_topk_f64(ptr(q), m, ptr(c), n, d, k, metric, ptr(idx), ptr(sc))
     check(rc)
     return idx, sc
+
+
+def topk_i8_host(q: np.ndarray, c: np.ndarray, k: int, metric: int):
+    """Host-buffer top-k of int8 rows (pmm_topk_i8).  q: (m, d), c: (n, d) int8;
+    0 <= k <= n.  Returns (idx uint32 (m, k), scores float64 (m, k)): the bits
+    ``topk_host`` returns for the same values as float64."""
+    q = np.ascontiguousarray(q, dtype=np.int8)
+    c = np.ascontiguousarray(c, dtype=np.int8)
+    m, d = q.shape
+    n = c.shape[0]
+    idx = np.empty((m, k), dtype=np.uint32)
+    sc = np.empty((m, k), dtype=np.float64)
+    check(_lib.pmm_topk_i8(ptr(q), m, ptr(c), n, d, k, metric, ptr(idx), ptr(sc)))
+    return idx, sc
+
+
+def topk_i8_device(q_ptr: int, ldq: int, m: int, c_ptr: int, ldc: int, n: int, d: int, k: int, metric: int,
+                   out_idx_ptr: int, out_score_ptr: int, *, index_base: int = 0, workspace: int = 0,
+                   workspace_bytes: int = 0, stream: int = 0) -> None:
+    """pmm_topk_i8_device over device pointers (row strides in bytes)."""
+    check(_lib.pmm_topk_i8_device(q_ptr, ldq, m, c_ptr, ldc, n, d, k, metric, index_base, out_idx_ptr,
+                                  out_score_ptr, workspace or None, workspace_bytes, stream or None))
+
+
+def i8_workspace_bytes(m: int, n: int, d: int, k: int, metric: int) -> int:
+    return int(_lib.pmm_topk_i8_workspace_bytes(m, n, d, k, metric))
 
 
 class _PinnedBlock:
@@ -566,6 +602,7 @@ def timing_read(kernel: str):
 DTYPE_F32 = 0
 DTYPE_F64 = 1
 DTYPE_BF16 = 2
+DTYPE_I8 = 3
 
 _COMPUTE_MODES = ("f32", "bf16")
 
@@ -592,6 +629,8 @@ def corpus_device_bytes(n: int, d: int, dtype=np.float32, compute: str = "f32", 
     ``compute="bf16"`` handle's figure is the same with and without it."""
     if check_compute(compute) == "bf16":
         return n * (-(-d // 128) * 128) * 2 + n * 4 * 4
+    if np.dtype(dtype) == np.int8:  # pmm_corpus_create_i8: the bytes padded to 64, a u32 and an f32 per row
+        return n * (-(-d // 64) * 64) + n * 2 * 4
     if np.dtype(dtype) == np.float64:
         dp = -(-d // 16) * 16
         return n * dp * 8 + n * 2 * 8
@@ -670,6 +709,30 @@ class DeviceCorpus:
         self.n, self.d = c.shape
         self._nbytes0 = corpus_device_bytes(self.n, self.d, self.dtype, compute)  # device footprint, not host bytes
 
+    @classmethod
+    def int8(cls, c: np.ndarray) -> "DeviceCorpus":
+        """An int8 corpus (pmm_corpus_create_i8): the signed bytes as they are
+        with each row's integer sum of squares.  ``topk`` then takes int8
+        queries and returns float64 scores -- the bits an f64 handle of the
+        same values returns -- from the int8 MFMA.  (``DeviceCorpus(c)`` of an
+        int8 array converts to f32, as before.)"""
+        c = np.asarray(c)
+        if c.dtype != np.int8 or c.ndim != 2:
+            raise TypeError(f"DeviceCorpus.int8 takes a 2-D int8 array, got {c.dtype} with shape {c.shape}")
+        c = np.ascontiguousarray(c)
+        self = cls.__new__(cls)
+        self.compute = "f32"
+        self.dtype = np.dtype(np.int8)
+        h = ctypes.c_void_p()
+        check(_lib.pmm_corpus_create_i8(ptr(c), c.shape[0], c.shape[1], ctypes.byref(h)))
+        self._h = h
+        self._lock = threading.Lock()
+        self._refs = 0
+        self._closing = False
+        self.n, self.d = c.shape
+        self._nbytes0 = corpus_device_bytes(self.n, self.d, np.int8)
+        return self
+
     @property
     def nbytes(self) -> int:
         """HBM the handle holds now (pmm_corpus_bytes): the creation-time
@@ -701,13 +764,17 @@ class DeviceCorpus:
     def topk(self, q: np.ndarray, k: int, metric: int):
         """(idx uint32 (m, k), scores (m, k) in the corpus dtype); q is
         converted to the corpus dtype."""
+        if self.dtype == np.int8 and np.asarray(q).dtype != np.int8:
+            raise TypeError(f"an int8 corpus takes int8 queries, not {np.asarray(q).dtype}")
         q = np.ascontiguousarray(q, dtype=self.dtype)
         if q.shape[1] != self.d:
             raise ValueError("dimension mismatch")
         m = q.shape[0]
         idx = np.empty((m, k), dtype=np.uint32)
-        sc = np.empty((m, k), dtype=self.dtype)
-        fn = (_lib.pmm_topk_bf16_corpus if self.compute == "bf16" else
+        i8 = self.dtype == np.int8
+        sc = np.empty((m, k), dtype=np.float64 if i8 else self.dtype)
+        fn = (_lib.pmm_topk_i8_corpus if i8 else
+              _lib.pmm_topk_bf16_corpus if self.compute == "bf16" else
               _lib.pmm_topk_f64_corpus if self.dtype == np.float64 else _lib.pmm_topk_f32_corpus)
         self.acquire()
         try:

@@ -102,17 +102,30 @@ def _is_f32(arr) -> bool:
     return False
 
 
+def _is_i8(arr) -> bool:
+    """List[i8] / Array[i8, d] / an int8 matrix: rows of signed bytes."""
+    if isinstance(arr, np.ndarray):
+        return arr.dtype == np.int8
+    t = arr.type
+    if pa.types.is_list(t) or pa.types.is_large_list(t) or pa.types.is_fixed_size_list(t):
+        return t.value_type == pa.int8()
+    return False
+
+
 def _nrows(arr) -> int:
     return arr.shape[0] if isinstance(arr, np.ndarray) else len(arr)
 
 
 def _values_numpy(values: pa.Array, np_dtype) -> np.ndarray:
     """Child values cast to the compute dtype, nulls -> 0.0 (src/matmul.rs:192, 224)."""
-    target = pa.float32() if np_dtype == np.float32 else pa.float64()
+    if np_dtype == np.int8:  # (only int8 children come here: borrowed as they are)
+        target, zero = pa.int8(), 0
+    else:
+        target, zero = (pa.float32() if np_dtype == np.float32 else pa.float64()), 0.0
     if values.type != target:
         values = pc.cast(values, target)
     if values.null_count:
-        values = values.fill_null(0.0)
+        values = values.fill_null(zero)
     return values.to_numpy(zero_copy_only=False)
 
 
@@ -281,7 +294,8 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: 
             return hit[1].acquire()
         if not _fits_device(dev_bytes):
             return None
-        dc = _native.DeviceCorpus(c) if compute == "f32" else _native.DeviceCorpus(c, compute=compute)
+        dc = (_native.DeviceCorpus.int8(c) if c.dtype == np.int8 and compute == "f32" else
+              _native.DeviceCorpus(c) if compute == "f32" else _native.DeviceCorpus(c, compute=compute))
         _cache[key] = (rv, dc)
         total = sum(v[1].nbytes for v in _cache.values())
         while total > _CACHE_BYTES and len(_cache) > 1:
@@ -713,6 +727,14 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
         raise _compute_error(str(e)) from None
     use_f32 = bf16 or (_is_f32(lv) and _is_f32(rv))  # src/matmul.rs:427
     dt = np.float32 if use_f32 else np.float64
+    # Signed bytes on both sides (an extension in speed only): the reference
+    # widens them to f64 (src/matmul.rs:143, :179) and so did this function;
+    # the int8 route returns those bits from the int8 MFMA (pmm_topk_i8).
+    # Everything else -- mixed dtypes, UInt8, wider integers, compute="bf16",
+    # subset=, groups=, a device list -- keeps the f64 route.
+    i8 = not bf16 and sel is None and grp is None and _is_i8(lv) and _is_i8(rv)
+    if i8:
+        dt = np.int8
     q = _series_to_matrix(lv, dt)
     c = _series_to_matrix(rv, dt)
     t = _lap("extract", t)
@@ -742,6 +764,8 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
         sc = sc.astype(np.float64, copy=False)
     else:
         _apply_devices_env()
+        if i8 and len(_native.get_devices()) > 1:  # int8 rows are not sharded: the f64 route
+            q, c, i8 = q.astype(np.float64), c.astype(np.float64), False
         # (an f32 or bf16 handle sharded over several GPUs serves k <= 1024;
         # larger k runs on one GPU, the device list's first.  An f64 handle is
         # sharded the same way and serves any k.)
@@ -753,6 +777,8 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
                 _reaccount_cache(dc)
             finally:
                 dc.release()
+        elif i8:
+            idx, sc = _native.topk_i8_host(q, c, kk, metric_id)
         else:
             idx, sc = _native.topk_host(q, c, kk, metric_id,
                                         compute=_native.COMPUTE_BF16 if bf16 else _native.COMPUTE_F32)
