@@ -65,6 +65,19 @@ DeviceInfo g_dev[kMaxDevices];  // fixed storage: readers index it without the l
 // (pmm_set_devices): process-wide, empty = one device.
 std::mutex g_devs_mu;
 std::vector<int> g_devs;
+std::vector<int> devices_snapshot() {
+  std::lock_guard<std::mutex> lk(g_devs_mu);
+  return g_devs;
+}
+// The device host entry points run on when a device list is set: its first
+// entry (the root, which also merges a sharded search), else -1 (the thread's
+// pmm_set_device choice or the current device).  A one-entry list therefore
+// moves all host work to that device; work that is not sharded (f32 k > 1024,
+// .pmm.matmul, int8 rows) runs on the root of a longer list.
+int list_root() {
+  std::lock_guard<std::mutex> lk(g_devs_mu);
+  return g_devs.empty() ? -1 : g_devs[0];
+}
 
 struct TimingRec {
   const char *name;
@@ -207,6 +220,15 @@ int arena_record(int dev, hipStream_t s) {
 }
 
 size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
+// Consecutive regions of an arena, each starting 256-byte aligned.
+struct Layout {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off += al256(bytes);
+    return o;
+  }
+};
 int next_pow2(int x, int lo = 64) {
   int p = lo;
   while (p < x) p <<= 1;
@@ -1595,7 +1617,12 @@ constexpr size_t kChunkedMinBytes = size_t(256) << 20;  // corpus bytes from whi
 constexpr int kChunks = 4;
 
 int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, int64_t d, int64_t k,
-                          int metric, uint32_t *out_idx, float *out_score, int dev, hipStream_t s) {
+                          int metric, uint32_t *out_idx, float *out_score) {
+  int dev, rc;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
+  hipStream_t s, cs;
+  if ((rc = thread_stream(dev, &s)) || (rc = thread_stream(dev, &cs, true))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   int64_t bnd[kChunks + 1];
   bnd[0] = 0;
@@ -1608,13 +1635,10 @@ int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, 
     route[i] = route_topk(m, bnd[i + 1] - bnd[i], d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
     ws_need = std::max(ws_need, route[i].total);
   }
-  const size_t lists = (size_t)kChunks * 2 * m * k * 4;
-  size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_l = off_c + al256((size_t)n * dp * 4);
-  size_t off_i = off_l + al256(lists), off_s = off_i + al256((size_t)m * k * 4);
-  size_t off_w = off_s + al256((size_t)m * k * 4);
-  hipStream_t cs;
-  int rc;
-  if ((rc = thread_stream(dev, &cs, true))) return rc;
+  Layout L;
+  const size_t off_q = L.take((size_t)m * dp * 4), off_c = L.take((size_t)n * dp * 4);
+  const size_t off_l = L.take((size_t)kChunks * 2 * m * k * 4);
+  const size_t off_i = L.take((size_t)m * k * 4), off_s = L.take((size_t)m * k * 4), off_w = L.off;
   void *base;
   if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
   char *b = (char *)base;
@@ -1681,284 +1705,6 @@ int topk_f32_host_chunked(const float *q, int64_t m, const float *c, int64_t n, 
 }
 
 // ---------------------------------------------------------------------------
-// Corpus-sharded top-k over several devices from ONE host thread (the
-// drop-in boundary's multi-GPU path; pmm_set_devices).  SURVEY 8e's plan in
-// one process: the corpus is row-sharded (contiguous, sizes differ by <= 1),
-// every device gets the queries, runs the fused top-k on its shard with
-// index_base = the shard's first global row into a [2][m][k] block (index
-// plane, score plane), the blocks are copied peer-to-peer (xGMI) into the
-// root device's [G][2][m][k] buffer and k-way merged there in place
-// (merge_kernel, the same strided loader the RCCL-gathered lists use).  All
-// devices work concurrently: every launch is asynchronous on the device's own
-// stream of this thread; the root waits on per-shard events.  Each shard's
-// list is the exact top-k of its rows under the total order, so the merged
-// list equals the one-device result bit for bit.
-// ---------------------------------------------------------------------------
-// One shard of a sharded search, T = float (ShardSrc: topk_sharded, f32 or
-// bf16 compute) or double (ShardSrc64: topk_sharded_f64).
-template <typename T>
-struct ShardSrcT {
-  int dev;
-  int64_t lo, rows;
-  const T *host;         // host corpus rows [lo, lo + rows), row stride d, or
-  const void *dev_rows;  // a corpus handle's resident rows at their padded stride: T, or bf16 under bf16 compute
-  const T *dev_norms;    // with dev_rows: the handle's norm array of this metric (nullptr for dot)
-};
-using ShardSrc = ShardSrcT<float>;
-using ShardSrc64 = ShardSrcT<double>;
-
-// The shards of n host rows (row stride d) over a device list: one per listed
-// device, at most n, contiguous, sizes differing by at most one.
-int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }  // shard g: rows [n g / G, n (g + 1) / G)
-template <typename T>
-std::vector<ShardSrcT<T>> host_shards(const std::vector<int> &devs, const T *c, int64_t n, int64_t d) {
-  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
-  std::vector<ShardSrcT<T>> sh(G);
-  for (int g = 0; g < G; g++) {
-    const int64_t lo = shard_lo(n, G, g), hi = shard_lo(n, G, g + 1);
-    sh[g] = ShardSrcT<T>{devs[g], lo, hi - lo, c + lo * d, nullptr, nullptr};
-  }
-  return sh;
-}
-
-std::mutex g_peer_mu;
-bool g_peer_tried[kMaxDevices][kMaxDevices];
-
-// Lets `dev` read `peer`'s memory directly (xGMI) when the platform allows;
-// a peer copy works either way, so failures are ignored.
-void enable_peer(int dev, int peer) {
-  if (dev == peer) return;
-  std::lock_guard<std::mutex> lk(g_peer_mu);
-  if (g_peer_tried[dev][peer]) return;
-  g_peer_tried[dev][peer] = true;
-  int can = 0;
-  if (hipDeviceCanAccessPeer(&can, dev, peer) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(peer, 0);
-  (void)hipGetLastError();
-}
-
-// What the two sharded searches (topk_sharded, topk_sharded_f64) share.  Their
-// per-device plans (DevPlan, Dev64) differ in their offsets; both carry dev,
-// the thread's stream s on it, the arena base and the plan's total bytes.
-//
-// The distinct devices of the list, appended to dps in order of first use;
-// returns shard -> index into dps.  (Pure: plan_sharded runs without a GPU.)
-template <typename Dev, typename T>
-std::vector<int> distinct_devices(const std::vector<ShardSrcT<T>> &sh, std::vector<Dev> &dps) {
-  std::vector<int> plan_of(sh.size());
-  for (size_t g = 0; g < sh.size(); g++) {
-    int j = 0;
-    while (j < (int)dps.size() && dps[j].dev != sh[g].dev) j++;
-    if (j == (int)dps.size()) {
-      Dev p;
-      p.dev = sh[g].dev;
-      dps.push_back(p);
-    }
-    plan_of[g] = j;
-  }
-  return plan_of;
-}
-
-// Every planned device's stream of this thread and an arena of its plan's size.
-template <typename Dev>
-int acquire_devices(std::vector<Dev> &dps) {
-  for (auto &p : dps) {
-    HIP_TRY(hipSetDevice(p.dev));
-    if (int rc = thread_stream(p.dev, &p.s)) return rc;
-    void *b;
-    if (int rc = arena(p.dev, p.s, p.total, &b)) return rc;
-    p.base = (char *)b;
-  }
-  return PMM_OK;
-}
-
-// The per-shard completion events of a sharded search and its one exit: a
-// failure first drains every device's stream (queued work writes into the
-// arenas), then the events are destroyed on their devices.
-template <typename Dev, typename T>
-struct ShardedExit {
-  std::vector<Dev> &dps;
-  const std::vector<ShardSrcT<T>> &sh;
-  std::vector<hipEvent_t> ev;
-  ShardedExit(std::vector<Dev> &dps_, const std::vector<ShardSrcT<T>> &sh_) : dps(dps_), sh(sh_), ev(sh_.size(), nullptr) {}
-  int operator()(int code) {
-    if (code != PMM_OK)
-      for (auto &p : dps) {
-        (void)hipSetDevice(p.dev);
-        (void)hipStreamSynchronize(p.s);
-      }
-    for (size_t g = 0; g < ev.size(); g++)
-      if (ev[g]) {
-        (void)hipSetDevice(sh[g].dev);
-        (void)hipEventDestroy(ev[g]);
-      }
-    return code;
-  }
-};
-// (in a function with a ShardedExit named `finish`)
-#define SH_TRY(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return finish(fail(PMM_ERR_HIP, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), \
-                         __FILE__, __LINE__, #expr));                                     \
-  } while (0)
-#define SH_RC(expr)                        \
-  do {                                     \
-    int rc_ = (expr);                      \
-    if (rc_ != PMM_OK) return finish(rc_); \
-  } while (0)
-
-// Memory plan of topk_sharded (pure: no HIP call, so the CPU tests check it
-// through pmm_shard_plan).  One DevPlan per DISTINCT device of the list: that
-// device's queries once, one workspace (its shards run in stream order), and
-// per shard the uploaded rows (host shards only) and its [2][m][k] list; the
-// root plan (the first shard's device) also holds the gathered [G][2][m][k]
-// lists and the merged output.
-struct DevPlan {
-  int dev;
-  hipStream_t s = nullptr;
-  char *base = nullptr;
-  size_t off_q = 0, off_qb = 0, off_ws = 0, ws_bytes = 0, total = 0;
-};
-struct ShardLayout {
-  std::vector<DevPlan> dps;
-  std::vector<int> plan_of;  // shard -> index into dps
-  std::vector<size_t> off_c, off_cb, off_list;
-  std::vector<TopkRoute> route;        // per shard (never screened)
-  size_t off_gather = 0, off_out = 0;  // in the root plan
-};
-
-void plan_sharded(const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t k, int metric, int compute,
-                  ShardLayout &L) {
-  const int G = (int)sh.size();
-  const bool bf16 = compute == PMM_COMPUTE_BF16;
-  const int64_t dp = padded_dim(bf16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, d);
-  const size_t list_bytes = (size_t)2 * m * k * 4;
-  L.dps.clear();
-  L.plan_of = distinct_devices(sh, L.dps);
-  L.off_c.assign(G, 0);
-  L.off_cb.assign(G, 0);
-  L.off_list.assign(G, 0);
-  L.route.assign(G, TopkRoute());
-  for (auto &p : L.dps) {
-    size_t off = 0;
-    p.off_q = off;  // f32: padded rows; bf16: f32 staging rows (stride d)
-    off = al256(off + (size_t)m * (bf16 ? d : dp) * 4);
-    p.off_qb = off;  // bf16 rows
-    off = al256(off + (bf16 ? (size_t)m * dp * 2 : 0));
-    for (int g = 0; g < G; g++) {
-      if (sh[g].dev != p.dev) continue;
-      L.route[g] = route_topk(m, sh[g].rows, d, k, metric, compute, device_cus(p.dev), false, true);
-      p.ws_bytes = std::max(p.ws_bytes, L.route[g].total);
-      L.off_c[g] = off;
-      if (sh[g].host) off = al256(off + (size_t)sh[g].rows * (bf16 ? d : dp) * 4);
-      L.off_cb[g] = off;
-      if (bf16 && sh[g].host) off = al256(off + (size_t)sh[g].rows * dp * 2);  // (resident: the handle's rows)
-      L.off_list[g] = off;
-      off = al256(off + list_bytes);
-    }
-    p.off_ws = off;
-    off = al256(off + p.ws_bytes);
-    p.total = off;
-  }
-  DevPlan &rp = L.dps[L.plan_of[0]];
-  L.off_gather = rp.total;
-  L.off_out = al256(L.off_gather + (size_t)G * list_bytes);
-  rp.total = al256(L.off_out + list_bytes);
-}
-
-int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, int compute,
-                 const std::vector<ShardSrc> &sh, uint32_t *out_idx, float *out_score) {
-  const int G = (int)sh.size();
-  DevScope restore;
-  HIP_TRY(hipGetDevice(&restore.prev));
-  const bool bf16 = compute == PMM_COMPUTE_BF16;
-  const int64_t dp = padded_dim(bf16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, d);
-  const int root = sh[0].dev;
-  const size_t list_bytes = (size_t)2 * m * k * 4;
-  for (const ShardSrc &x : sh)
-    if (int rc = probe_device(x.dev)) return rc;
-  ShardLayout L;
-  plan_sharded(sh, m, d, k, metric, compute, L);
-  std::vector<DevPlan> &dps = L.dps;
-  const std::vector<int> &plan_of = L.plan_of;
-  const std::vector<size_t> &off_c = L.off_c, &off_cb = L.off_cb, &off_list = L.off_list;
-  DevPlan &rp = dps[plan_of[0]];
-  const size_t off_gather = L.off_gather, off_out = L.off_out;
-  if (int rc = acquire_devices(dps)) return rc;
-  ShardedExit<DevPlan, float> finish(dps, sh);
-  std::vector<hipEvent_t> &ev = finish.ev;
-  // queries to every device
-  for (auto &p : dps) {
-    SH_TRY(hipSetDevice(p.dev));
-    if (bf16) {
-      SH_TRY(hipMemcpyAsync(p.base + p.off_q, q, (size_t)m * d * 4, hipMemcpyHostToDevice, p.s));
-      SH_TRY(launch_f32_to_bf16((const float *)(p.base + p.off_q), m, d, d, (uint16_t *)(p.base + p.off_qb), dp,
-                                p.s));
-    } else {
-      SH_RC(upload_padded(p.base + p.off_q, q, m, d, dp, 4, p.s));
-    }
-  }
-  // per shard: rows, fused top-k with global indices, completion event
-  for (int g = 0; g < G; g++) {
-    DevPlan &p = dps[plan_of[g]];
-    const ShardSrc &x = sh[g];
-    SH_TRY(hipSetDevice(p.dev));
-    SH_TRY(hipEventCreateWithFlags(&ev[g], hipEventDisableTiming));
-    uint32_t *li = (uint32_t *)(p.base + off_list[g]);
-    float *ls = (float *)(li + (size_t)m * k);
-    if (bf16) {
-      const uint16_t *cb = (const uint16_t *)x.dev_rows;
-      if (x.host) {
-        SH_TRY(hipMemcpyAsync(p.base + off_c[g], x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
-        SH_TRY(launch_f32_to_bf16((const float *)(p.base + off_c[g]), x.rows, d, d,
-                                  (uint16_t *)(p.base + off_cb[g]), dp, p.s));
-        cb = (const uint16_t *)(p.base + off_cb[g]);
-      }
-      // (a resident shard brings its norms; the query norms are this call's)
-      SH_RC(topk_bf16_device_impl(L.route[g], (const uint16_t *)(p.base + p.off_qb), dp, m, cb, dp, x.rows, d, k,
-                                  metric, (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev, nullptr,
-                                  x.host ? nullptr : x.dev_norms));
-    } else {
-      const float *c = (const float *)x.dev_rows;
-      if (x.host) {
-        SH_RC(upload_padded(p.base + off_c[g], x.host, x.rows, d, dp, 4, p.s));
-        c = (const float *)(p.base + off_c[g]);
-      }
-      SH_RC(topk_f32_device_impl(L.route[g], (const float *)(p.base + p.off_q), dp, m, c, dp, x.rows, d, k, metric,
-                                 (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev,
-                                 x.host ? nullptr : x.dev_norms));
-    }
-    SH_TRY(hipEventRecord(ev[g], p.s));
-  }
-  // gather into the root (peer copies over xGMI), merge, download
-  SH_TRY(hipSetDevice(root));
-  char *gb = rp.base + off_gather;
-  for (int g = 0; g < G; g++) {
-    enable_peer(root, sh[g].dev);
-    SH_TRY(hipStreamWaitEvent(rp.s, ev[g], 0));
-    SH_TRY(hipMemcpyPeerAsync(gb + (size_t)g * list_bytes, root, dps[plan_of[g]].base + off_list[g], sh[g].dev,
-                              list_bytes, rp.s));
-  }
-  // (each shard's lists are a top-k output: best first)
-  uint32_t *oi = (uint32_t *)(rp.base + off_out);
-  const MergeArgs ma = merge_lists_args((const uint32_t *)gb, (const float *)((const uint32_t *)gb + (size_t)m * k), m,
-                                        G, k, k, 2 * m * k, k, metric, true, oi, (float *)(oi + (size_t)m * k));
-  {
-    Timed t("merge_devices", rp.s);
-    SH_TRY(launch_merge(ma, 1, rp.s));
-    // (the shards' zero scores carry their signs; the merge's keys fold them)
-    if (metric != kMetricEuclidean)
-      SH_TRY(launch_zero_sign_lists(ma.in_idx, ma.in_score, G, (int)k, k, 2 * m * k, (int)m, (int)k, ma.out_idx,
-                                    ma.out_score, rp.s));
-  }
-  SH_TRY(hipMemcpyAsync(out_idx, ma.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
-  SH_TRY(hipMemcpyAsync(out_score, ma.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
-  SH_TRY(hipStreamSynchronize(rp.s));
-  return finish(PMM_OK);
-}
-
-// ---------------------------------------------------------------------------
 // f64 top-k (src/matmul.rs:449-468 -> src/metrics.rs:258-311 + src/topk.rs:6-39)
 // on device rows of stride >= roundup(d, 16), zero-padded.  k <= kFusedMaxK:
 // the fused chunked scan of pmm_f64.hip (no M x N matrix); a row whose buffer
@@ -1966,18 +1712,49 @@ int topk_sharded(const float *q, int64_t m, int64_t d, int64_t k, int metric, in
 // fused limit: the materialised path (f64 GEMM store + row select), which also
 // serves as the PMM_F64_FUSED=0 reference.
 // ---------------------------------------------------------------------------
+// The schedule of a chunked scan (the f64 scan here, the int8 scan of
+// topk_i8_device_impl), stated once.  A row keeps a candidate buffer of `cap`
+// entries; a pass takes the `mc` query rows whose buffers fit the budget; the
+// first chunk of `s0` columns fills half a buffer (accept-all), later chunks
+// are g times the columns seen.  After `seen` columns the threshold is the
+// k-th best of them, so a chunk of g * seen columns from the same distribution
+// leaves ~g * X survivors in a row, X ~ Gamma(k) (the k-th order statistic's
+// quantile times seen).  Its spread is k^-1/2 of its mean whatever `seen` is,
+// so g is sized for the tail, not the mean: with
+// P(X > k + t) <= exp(-t^2 / (2 (k + t))) and t = 23 + sqrt(529 + 46 k)
+// (a per-row, per-chunk tail of e^-23 ~ 1e-10), g (k + t) <= cap - k keeps
+// every row inside its buffer.  (g = (cap/2 - k) / k, sized for the mean,
+// overflowed some row of nearly every call at 4096 x 1M: the whole call
+// then re-ran materialised, 257 vs 209 ms; profiles/r4_f64/.)  Adversarial
+// orders still overflow; each scan has its own fallback for them.
+constexpr size_t kF64CandBudget = size_t(1) << 30;
+struct ChunkSchedule {
+  int cap = 0;
+  int64_t mc = 0, s0 = 0, g = 1;
+};
+int chunk_cap(int64_t k) {
+  return std::min(4096, std::max(1024, next_pow2(4 * (int)std::min<int64_t>(k, kFusedMaxK) + 256)));
+}
+// cap: chunk_cap(k), or a smaller buffer a test asks for (PMM_I8_CAP)
+ChunkSchedule chunk_schedule(int64_t m, int64_t n, int64_t k, int cap) {
+  ChunkSchedule c;
+  c.cap = cap;
+  c.mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kF64CandBudget / ((size_t)cap * 16))));
+  c.s0 = std::min<int64_t>(n, cap / 2);
+  const double tail = 23.0 + std::sqrt(529.0 + 46.0 * (double)k);
+  c.g = std::max<int64_t>(1, (int64_t)((double)(cap - k) / ((double)k + tail)));
+  return c;
+}
+
 struct F64Plan {
-  int cap = 0, P = 0;
-  int64_t mc = 0;  // query rows per pass (candidate-buffer budget)
+  ChunkSchedule sched;
   size_t off_qn = 0, off_cn = 0, off_tkey = 0, off_tidx = 0, off_cnt = 0, off_cand = 0, off_flag = 0,
          off_mat = 0, total = 0;
 };
-constexpr size_t kF64CandBudget = size_t(1) << 30;
 
 void plan_f64(int64_t m, int64_t n, int64_t k, F64Plan &p) {
-  p.cap = std::min(4096, std::max(1024, next_pow2(4 * (int)std::min<int64_t>(k, kFusedMaxK) + 256)));
-  p.P = p.cap;
-  p.mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kF64CandBudget / ((size_t)p.cap * 16))));
+  p.sched = chunk_schedule(m, n, k, chunk_cap(k));
+  const int64_t mc = p.sched.mc;
   size_t off = 0;
   p.off_flag = off;
   off += 256;
@@ -1986,13 +1763,13 @@ void plan_f64(int64_t m, int64_t n, int64_t k, F64Plan &p) {
   p.off_cn = off;
   off = al256(off + (size_t)n * 8);
   p.off_tkey = off;
-  off = al256(off + (size_t)p.mc * 8);
+  off = al256(off + (size_t)mc * 8);
   p.off_tidx = off;
-  off = al256(off + (size_t)p.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   p.off_cnt = off;
-  off = al256(off + (size_t)p.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   p.off_cand = off;
-  off = al256(off + (size_t)p.mc * p.cap * 16);
+  off = al256(off + (size_t)mc * p.sched.cap * 16);
   p.total = off;
 }
 
@@ -2097,29 +1874,15 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
     if (cn_pre) cn = (double *)cn_pre;
     else HIP_TRY(launch_norms_f64(dc, n, d, ldc, sq, cn, s));
   }
-  // chunk schedule: the first chunk fills half a buffer (accept-all), later
-  // chunks are g times the columns seen.  After `seen` columns the threshold
-  // is the k-th best of them, so a chunk of g * seen columns from the same
-  // distribution leaves ~g * X survivors in a row, X ~ Gamma(k) (the k-th
-  // order statistic's quantile times seen).  Its spread is k^-1/2 of its mean
-  // whatever `seen` is, so g is sized for the tail, not the mean: with
-  // P(X > k + t) <= exp(-t^2 / (2 (k + t))) and t = 23 + sqrt(529 + 46 k)
-  // (a per-row, per-chunk tail of e^-23 ~ 1e-10), g (k + t) <= cap - k keeps
-  // every row inside its buffer.  (g = (cap/2 - k) / k, sized for the mean,
-  // overflowed some row of nearly every call at 4096 x 1M: the whole call
-  // then re-ran materialised, 257 vs 209 ms; profiles/r4_f64/.)  Adversarial
-  // orders still overflow and fall back below.
-  const int64_t s0 = std::min<int64_t>(n, p.cap / 2);
-  const double tail = 23.0 + std::sqrt(529.0 + 46.0 * (double)k);
-  const int64_t g = std::max<int64_t>(1, (int64_t)((double)(p.cap - k) / ((double)k + tail)));
+  const ChunkSchedule &sched = p.sched;  // (chunk_schedule; an overflowed call falls back below)
   HIP_TRY(hipMemsetAsync(flag, 0, 4, s));
-  for (int64_t r0 = 0; r0 < m; r0 += p.mc) {
-    const int rows = (int)std::min<int64_t>(p.mc, m - r0);
+  for (int64_t r0 = 0; r0 < m; r0 += sched.mc) {
+    const int rows = (int)std::min<int64_t>(sched.mc, m - r0);
     unsigned long long *tkey = (unsigned long long *)(w + p.off_tkey);
     uint32_t *tidx = (uint32_t *)(w + p.off_tidx);
     unsigned *cnt = (unsigned *)(w + p.off_cnt);
     Ent *cand = (Ent *)(w + p.off_cand);
-    HIP_TRY(launch_f64_reset(tkey, tidx, cnt, rows, (unsigned)s0, s));
+    HIP_TRY(launch_f64_reset(tkey, tidx, cnt, rows, (unsigned)sched.s0, s));
     F64TopkArgs a{};
     a.q = dq + r0 * ldq;
     a.c = dc;
@@ -2134,14 +1897,14 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
     a.tidx = tidx;
     a.cnt = cnt;
     a.cand = cand;
-    a.cap = p.cap;
+    a.cap = sched.cap;
     F64SelArgs sa{};
     sa.cand = cand;
     sa.cnt = cnt;
-    sa.cap = p.cap;
+    sa.cap = sched.cap;
     sa.M = rows;
     sa.k = (int)k;
-    sa.P = p.P;
+    sa.P = sched.cap;
     sa.tkey = tkey;
     sa.tidx = tidx;
     sa.metric = metric;
@@ -2149,7 +1912,7 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
     sa.out_idx = oi + r0 * k;
     sa.out_score = os + r0 * k;
     sa.overflow = flag;
-    int64_t seen = 0, chunk = s0;
+    int64_t seen = 0, chunk = sched.s0;
     while (seen < n) {
       const int64_t cc = std::min<int64_t>(chunk, n - seen);
       a.col0 = (int)seen;
@@ -2165,7 +1928,7 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
         Timed t("select_f64", s);
         HIP_TRY(launch_f64_select(sa, s));
       }
-      chunk = seen * g;
+      chunk = seen * sched.g;
     }
   }
   // the sign of zero scores (an overflowed call's lists are redone below, with theirs)
@@ -2183,185 +1946,422 @@ int topk_f64_device_impl(const double *dq, int64_t ldq, int64_t m, const double 
 }
 
 // ---------------------------------------------------------------------------
-// Corpus-sharded f64 top-k (the drop-in path of Polars' default Float64
-// columns under pmm_set_devices): the f32 path's plan (topk_sharded) with the
-// f64 top-k per shard.  Every device gets the queries once; each shard runs
-// topk_f64_device_impl on its rows with index_base = its first global row,
-// k_g = min(k, rows) (a shorter list is padded with empty slots); the fused
-// scans' overflow flags are read only after every device has finished (an
-// overflowed shard re-runs materialised, as one device would); the [m][k]
-// lists meet in the root's [G][m][k] planes by peer copies and
-// f64_kway_merge_kernel merges them.  A shard's list is the exact top-k of
-// its rows under the f64 total order, so the merged list equals the
-// one-device result bit for bit (indices and f64 scores).
+// Corpus-sharded top-k over several devices from ONE host thread (the
+// drop-in boundary's multi-GPU path; pmm_set_devices), for f32 rows, bf16
+// compute and f64 rows (Polars' default Float64 columns): one memory plan
+// (plan_sharded) and one driver (topk_sharded).  SURVEY 8e's plan in one
+// process: the corpus is row-sharded (contiguous, sizes differ by <= 1), every
+// device gets the queries and searches its shard with index_base = the shard's
+// first global row, the shards' m x k lists are copied peer-to-peer (xGMI)
+// into the root device's gather buffer and k-way merged there.  All devices
+// work concurrently: every launch is asynchronous on the device's own stream
+// of this thread; the root waits on per-shard events.  Each shard's list is
+// the exact top-k of its rows under the row type's total order, so the merged
+// list equals the one-device result bit for bit.
 // ---------------------------------------------------------------------------
-int topk_sharded_f64(const double *q, int64_t m, int64_t d, int64_t k, int metric, const std::vector<ShardSrc64> &sh,
-                     uint32_t *out_idx, double *out_score) {
-  const int G = (int)sh.size();
-  DevScope restore;
-  HIP_TRY(hipGetDevice(&restore.prev));
-  const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
-  const int root = sh[0].dev;
-  for (const ShardSrc64 &x : sh)
-    if (int rc = probe_device(x.dev)) return rc;
-  struct Dev64 {
-    int dev;
-    hipStream_t s = nullptr;
-    char *base = nullptr;
-    size_t off_q = 0, off_ws = 0, ws_bytes = 0, off_flags = 0, total = 0;
-  };
-  std::vector<Dev64> dps;
-  const std::vector<int> plan_of = distinct_devices(sh, dps);
-  std::vector<int> slot(G);
-  std::vector<int64_t> kg(G);
-  std::vector<bool> fused(G);
-  std::vector<size_t> off_c(G), off_tmp(G), off_tmps(G), off_li(G), off_ls(G);
+// One shard.  The rows and norms are of the search's row type: f32, f64, or
+// bf16 rows with f32 norms under bf16 compute.
+struct ShardSrc {
+  int dev;
+  int64_t lo, rows;
+  const void *host;       // host corpus rows [lo, lo + rows), row stride d (f32 for bf16 compute), or
+  const void *dev_rows;   // a corpus handle's resident rows at their padded stride
+  const void *dev_norms;  // with dev_rows: the handle's norm array of this metric (nullptr for dot)
+};
+
+// The shards of n host rows (row stride d, elements of `elem` bytes) over a
+// device list: one per listed device, at most n, contiguous, sizes differing by
+// at most one.
+int64_t shard_lo(int64_t n, int G, int g) { return n * g / G; }  // shard g: rows [n g / G, n (g + 1) / G)
+std::vector<ShardSrc> host_shards(const std::vector<int> &devs, const void *c, int64_t n, int64_t d, size_t elem) {
+  const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
+  std::vector<ShardSrc> sh(G);
   for (int g = 0; g < G; g++) {
-    kg[g] = std::min<int64_t>(k, sh[g].rows);
-    fused[g] = f64_use_fused(m, sh[g].rows, kg[g]);
+    const int64_t lo = shard_lo(n, G, g), hi = shard_lo(n, G, g + 1);
+    sh[g] = ShardSrc{devs[g], lo, hi - lo, (const char *)c + (size_t)lo * d * elem, nullptr, nullptr};
   }
-  for (int j = 0; j < (int)dps.size(); j++) {
-    Dev64 &p = dps[j];
+  return sh;
+}
+
+std::mutex g_peer_mu;
+bool g_peer_tried[kMaxDevices][kMaxDevices];
+
+// Lets `dev` read `peer`'s memory directly (xGMI) when the platform allows;
+// a peer copy works either way, so failures are ignored.
+void enable_peer(int dev, int peer) {
+  if (dev == peer) return;
+  std::lock_guard<std::mutex> lk(g_peer_mu);
+  if (g_peer_tried[dev][peer]) return;
+  g_peer_tried[dev][peer] = true;
+  int can = 0;
+  if (hipDeviceCanAccessPeer(&can, dev, peer) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(peer, 0);
+  (void)hipGetLastError();
+}
+
+// What differs between the row types.
+struct ShardRows {
+  int dtype;                     // PMM_DTYPE_F32, _BF16 (f32 host rows and queries, searched as bf16) or _F64
+  size_t host_elem, score_elem;  // bytes of a host row (and query) element, of a score
+  // bf16: host rows and queries go up unpadded as f32 (staging rows of stride
+  // d) and are rounded into a second, padded copy, which the kernels read
+  bool staged;
+  // f64: a shard is searched for k_g = min(k, rows) entries (a shorter list is
+  // written compact, then laid behind empty slots: idx 0xFFFFFFFF, score NaN);
+  // its fused scan's overflow flag has a slot in its device's plan, read once
+  // every device has finished; a list's index and score planes are aligned
+  // separately (f64_kway_merge_kernel).  f32, bf16: the kernels pad a short
+  // list themselves, nothing is deferred, a list is one [2][m][k] block
+  // (merge_kernel's strided loader, as for RCCL-gathered lists).
+  bool f64;
+};
+ShardRows shard_rows(int dtype) {
+  if (dtype == PMM_DTYPE_F64) return ShardRows{dtype, 8, 8, false, true};
+  return ShardRows{dtype, 4, 4, dtype == PMM_DTYPE_BF16, false};
+}
+
+// Memory plan (pure: no HIP call, so the CPU tests check it through
+// pmm_shard_plan).  One DevPlan per DISTINCT device of the list, in order of
+// first use: that device's queries once, one workspace (its shards run in
+// stream order), and per shard (ShardSlot) the uploaded rows (host shards only)
+// and its lists; the root plan (the first shard's device) also holds the
+// gathered lists of all G shards and the merged output.
+struct DevPlan {
+  int dev = 0;
+  hipStream_t s = nullptr;
+  char *base = nullptr;
+  size_t off_q = 0, off_qb = 0, off_flags = 0, off_ws = 0, ws_bytes = 0, total = 0;
+};
+struct ShardSlot {
+  int64_t k = 0;       // entries the shard is searched for (ShardRows::f64)
+  bool fused = false;  // f64: the fused scan, whose flag is word `slot` at off_flags
+  int slot = 0;        // the shard's place among its device's shards
+  TopkRoute route;     // f32, bf16 (never screened)
+  size_t off_c = 0, off_cb = 0;  // uploaded rows; bf16: their rounded copy
+  size_t off_ti = 0, off_ts = 0, off_li = 0, off_ls = 0;  // the compact list of a short f64 shard; the m x k list
+};
+struct ShardLayout {
+  ShardRows rt;
+  int64_t m = 0, d = 0, dp = 0, k = 0;
+  int metric = 0;
+  std::vector<DevPlan> dps;
+  std::vector<int> plan_of;  // shard -> index into dps
+  std::vector<ShardSlot> sl;
+  // in the root plan: shard g's gathered planes at off_gi / off_gs + g * gstride entries, the output planes
+  size_t off_gi = 0, off_gs = 0, gstride = 0, off_oi = 0, off_os = 0;
+};
+
+void plan_sharded(int dtype, const std::vector<ShardSrc> &sh, int64_t m, int64_t d, int64_t k, int metric,
+                  ShardLayout &L) {
+  const int G = (int)sh.size();
+  const ShardRows rt = shard_rows(dtype);
+  const int64_t dp = padded_dim(dtype, d);
+  const size_t mk = (size_t)m * k;
+  L = ShardLayout{rt, m, d, dp, k, metric};
+  L.plan_of.resize(G);
+  L.sl.assign(G, ShardSlot());
+  for (int g = 0; g < G; g++) {
+    int j = 0;
+    while (j < (int)L.dps.size() && L.dps[j].dev != sh[g].dev) j++;
+    if (j == (int)L.dps.size()) {
+      L.dps.push_back(DevPlan());
+      L.dps[j].dev = sh[g].dev;
+    }
+    L.plan_of[g] = j;
+  }
+  // an index plane and a score plane of `count` entries each, from off on
+  auto planes = [&](size_t &off, size_t count, size_t &oi, size_t &os) {
+    oi = off;
+    os = rt.f64 ? al256(off + count * 4) : off + count * 4;
+    off = al256(os + count * rt.score_elem);
+  };
+  const size_t up_row = (size_t)(rt.staged ? d : dp) * rt.host_elem, rounded_row = rt.staged ? (size_t)dp * 2 : 0;
+  for (int j = 0; j < (int)L.dps.size(); j++) {
+    DevPlan &p = L.dps[j];
     size_t off = 0;
     p.off_q = off;
-    off = al256(off + (size_t)m * dp * 8);
+    off = al256(off + (size_t)m * up_row);
+    p.off_qb = off;
+    off = al256(off + (size_t)m * rounded_row);
     int ns = 0;
     for (int g = 0; g < G; g++) {
-      if (plan_of[g] != j) continue;
-      slot[g] = ns++;
-      p.ws_bytes = std::max(p.ws_bytes, f64_workspace_bytes(m, sh[g].rows, kg[g], fused[g]));
-      off_c[g] = off;
-      if (sh[g].host) off = al256(off + (size_t)sh[g].rows * dp * 8);
-      // (a short shard's compact list: index and score halves, each at an
-      // aligned offset of its own -- m * kg may be odd)
-      off_tmp[g] = off;
-      if (kg[g] < k) off = al256(off + (size_t)m * kg[g] * 4);
-      off_tmps[g] = off;
-      if (kg[g] < k) off = al256(off + (size_t)m * kg[g] * 8);
-      off_li[g] = off;
-      off = al256(off + (size_t)m * k * 4);
-      off_ls[g] = off;
-      off = al256(off + (size_t)m * k * 8);
+      if (L.plan_of[g] != j) continue;
+      ShardSlot &t = L.sl[g];
+      const int64_t rows = sh[g].rows;
+      t.slot = ns++;
+      t.k = rt.f64 ? std::min<int64_t>(k, rows) : k;
+      if (rt.f64) {
+        t.fused = f64_use_fused(m, rows, t.k);
+        p.ws_bytes = std::max(p.ws_bytes, f64_workspace_bytes(m, rows, t.k, t.fused));
+      } else {
+        t.route = route_topk(m, rows, d, k, metric, rt.staged ? PMM_COMPUTE_BF16 : PMM_COMPUTE_F32,
+                             device_cus(p.dev), false, true);
+        p.ws_bytes = std::max(p.ws_bytes, t.route.total);
+      }
+      t.off_c = off;
+      if (sh[g].host) off = al256(off + (size_t)rows * up_row);
+      t.off_cb = off;
+      if (sh[g].host) off = al256(off + (size_t)rows * rounded_row);  // (resident: the handle's rows)
+      t.off_ti = t.off_ts = off;
+      if (t.k < k) planes(off, (size_t)m * t.k, t.off_ti, t.off_ts);
+      planes(off, mk, t.off_li, t.off_ls);
     }
     p.off_flags = off;
-    off = al256(off + (size_t)ns * 4);
+    if (rt.f64) off = al256(off + (size_t)ns * 4);
     p.off_ws = off;
     off = al256(off + p.ws_bytes);
     p.total = off;
   }
-  Dev64 &rp = dps[plan_of[0]];
-  const size_t off_gi = rp.total, off_gs = al256(off_gi + (size_t)G * m * k * 4);
-  const size_t off_oi = al256(off_gs + (size_t)G * m * k * 8), off_os = al256(off_oi + (size_t)m * k * 4);
-  rp.total = al256(off_os + (size_t)m * k * 8);
+  DevPlan &rp = L.dps[L.plan_of[0]];
+  size_t off = rp.total;
+  L.off_gi = off;
+  if (rt.f64) {  // [G][m][k] index plane, [G][m][k] score plane
+    L.gstride = mk;
+    L.off_gs = al256(off + (size_t)G * mk * 4);
+    off = al256(L.off_gs + (size_t)G * mk * 8);
+  } else {  // [G][2][m][k]
+    L.gstride = 2 * mk;
+    L.off_gs = off + mk * 4;
+    off = al256(off + (size_t)G * 2 * mk * 4);
+  }
+  planes(off, mk, L.off_oi, L.off_os);
+  rp.total = off;
+}
+
+// Every planned device's stream of this thread and an arena of its plan's size.
+int acquire_devices(std::vector<DevPlan> &dps) {
+  for (auto &p : dps) {
+    HIP_TRY(hipSetDevice(p.dev));
+    if (int rc = thread_stream(p.dev, &p.s)) return rc;
+    void *b;
+    if (int rc = arena(p.dev, p.s, p.total, &b)) return rc;
+    p.base = (char *)b;
+  }
+  return PMM_OK;
+}
+
+// The per-shard completion events of a sharded search and its one exit: a
+// failure first drains every device's stream (queued work writes into the
+// arenas), then the events are destroyed on their devices.
+struct ShardedExit {
+  std::vector<DevPlan> &dps;
+  const std::vector<ShardSrc> &sh;
+  std::vector<hipEvent_t> ev;
+  ShardedExit(std::vector<DevPlan> &dps_, const std::vector<ShardSrc> &sh_) : dps(dps_), sh(sh_), ev(sh_.size(), nullptr) {}
+  int operator()(int code) {
+    if (code != PMM_OK)
+      for (auto &p : dps) {
+        (void)hipSetDevice(p.dev);
+        (void)hipStreamSynchronize(p.s);
+      }
+    for (size_t g = 0; g < ev.size(); g++)
+      if (ev[g]) {
+        (void)hipSetDevice(sh[g].dev);
+        (void)hipEventDestroy(ev[g]);
+      }
+    return code;
+  }
+};
+
+// What a row type supplies to the driver, each on the shard's device (current)
+// and stream.  f32 and bf16 compute: shard g's host rows to the device and its
+// fused top-k with global indices.
+int search_shard_f32(const ShardLayout &L, int g, const ShardSrc &x) {
+  const DevPlan &p = L.dps[L.plan_of[g]];
+  const ShardSlot &t = L.sl[g];
+  const int64_t m = L.m, d = L.d, dp = L.dp;
+  uint32_t *li = (uint32_t *)(p.base + t.off_li);
+  float *ls = (float *)(p.base + t.off_ls);
+  // (a resident shard brings its norms; the query norms are this call's)
+  const float *cn = x.host ? nullptr : (const float *)x.dev_norms;
+  if (L.rt.staged) {
+    const uint16_t *cb = (const uint16_t *)x.dev_rows;
+    if (x.host) {
+      HIP_TRY(hipMemcpyAsync(p.base + t.off_c, x.host, (size_t)x.rows * d * 4, hipMemcpyHostToDevice, p.s));
+      HIP_TRY(launch_f32_to_bf16((const float *)(p.base + t.off_c), x.rows, d, d, (uint16_t *)(p.base + t.off_cb), dp,
+                                 p.s));
+      cb = (const uint16_t *)(p.base + t.off_cb);
+    }
+    return topk_bf16_device_impl(t.route, (const uint16_t *)(p.base + p.off_qb), dp, m, cb, dp, x.rows, d, L.k,
+                                 L.metric, (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev, nullptr,
+                                 cn);
+  }
+  const float *c = (const float *)x.dev_rows;
+  if (x.host) {
+    if (int rc = upload_padded(p.base + t.off_c, x.host, x.rows, d, dp, 4, p.s)) return rc;
+    c = (const float *)(p.base + t.off_c);
+  }
+  return topk_f32_device_impl(t.route, (const float *)(p.base + p.off_q), dp, m, c, dp, x.rows, d, L.k, L.metric,
+                              (uint32_t)x.lo, li, ls, p.base + p.off_ws, p.ws_bytes, p.s, p.dev, cn);
+}
+
+// f64: the same with topk_f64_device_impl, which copies the fused scan's
+// overflow flag into the shard's slot instead of waiting for it.  rerun: the
+// shard again on the materialised path (its rows are on the device already).
+int search_shard_f64(const ShardLayout &L, int g, const ShardSrc &x, bool rerun) {
+  const DevPlan &p = L.dps[L.plan_of[g]];
+  const ShardSlot &t = L.sl[g];
+  const int64_t m = L.m, d = L.d, dp = L.dp, k = L.k;
+  const double *q = (const double *)(p.base + p.off_q), *cn = (const double *)x.dev_norms;
+  const double *c = x.host ? (const double *)(p.base + t.off_c) : (const double *)x.dev_rows;
+  unsigned *flag = (unsigned *)(p.base + p.off_flags) + t.slot;
+  if (!rerun) {
+    if (x.host)
+      if (int rc = upload_padded(p.base + t.off_c, x.host, x.rows, d, dp, 8, p.s)) return rc;
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, p.s));
+  }
+  uint32_t *li = (uint32_t *)(p.base + t.off_li), *oi = li;
+  double *ls = (double *)(p.base + t.off_ls), *os = ls;
+  if (t.k < k) {
+    oi = (uint32_t *)(p.base + t.off_ti);
+    os = (double *)(p.base + t.off_ts);
+    HIP_TRY(hipMemsetAsync(li, 0xFF, (size_t)m * k * 4, p.s));
+    HIP_TRY(hipMemsetAsync(ls, 0xFF, (size_t)m * k * 8, p.s));  // (all-ones f64: a NaN)
+  }
+  const int rc = rerun ? topk_f64_materialised(q, dp, m, c, dp, x.rows, d, t.k, L.metric, (uint32_t)x.lo, oi, os,
+                                               p.base + p.off_ws, p.s, cn)
+                       : topk_f64_device_impl(q, dp, m, c, dp, x.rows, d, t.k, L.metric, (uint32_t)x.lo, oi, os,
+                                              p.base + p.off_ws, p.s, t.fused, cn, t.fused ? flag : nullptr);
+  if (rc) return rc;
+  if (t.k < k) {
+    HIP_TRY(hipMemcpy2DAsync(li, (size_t)k * 4, oi, (size_t)t.k * 4, (size_t)t.k * 4, (size_t)m,
+                             hipMemcpyDeviceToDevice, p.s));
+    HIP_TRY(hipMemcpy2DAsync(ls, (size_t)k * 8, os, (size_t)t.k * 8, (size_t)t.k * 8, (size_t)m,
+                             hipMemcpyDeviceToDevice, p.s));
+  }
+  return PMM_OK;
+}
+
+// f64, once every device has finished: an overflowed shard re-runs
+// materialised (its rows, its workspace), as one device would.
+int rerun_overflowed_f64(const ShardLayout &L, int g, const ShardSrc &x) {
+  const DevPlan &p = L.dps[L.plan_of[g]];
+  if (!L.sl[g].fused) return PMM_OK;
+  unsigned of = 0;
+  HIP_TRY(hipMemcpy(&of, (unsigned *)(p.base + p.off_flags) + L.sl[g].slot, 4, hipMemcpyDeviceToHost));
+  return of ? search_shard_f64(L, g, x, true) : PMM_OK;
+}
+
+// The root's k-way merge of the G gathered lists (each best first) into the
+// output planes, on the root's stream.
+int merge_shards(const ShardLayout &L, int G, const DevPlan &rp) {
+  const int64_t m = L.m, k = L.k;
+  uint32_t *gi = (uint32_t *)(rp.base + L.off_gi), *oi = (uint32_t *)(rp.base + L.off_oi);
+  if (L.rt.f64) {
+    F64MergeArgs ma{};
+    ma.gi = gi;
+    ma.gs = (double *)(rp.base + L.off_gs);
+    ma.list_stride = m * k;
+    ma.M = (int)m;
+    ma.G = G;
+    ma.k = (int)k;
+    ma.metric = L.metric;
+    ma.out_idx = oi;
+    ma.out_score = (double *)(rp.base + L.off_os);
+    Timed t("merge_devices_f64", rp.s);
+    HIP_TRY(launch_f64_merge(ma, rp.s));
+    return PMM_OK;
+  }
+  const MergeArgs ma = merge_lists_args(gi, (const float *)(rp.base + L.off_gs), m, G, k, k, 2 * m * k, k, L.metric,
+                                        true, oi, (float *)(rp.base + L.off_os));
+  Timed t("merge_devices", rp.s);
+  HIP_TRY(launch_merge(ma, 1, rp.s));
+  // (the shards' zero scores carry their signs; the merge's keys fold them)
+  if (L.metric != kMetricEuclidean)
+    HIP_TRY(launch_zero_sign_lists(ma.in_idx, ma.in_score, G, (int)k, k, 2 * m * k, (int)m, (int)k, ma.out_idx,
+                                   ma.out_score, rp.s));
+  return PMM_OK;
+}
+
+// The driver.  q, out_score: f32 (dtype f32, bf16) or f64.
+int topk_sharded(int dtype, const void *q, int64_t m, int64_t d, int64_t k, int metric, const std::vector<ShardSrc> &sh,
+                 uint32_t *out_idx, void *out_score) {
+  const int G = (int)sh.size();
+  DevScope restore;
+  HIP_TRY(hipGetDevice(&restore.prev));
+  const int root = sh[0].dev;
+  for (const ShardSrc &x : sh)
+    if (int rc = probe_device(x.dev)) return rc;
+  ShardLayout L;
+  plan_sharded(dtype, sh, m, d, k, metric, L);
+  const ShardRows &rt = L.rt;
+  std::vector<DevPlan> &dps = L.dps;
+  DevPlan &rp = dps[L.plan_of[0]];
   if (int rc = acquire_devices(dps)) return rc;
-  ShardedExit<Dev64, double> finish(dps, sh);
-  std::vector<hipEvent_t> &ev = finish.ev;
+  ShardedExit finish(dps, sh);
+#define SH_TRY(expr)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return finish(fail(PMM_ERR_HIP, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), \
+                         __FILE__, __LINE__, #expr));                                     \
+  } while (0)
+#define SH_RC(expr)                        \
+  do {                                     \
+    int rc_ = (expr);                      \
+    if (rc_ != PMM_OK) return finish(rc_); \
+  } while (0)
+  // queries to every device
   for (auto &p : dps) {
     SH_TRY(hipSetDevice(p.dev));
-    SH_RC(upload_padded(p.base + p.off_q, q, m, d, dp, 8, p.s));
+    if (rt.staged) {
+      SH_TRY(hipMemcpyAsync(p.base + p.off_q, q, (size_t)m * d * 4, hipMemcpyHostToDevice, p.s));
+      SH_TRY(launch_f32_to_bf16((const float *)(p.base + p.off_q), m, d, d, (uint16_t *)(p.base + p.off_qb), L.dp,
+                                p.s));
+    } else {
+      SH_RC(upload_padded(p.base + p.off_q, q, m, d, L.dp, rt.host_elem, p.s));
+    }
   }
-  // per shard: rows, f64 top-k with global indices (every device at once:
-  // the overflow flags are copied, not waited for)
-  auto run_shard = [&](int g, bool materialised) -> int {
-    Dev64 &p = dps[plan_of[g]];
-    const ShardSrc64 &x = sh[g];
-    const double *c = (const double *)x.dev_rows;
-    if (x.host) c = (const double *)(p.base + off_c[g]);
-    uint32_t *li = (uint32_t *)(p.base + off_li[g]);
-    double *ls = (double *)(p.base + off_ls[g]);
-    uint32_t *oi = li;
-    double *os = ls;
-    if (kg[g] < k) {
-      // a shard shorter than k: its kg best into a compact list, then into
-      // the [m][k] rows behind empty slots (idx 0xFFFFFFFF, score NaN)
-      oi = (uint32_t *)(p.base + off_tmp[g]);
-      os = (double *)(p.base + off_tmps[g]);
-      HIP_TRY(hipMemsetAsync(li, 0xFF, (size_t)m * k * 4, p.s));
-      HIP_TRY(hipMemsetAsync(ls, 0xFF, (size_t)m * k * 8, p.s));  // (all-ones f64: a NaN)
-    }
-    unsigned *flag = (unsigned *)(p.base + p.off_flags) + slot[g];
-    int rc = materialised ? topk_f64_materialised((const double *)(p.base + p.off_q), dp, m, c, dp, x.rows, d,
-                                                  kg[g], metric, (uint32_t)x.lo, oi, os, p.base + p.off_ws, p.s,
-                                                  x.dev_norms)
-                          : topk_f64_device_impl((const double *)(p.base + p.off_q), dp, m, c, dp, x.rows, d, kg[g],
-                                                 metric, (uint32_t)x.lo, oi, os, p.base + p.off_ws, p.s, fused[g],
-                                                 x.dev_norms, fused[g] ? flag : nullptr);
-    if (rc) return rc;
-    if (kg[g] < k) {
-      HIP_TRY(hipMemcpy2DAsync(li, (size_t)k * 4, oi, (size_t)kg[g] * 4, (size_t)kg[g] * 4, (size_t)m,
-                               hipMemcpyDeviceToDevice, p.s));
-      HIP_TRY(hipMemcpy2DAsync(ls, (size_t)k * 8, os, (size_t)kg[g] * 8, (size_t)kg[g] * 8, (size_t)m,
-                               hipMemcpyDeviceToDevice, p.s));
-    }
+  // per shard: rows, top-k with global indices, completion event.  All devices
+  // work concurrently: every launch is asynchronous on the device's own stream
+  // of this thread.  f64 defers the events behind the overflow flags, which are
+  // read only once every device is done.
+  auto record = [&](int g) -> int {
+    HIP_TRY(hipEventCreateWithFlags(&finish.ev[g], hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(finish.ev[g], dps[L.plan_of[g]].s));
     return PMM_OK;
   };
   for (int g = 0; g < G; g++) {
-    Dev64 &p = dps[plan_of[g]];
-    SH_TRY(hipSetDevice(p.dev));
-    if (sh[g].host) SH_RC(upload_padded(p.base + off_c[g], sh[g].host, sh[g].rows, d, dp, 8, p.s));
-    SH_TRY(hipMemsetAsync((unsigned *)(p.base + p.off_flags) + slot[g], 0, 4, p.s));
-    SH_RC(run_shard(g, false));
+    SH_TRY(hipSetDevice(sh[g].dev));
+    SH_RC(rt.f64 ? search_shard_f64(L, g, sh[g], false) : search_shard_f32(L, g, sh[g]));
+    if (!rt.f64) SH_RC(record(g));
   }
-  // overflow flags, once every device is done: an overflowed shard re-runs
-  // on the materialised path (its rows, its workspace)
-  for (auto &p : dps) {
-    SH_TRY(hipSetDevice(p.dev));
-    SH_TRY(hipStreamSynchronize(p.s));
-  }
-  for (int g = 0; g < G; g++) {
-    Dev64 &p = dps[plan_of[g]];
-    SH_TRY(hipSetDevice(p.dev));
-    if (fused[g]) {
-      unsigned of = 0;
-      SH_TRY(hipMemcpy(&of, (unsigned *)(p.base + p.off_flags) + slot[g], 4, hipMemcpyDeviceToHost));
-      if (of) SH_RC(run_shard(g, true));
+  if (rt.f64) {
+    for (auto &p : dps) {
+      SH_TRY(hipSetDevice(p.dev));
+      SH_TRY(hipStreamSynchronize(p.s));
     }
-    SH_TRY(hipEventCreateWithFlags(&ev[g], hipEventDisableTiming));
-    SH_TRY(hipEventRecord(ev[g], p.s));
+    for (int g = 0; g < G; g++) {
+      SH_TRY(hipSetDevice(sh[g].dev));
+      SH_RC(rerun_overflowed_f64(L, g, sh[g]));
+      SH_RC(record(g));
+    }
   }
-  // gather into the root (peer copies over xGMI), merge, download
+  // gather into the root (peer copies over xGMI; the root waits on the shards'
+  // events), merge, download
   SH_TRY(hipSetDevice(root));
-  uint32_t *gi = (uint32_t *)(rp.base + off_gi);
-  double *gs = (double *)(rp.base + off_gs);
+  const size_t mk = (size_t)m * k;
   for (int g = 0; g < G; g++) {
     enable_peer(root, sh[g].dev);
-    SH_TRY(hipStreamWaitEvent(rp.s, ev[g], 0));
-    const char *pb = dps[plan_of[g]].base;
-    SH_TRY(hipMemcpyPeerAsync(gi + (size_t)g * m * k, root, pb + off_li[g], sh[g].dev, (size_t)m * k * 4, rp.s));
-    SH_TRY(hipMemcpyPeerAsync(gs + (size_t)g * m * k, root, pb + off_ls[g], sh[g].dev, (size_t)m * k * 8, rp.s));
+    SH_TRY(hipStreamWaitEvent(rp.s, finish.ev[g], 0));
+    const char *pb = dps[L.plan_of[g]].base;
+    char *di = rp.base + L.off_gi + (size_t)g * L.gstride * 4;
+    if (rt.f64) {
+      SH_TRY(hipMemcpyPeerAsync(di, root, pb + L.sl[g].off_li, sh[g].dev, mk * 4, rp.s));
+      SH_TRY(hipMemcpyPeerAsync(rp.base + L.off_gs + (size_t)g * L.gstride * 8, root, pb + L.sl[g].off_ls, sh[g].dev,
+                                mk * 8, rp.s));
+    } else {  // (a [2][m][k] block at both ends: one copy)
+      SH_TRY(hipMemcpyPeerAsync(di, root, pb + L.sl[g].off_li, sh[g].dev, 2 * mk * 4, rp.s));
+    }
   }
-  F64MergeArgs ma{};
-  ma.gi = gi;
-  ma.gs = gs;
-  ma.list_stride = m * k;
-  ma.M = (int)m;
-  ma.G = G;
-  ma.k = (int)k;
-  ma.metric = metric;
-  ma.out_idx = (uint32_t *)(rp.base + off_oi);
-  ma.out_score = (double *)(rp.base + off_os);
-  {
-    Timed t("merge_devices_f64", rp.s);
-    SH_TRY(launch_f64_merge(ma, rp.s));
-  }
-  SH_TRY(hipMemcpyAsync(out_idx, ma.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, rp.s));
-  SH_TRY(hipMemcpyAsync(out_score, ma.out_score, (size_t)m * k * 8, hipMemcpyDeviceToHost, rp.s));
+  SH_RC(merge_shards(L, G, rp));
+  SH_TRY(hipMemcpyAsync(out_idx, rp.base + L.off_oi, mk * 4, hipMemcpyDeviceToHost, rp.s));
+  SH_TRY(hipMemcpyAsync(out_score, rp.base + L.off_os, mk * rt.score_elem, hipMemcpyDeviceToHost, rp.s));
   SH_TRY(hipStreamSynchronize(rp.s));
-  return finish(PMM_OK);
-}
 #undef SH_TRY
 #undef SH_RC
-
-std::vector<int> devices_snapshot() {
-  std::lock_guard<std::mutex> lk(g_devs_mu);
-  return g_devs;
+  return finish(PMM_OK);
 }
 
-// The device host entry points run on when a device list is set: its first
-// entry (the root, which also merges a sharded search), else -1 (the thread's
-// pmm_set_device choice or the current device).  A one-entry list therefore
-// moves all host work to that device; work that is not sharded (f32 k > 1024,
-// .pmm.matmul) runs on the root of a longer list.
 // ---------------------------------------------------------------------------
 // int8 top-k (pmm_i8.hip; DESIGN.md §4d "Int8 rows"): the f64 branch's answer for rows of
 // signed bytes -- indices and f64 score bits -- from the int8 MFMA.  One route
@@ -2375,8 +2375,7 @@ std::vector<int> devices_snapshot() {
 // ---------------------------------------------------------------------------
 struct I8Route {
   bool native = false;
-  int cap = 0;
-  int64_t mc = 0;  // query rows per pass (candidate-buffer budget)
+  ChunkSchedule sched;  // native
   size_t off_count = 0, off_qs = 0, off_qf = 0, off_cs = 0, off_cf = 0, off_tkey = 0, off_tidx = 0, off_cnt = 0,
          off_ovf = 0, off_rows = 0, off_cand = 0;
   bool fused64 = false;  // widened: the f64 path's own route
@@ -2385,11 +2384,11 @@ struct I8Route {
   size_t total = 0;
 };
 
-// The candidate-buffer capacity: the f64 scan's rule.  PMM_I8_CAP (per call;
-// a power of two from 64 up, below the rule's value) lowers it, so that a test
+// The candidate-buffer capacity: chunk_cap's, which PMM_I8_CAP (per call; a
+// power of two from 64 up, below the rule's value) lowers, so that a test
 // reaches the overflow re-run with a small corpus.
 int i8_cap(int64_t k) {
-  const int cap = std::min(4096, std::max(1024, next_pow2(4 * (int)std::min<int64_t>(k, kFusedMaxK) + 256)));
+  const int cap = chunk_cap(k);
   const char *e = getenv("PMM_I8_CAP");
   const int v = e ? atoi(e) : 0;
   return (v >= 64 && v < cap && (v & (v - 1)) == 0) ? v : cap;
@@ -2411,8 +2410,8 @@ I8Route route_i8(int64_t m, int64_t n, int64_t d, int64_t k) {
     r.total = off + f64_workspace_bytes(m, n, k, r.fused64);
     return r;
   }
-  r.cap = i8_cap(k);
-  r.mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kF64CandBudget / ((size_t)r.cap * 16))));
+  r.sched = chunk_schedule(m, n, k, i8_cap(k));
+  const int64_t mc = r.sched.mc;
   r.off_count = off;
   off += 256;
   r.off_qs = off;
@@ -2424,17 +2423,17 @@ I8Route route_i8(int64_t m, int64_t n, int64_t d, int64_t k) {
   r.off_cf = off;
   off = al256(off + (size_t)n * 4);
   r.off_tkey = off;
-  off = al256(off + (size_t)r.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   r.off_tidx = off;
-  off = al256(off + (size_t)r.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   r.off_cnt = off;
-  off = al256(off + (size_t)r.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   r.off_ovf = off;
-  off = al256(off + (size_t)r.mc * 4);
+  off = al256(off + (size_t)mc * 4);
   r.off_rows = off;
   off = al256(off + (size_t)m * 4);
   r.off_cand = off;
-  off = al256(off + (size_t)r.mc * r.cap * 16);
+  off = al256(off + (size_t)mc * r.sched.cap * 16);
   r.total = off;
   return r;
 }
@@ -2506,13 +2505,9 @@ int topk_i8_device_impl(const I8Route &r, const int8_t *dq, int64_t ldq, int64_t
       HIP_TRY(launch_i8_norms(dc, n, ldc, (int)dp, cs, cf, s));
     }
   }
-  // the f64 scan's chunk schedule (topk_f64_device_impl): the first chunk
-  // half a buffer, later ones g times the columns seen, g sized for the tail
-  const int64_t s0 = std::min<int64_t>(n, r.cap / 2);
-  const double tail = 23.0 + std::sqrt(529.0 + 46.0 * (double)k);
-  const int64_t g = std::max<int64_t>(1, (int64_t)((double)(r.cap - k) / ((double)k + tail)));
-  for (int64_t r0 = 0; r0 < m; r0 += r.mc) {
-    const int rws = (int)std::min<int64_t>(r.mc, m - r0);
+  const ChunkSchedule &sched = r.sched;
+  for (int64_t r0 = 0; r0 < m; r0 += sched.mc) {
+    const int rws = (int)std::min<int64_t>(sched.mc, m - r0);
     uint32_t *tkey = (uint32_t *)(w + r.off_tkey), *tidx = (uint32_t *)(w + r.off_tidx);
     unsigned *cnt = (unsigned *)(w + r.off_cnt), *ovf = (unsigned *)(w + r.off_ovf);
     Ent *cand = (Ent *)(w + r.off_cand);
@@ -2533,14 +2528,14 @@ int topk_i8_device_impl(const I8Route &r, const int8_t *dq, int64_t ldq, int64_t
     a.tidx = tidx;
     a.cnt = cnt;
     a.cand = cand;
-    a.cap = r.cap;
+    a.cap = sched.cap;
     I8SelArgs sa{};
     sa.cand = cand;
     sa.cnt = cnt;
-    sa.cap = r.cap;
+    sa.cap = sched.cap;
     sa.M = rws;
     sa.k = (int)k;
-    sa.P = r.cap;
+    sa.P = sched.cap;
     sa.tkey = tkey;
     sa.tidx = tidx;
     sa.ovf = ovf;
@@ -2550,7 +2545,7 @@ int topk_i8_device_impl(const I8Route &r, const int8_t *dq, int64_t ldq, int64_t
     sa.index_base = index_base;
     sa.out_idx = oi + r0 * k;
     sa.out_score = os + r0 * k;
-    int64_t seen = 0, chunk = s0;
+    int64_t seen = 0, chunk = sched.s0;
     while (seen < n) {
       const int64_t cc = std::min<int64_t>(chunk, n - seen);
       a.col0 = (int)seen;
@@ -2567,7 +2562,7 @@ int topk_i8_device_impl(const I8Route &r, const int8_t *dq, int64_t ldq, int64_t
         Timed t("i8_finish", s);
         HIP_TRY(launch_i8_finish(sa, s));
       }
-      chunk = seen * g;
+      chunk = seen * sched.g;
     }
     HIP_TRY(launch_i8_collect(ovf, rws, (int)r0, count, rows, s));
   }
@@ -2588,11 +2583,6 @@ int validate_i8(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
     return fail(PMM_ERR_UNSUPPORTED, "int8 rows take d < %d (got %lld): a sum of squares must fit in 32 bits",
                 kI8DimLimit, (long long)d);
   return PMM_OK;
-}
-
-int list_root() {
-  std::lock_guard<std::mutex> lk(g_devs_mu);
-  return g_devs.empty() ? -1 : g_devs[0];
 }
 
 }  // namespace
@@ -2891,9 +2881,7 @@ static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_cor
   int dev;
   DevScope scope;
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  if (dtype == PMM_DTYPE_I8 && d >= kI8DimLimit)
-    return fail(PMM_ERR_UNSUPPORTED, "int8 rows take d < %d (got %lld): a sum of squares must fit in 32 bits",
-                kI8DimLimit, (long long)d);
+  if (dtype == PMM_DTYPE_I8 && (rc = validate_i8(0, n, d, 0, kMetricDot))) return rc;  // (the dimension limit)
   std::vector<int> devs = devices_snapshot();
   // (an int8 handle is not sharded: it lives on the list's first device)
   if (devs.size() <= 1 || dtype == PMM_DTYPE_I8) devs.assign(1, dev);
@@ -2936,51 +2924,96 @@ static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_cor
   return PMM_OK;
 }
 
-// The call path of pmm_topk_f32_corpus / _f64_corpus / _bf16_corpus, Score
-// the type of the queries and of the scores.  A sharded handle goes to the
-// sharded search on its resident shards; a handle of one shard to `one_shard`
-// -- what differs by row type: the arena layout, the queries' way to the
-// device, the route and the executor -- on the shard's device and this
-// thread's stream there, which leaves the device lists in *oi and *os.
-template <typename Score, typename OneShard>
-static int corpus_topk(const pmm_corpus *h, int dtype, const Score *q, int64_t m, int64_t k, int metric,
-                       uint32_t *out_idx, Score *out_score, OneShard one_shard) {
+// ---------------------------------------------------------------------------
+// The frame of a host top-k call on one device, the same for every row type
+// and for host rows and handles: the device (the handle's, else the device
+// list's root or the thread's choice) and this thread's stream on it; one arena
+// of [uploaded q | uploaded c | the entry's own regions | index list | score
+// list | workspace]; the zero-padded upload of the operands that are host rows;
+// the entry's executor; a derived handle's index remap; the download and the
+// call's one synchronisation.  An entry supplies what differs:
+//   plan(f, L) -> workspace bytes: decides the route on f.dev (f.s is set:
+//     the f32 handle may build its screen image) and takes the entry's own
+//     regions from L (bf16's staging rows, rounded rows and query norms);
+//   run(f): fills those regions and calls the executor, which leaves the lists
+//     in f.oi / f.os.
+// ---------------------------------------------------------------------------
+struct HostRows {  // rows x d host elements, uploaded at row stride dp (src nullptr: no operand of the frame's)
+  const void *src = nullptr;
+  int64_t rows = 0, d = 0, dp = 0;
+  size_t elem = 0;
+};
+template <typename Score>
+struct HostCall {
+  int dev = 0;
+  hipStream_t s = nullptr;
+  char *b = nullptr;                // the arena
+  char *q = nullptr, *c = nullptr;  // the uploaded operands
+  uint32_t *oi = nullptr;
+  Score *os = nullptr;
+  char *w = nullptr;
+  size_t ws_bytes = 0;
+};
+template <typename Score, typename PlanFn, typename RunFn>
+static int host_topk(const pmm_corpus *h, const HostRows &qr, const HostRows &cr, int64_t m, int64_t k,
+                     uint32_t *out_idx, Score *out_score, PlanFn plan, RunFn run) {
+  HostCall<Score> f;
+  DevScope scope;
+  int rc = ensure_device(&f.dev, &scope, h ? h->shards[0].device : list_root());
+  if (rc) return rc;
+  if ((rc = thread_stream(f.dev, &f.s))) return rc;
+  Layout L;
+  const size_t off_q = L.take(qr.src ? (size_t)qr.rows * qr.dp * qr.elem : 0);
+  const size_t off_c = L.take(cr.src ? (size_t)cr.rows * cr.dp * cr.elem : 0);
+  f.ws_bytes = plan(f, L);
+  const size_t off_i = L.take((size_t)m * k * 4), off_s = L.take((size_t)m * k * sizeof(Score));
+  void *base;
+  if ((rc = arena(f.dev, f.s, L.off + f.ws_bytes, &base))) return rc;
+  f.b = (char *)base;
+  f.q = f.b + off_q;
+  f.c = f.b + off_c;
+  f.oi = (uint32_t *)(f.b + off_i);
+  f.os = (Score *)(f.b + off_s);
+  f.w = f.b + L.off;
+  if (qr.src && (rc = upload_padded(f.q, qr.src, qr.rows, qr.d, qr.dp, qr.elem, f.s))) return rc;
+  if (cr.src && (rc = upload_padded(f.c, cr.src, cr.rows, cr.d, cr.dp, cr.elem, f.s))) return rc;
+  if ((rc = run(f))) return rc;
+  if (h && (rc = remap_lists(h, f.oi, m, k, f.s))) return rc;
+  return download_lists(out_idx, out_score, f.oi, f.os, m, k, f.s);
+}
+
+// The call path of the four pmm_topk_*_corpus entries, Row the type of the
+// queries and Score that of the scores.  A sharded handle goes to the sharded
+// search on its resident shards; a handle of one shard through host_topk with
+// the entry's plan and run.  The queries go up padded to the handle's stride;
+// a bf16 handle's as they are (f32 staging rows, which its entry rounds).
+template <typename Row, typename Score, typename PlanFn, typename RunFn>
+static int corpus_topk(const pmm_corpus *h, int dtype, const Row *q, int64_t m, int64_t k, int metric,
+                       uint32_t *out_idx, Score *out_score, PlanFn plan, RunFn run) {
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
   if (h->partitioned()) return partitioned_handle(h);
   if (h->dtype != dtype) return wrong_handle(h);
-  int rc = validate_sizes(m, h->n, h->d, k, true);
+  int rc = dtype == PMM_DTYPE_I8 ? validate_i8(m, h->n, h->d, k, metric) : validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
   if ((rc = check_metric(metric))) return rc;
   if (m == 0 || k == 0) return PMM_OK;
   if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  if (h->shards.size() > 1) {
-    constexpr bool f64 = std::is_same<Score, double>::value;
-    // (the f32 and bf16 shards run the fused top-k only; f64 has a path for every k)
-    if (!f64 && k > kFusedMaxK)
-      return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
-                  (long long)k);
-    std::vector<ShardSrcT<Score>> sh(h->shards.size());
-    for (size_t g = 0; g < sh.size(); g++) {
-      const CorpusShard &x = h->shards[g];
-      sh[g] = ShardSrcT<Score>{x.device, x.lo, x.n, nullptr, x.rows, shard_norms<Score>(h, x, metric)};
+  if constexpr (!std::is_same<Row, int8_t>::value) {  // (an int8 handle has one shard)
+    if (h->shards.size() > 1) {
+      // (the f32 and bf16 shards run the fused top-k only; f64 has a path for every k)
+      if (dtype != PMM_DTYPE_F64 && k > kFusedMaxK)
+        return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus supports k <= %d (got %lld)", kFusedMaxK,
+                    (long long)k);
+      std::vector<ShardSrc> sh(h->shards.size());
+      for (size_t g = 0; g < sh.size(); g++) {
+        const CorpusShard &x = h->shards[g];
+        sh[g] = ShardSrc{x.device, x.lo, x.n, nullptr, x.rows, shard_norms<Score>(h, x, metric)};
+      }
+      return topk_sharded(dtype, q, m, h->d, k, metric, sh, out_idx, out_score);
     }
-    if constexpr (f64)
-      return topk_sharded_f64(q, m, h->d, k, metric, sh, out_idx, out_score);
-    else
-      return topk_sharded(q, m, h->d, k, metric, dtype == PMM_DTYPE_BF16 ? PMM_COMPUTE_BF16 : PMM_COMPUTE_F32, sh,
-                          out_idx, out_score);
   }
-  const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  uint32_t *oi = nullptr;
-  Score *os = nullptr;
-  if ((rc = one_shard(x, dev, s, &oi, &os))) return rc;
-  if ((rc = remap_lists(h, oi, m, k, s))) return rc;
-  return download_lists(out_idx, out_score, oi, os, m, k, s);
+  const HostRows qr{q, m, h->d, dtype == PMM_DTYPE_BF16 ? h->d : h->dp, sizeof(Row)};
+  return host_topk(h, qr, HostRows{}, m, k, out_idx, out_score, plan, run);
 }
 
 // ---------------------------------------------------------------------------
@@ -3311,7 +3344,7 @@ int pmm_shard_plan(const int *devs, int G, int64_t m, int64_t n, int64_t d, int6
     sh[g] = ShardSrc{devs[g], lo, hi - lo, host_rows ? &kHostTag : nullptr, nullptr, nullptr};
   }
   ShardLayout L;
-  plan_sharded(sh, m, d, k, metric, compute, L);
+  plan_sharded(compute == PMM_COMPUTE_BF16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, sh, m, d, k, metric, L);
   *n_plans = (int)L.dps.size();
   for (int j = 0; j < (int)L.dps.size(); j++) {
     plan_dev[j] = L.dps[j].dev;
@@ -3319,7 +3352,7 @@ int pmm_shard_plan(const int *devs, int G, int64_t m, int64_t n, int64_t d, int6
   }
   for (int g = 0; g < G; g++) {
     plan_of[g] = L.plan_of[g];
-    list_offsets[g] = L.off_list[g];
+    list_offsets[g] = L.sl[g].off_li;
   }
   return PMM_OK;
 }
@@ -3418,58 +3451,51 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
     // shard per listed device (at most n shards), results merged on the first
     const std::vector<int> devs = devices_snapshot();
     if (devs.size() > 1 && k <= kFusedMaxK)
-      return topk_sharded(q, m, d, k, metric, compute, host_shards(devs, c, n, d), out_idx, out_score);
+      return topk_sharded(compute == PMM_COMPUTE_BF16 ? PMM_DTYPE_BF16 : PMM_DTYPE_F32, q, m, d, k, metric,
+                          host_shards(devs, c, n, d, 4), out_idx, out_score);
   }
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
+  TopkRoute route;
+  auto plan_route = [&](const HostCall<float> &f) {
+    route = route_topk(m, n, d, k, metric, compute, g_dev[f.dev].cus, true, true);
+    return route.total;
+  };
   if (compute == PMM_COMPUTE_BF16) {
     // f32 rows uploaded as they are, rounded to zero-padded bf16 rows on device
     const int64_t db = padded_dim(PMM_DTYPE_BF16, d);
-    const TopkRoute route = route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true);
-    const size_t ws_need = route.total;
-    size_t off_qf = 0, off_cf = al256((size_t)m * d * 4);
-    size_t off_qb = off_cf + al256((size_t)n * d * 4), off_cb = off_qb + al256((size_t)m * db * 2);
-    size_t off_i = off_cb + al256((size_t)n * db * 2), off_s = off_i + al256((size_t)m * k * 4);
-    size_t off_w = off_s + al256((size_t)m * k * 4);
-    void *base;
-    if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
-    char *b = (char *)base;
-    HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + off_cf, c, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
-    {
-      Timed t("f32_to_bf16", s);  // (measured against round_norms_bf16, profiles/bf16_corpus)
-      HIP_TRY(launch_f32_to_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db, s));
-      HIP_TRY(launch_f32_to_bf16((const float *)(b + off_cf), n, d, d, (uint16_t *)(b + off_cb), db, s));
-    }
-    rc = topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, (const uint16_t *)(b + off_cb),
-                               db, n, d, k, metric, 0u, (uint32_t *)(b + off_i),
-                               (float *)(b + off_s), b + off_w, ws_need, s, dev);
-    if (rc) return rc;
-    return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+    size_t off_qf = 0, off_cf = 0, off_qb = 0, off_cb = 0;
+    return host_topk(
+        nullptr, HostRows{}, HostRows{}, m, k, out_idx, out_score,
+        [&](const HostCall<float> &f, Layout &L) {
+          off_qf = L.take((size_t)m * d * 4), off_cf = L.take((size_t)n * d * 4);
+          off_qb = L.take((size_t)m * db * 2), off_cb = L.take((size_t)n * db * 2);
+          return plan_route(f);
+        },
+        [&](const HostCall<float> &f) -> int {
+          uint16_t *qb = (uint16_t *)(f.b + off_qb), *cb = (uint16_t *)(f.b + off_cb);
+          HIP_TRY(hipMemcpyAsync(f.b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, f.s));
+          HIP_TRY(hipMemcpyAsync(f.b + off_cf, c, (size_t)n * d * 4, hipMemcpyHostToDevice, f.s));
+          {
+            Timed t("f32_to_bf16", f.s);  // (measured against round_norms_bf16, profiles/bf16_corpus)
+            HIP_TRY(launch_f32_to_bf16((const float *)(f.b + off_qf), m, d, d, qb, db, f.s));
+            HIP_TRY(launch_f32_to_bf16((const float *)(f.b + off_cf), n, d, d, cb, db, f.s));
+          }
+          return topk_bf16_device_impl(route, qb, db, m, cb, db, n, d, k, metric, 0u, f.oi, f.os, f.w, f.ws_bytes, f.s,
+                                       f.dev);
+        });
   }
   const int64_t dp = padded_dim(PMM_DTYPE_F32, d);
   {
     const char *ce = getenv("PMM_CHUNKED_UPLOAD");  // 0: one upload, then one launch
     if (k <= kFusedMaxK && (size_t)n * dp * 4 >= kChunkedMinBytes && n >= 64 * k && !(ce && atoi(ce) == 0))
-      return topk_f32_host_chunked(q, m, c, n, d, k, metric, out_idx, out_score, dev, s);
+      return topk_f32_host_chunked(q, m, c, n, d, k, metric, out_idx, out_score);
   }
-  const TopkRoute route = route_topk(m, n, d, k, metric, compute, g_dev[dev].cus, true, true);
-  const size_t ws_need = route.total;
-  size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_i = off_c + al256((size_t)n * dp * 4);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
-  void *base;
-  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
-  char *b = (char *)base;
-  if ((rc = upload_padded(b + off_q, q, m, d, dp, 4, s))) return rc;
-  if ((rc = upload_padded(b + off_c, c, n, d, dp, 4, s))) return rc;
-  rc = topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, (const float *)(b + off_c), dp, n,
-                            d, k, metric, 0u, (uint32_t *)(b + off_i), (float *)(b + off_s),
-                            b + off_w, ws_need, s, dev);
-  if (rc) return rc;
-  return download_lists(out_idx, out_score, b + off_i, b + off_s, m, k, s);
+  return host_topk(
+      nullptr, HostRows{q, m, d, dp, 4}, HostRows{c, n, d, dp, 4}, m, k, out_idx, out_score,
+      [&](const HostCall<float> &f, Layout &) { return plan_route(f); },
+      [&](const HostCall<float> &f) {
+        return topk_f32_device_impl(route, (const float *)f.q, dp, m, (const float *)f.c, dp, n, d, k, metric, 0u, f.oi,
+                                    f.os, f.w, f.ws_bytes, f.s, f.dev);
+      });
 }
 
 int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
@@ -3514,31 +3540,20 @@ int pmm_topk_f64(const double *q, int64_t m, const double *c, int64_t n, int64_t
   if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
   {
-    // a device list (pmm_set_devices): the corpus row-sharded over it, as the
-    // f32 path does (topk_sharded_f64)
+    // a device list (pmm_set_devices): the corpus row-sharded over it, as the f32 path does
     const std::vector<int> devs = devices_snapshot();
     if (devs.size() > 1 && n > 1)
-      return topk_sharded_f64(q, m, d, k, metric, host_shards(devs, c, n, d), out_idx, out_score);
+      return topk_sharded(PMM_DTYPE_F64, q, m, d, k, metric, host_shards(devs, c, n, d, 8), out_idx, out_score);
   }
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
-  size_t off_q = 0, off_c = al256((size_t)m * dp * 8), off_i = off_c + al256((size_t)n * dp * 8);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
-  void *base;
   const bool fused = f64_use_fused(m, n, k);
-  if ((rc = arena(dev, s, off_w + f64_workspace_bytes(m, n, k, fused), &base))) return rc;
-  char *b = (char *)base;
-  const double *dq = (const double *)(b + off_q), *dc = (const double *)(b + off_c);
-  if ((rc = upload_padded(b + off_q, q, m, d, dp, 8, s))) return rc;
-  if ((rc = upload_padded(b + off_c, c, n, d, dp, 8, s))) return rc;
-  uint32_t *oi = (uint32_t *)(b + off_i);
-  double *os = (double *)(b + off_s);
-  if ((rc = topk_f64_device_impl(dq, dp, m, dc, dp, n, d, k, metric, 0u, oi, os, b + off_w, s, fused))) return rc;
-  return download_lists(out_idx, out_score, oi, os, m, k, s);
+  return host_topk(
+      nullptr, HostRows{q, m, d, dp, 8}, HostRows{c, n, d, dp, 8}, m, k, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) { return f64_workspace_bytes(m, n, k, fused); },
+      [&](const HostCall<double> &f) {
+        return topk_f64_device_impl((const double *)f.q, dp, m, (const double *)f.c, dp, n, d, k, metric, 0u, f.oi, f.os,
+                                    f.w, f.s, fused);
+      });
 }
 
 int pmm_topk_f64_device(const double *q, int64_t ldq, int64_t m, const double *c, int64_t ldc, int64_t n,
@@ -3957,46 +3972,41 @@ int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **ou
 
 int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, double *out_score) {
-  return corpus_topk(h, PMM_DTYPE_F64, q, m, k, metric, out_idx, out_score,
-                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, double **os) -> int {
-    const int64_t dp = h->dp, n = h->n;
-    const bool fused = f64_use_fused(m, n, k);
-    size_t off_q = 0, off_i = al256((size_t)m * dp * 8);
-    size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
-    void *base;
-    if (int rc = arena(dev, s, off_w + f64_workspace_bytes(m, n, k, fused), &base)) return rc;
-    char *b = (char *)base;
-    if (int rc = upload_padded(b + off_q, q, m, h->d, dp, 8, s)) return rc;
-    *oi = (uint32_t *)(b + off_i);
-    *os = (double *)(b + off_s);
-    return topk_f64_device_impl((const double *)(b + off_q), dp, m, x.rows_as<double>(), dp, n, h->d, k, metric, 0u,
-                                *oi, *os, b + off_w, s, fused, shard_norms<double>(h, x, metric));
-  });
+  bool fused = false;
+  return corpus_topk(
+      h, PMM_DTYPE_F64, q, m, k, metric, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) {
+        fused = f64_use_fused(m, h->n, k);
+        return f64_workspace_bytes(m, h->n, k, fused);
+      },
+      [&](const HostCall<double> &f) {
+        const CorpusShard &x = h->shards[0];
+        return topk_f64_device_impl((const double *)f.q, h->dp, m, x.rows_as<double>(), h->dp, h->n, h->d, k, metric, 0u,
+                                    f.oi, f.os, f.w, f.s, fused, shard_norms<double>(h, x, metric));
+      });
 }
 
 int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, float *out_score) {
-  return corpus_topk(h, PMM_DTYPE_F32, q, m, k, metric, out_idx, out_score,
-                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, float **os) -> int {
-    const int64_t dp = h->dp;
-    // The screened route when the shape asks for it (screen_wanted, as the
-    // device entry's) and the handle has, or can now build, its ScreenImage;
-    // else the f32 kernel on the cached norms, as for every other metric.
-    TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, true, true, true);
-    const ScreenImage *img = route.kind == Route::kF32Screened ? corpus_screen_image(h, s) : nullptr;
-    if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[dev].cus, false, false);
-    const size_t ws_need = route.total;
-    size_t off_q = 0, off_i = al256((size_t)m * dp * 4);
-    size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 4);
-    void *base;
-    if (int rc = arena(dev, s, off_w + ws_need, &base)) return rc;
-    char *b = (char *)base;
-    if (int rc = upload_padded(b + off_q, q, m, h->d, dp, 4, s)) return rc;
-    *oi = (uint32_t *)(b + off_i);
-    *os = (float *)(b + off_s);
-    return topk_f32_device_impl(route, (const float *)(b + off_q), dp, m, x.rows_as<float>(), dp, h->n, h->d, k, metric,
-                                0u, *oi, *os, b + off_w, ws_need, s, dev, shard_norms<float>(h, x, metric), false, img);
-  });
+  TopkRoute route;
+  const ScreenImage *img = nullptr;
+  return corpus_topk(
+      h, PMM_DTYPE_F32, q, m, k, metric, out_idx, out_score,
+      [&](const HostCall<float> &f, Layout &) {
+        // The screened route when the shape asks for it (screen_wanted, as the
+        // device entry's) and the handle has, or can now build, its ScreenImage;
+        // else the f32 kernel on the cached norms, as for every other metric.
+        route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, true, true, true);
+        img = route.kind == Route::kF32Screened ? corpus_screen_image(h, f.s) : nullptr;
+        if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, false, false);
+        return route.total;
+      },
+      [&](const HostCall<float> &f) {
+        const CorpusShard &x = h->shards[0];
+        return topk_f32_device_impl(route, (const float *)f.q, h->dp, m, x.rows_as<float>(), h->dp, h->n, h->d, k, metric,
+                                    0u, f.oi, f.os, f.w, f.ws_bytes, f.s, f.dev, shard_norms<float>(h, x, metric), false,
+                                    img);
+      });
 }
 
 // Range search.  The tile variant of the emit pass: the ones
@@ -4274,37 +4284,33 @@ int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **ou
 
 int pmm_topk_bf16_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric, uint32_t *out_idx,
                          float *out_score) {
-  return corpus_topk(h, PMM_DTYPE_BF16, q, m, k, metric, out_idx, out_score,
-                     [&](const CorpusShard &x, int dev, hipStream_t s, uint32_t **oi, float **os) -> int {
-    const int64_t d = h->d, db = h->dp, n = h->n;
-    // the route pmm_topk_f32_ex's bf16 branch asks for, so the same kernels run
-    const TopkRoute route = route_topk(m, n, d, k, metric, PMM_COMPUTE_BF16, g_dev[dev].cus, true, true);
-    const size_t ws_need = route.total;
-    // query norms sit outside the route's workspace (topk_bf16_native zeroes its top)
-    size_t off_qf = 0, off_qb = al256((size_t)m * d * 4), off_qn = off_qb + al256((size_t)m * db * 2);
-    size_t off_i = off_qn + al256((size_t)m * 4), off_s = off_i + al256((size_t)m * k * 4);
-    size_t off_w = off_s + al256((size_t)m * k * 4);
-    void *base;
-    if (int rc = arena(dev, s, off_w + ws_need, &base)) return rc;
-    char *b = (char *)base;
-    {
-      Timed t("h2d", s);
-      HIP_TRY(hipMemcpyAsync(b + off_qf, q, (size_t)m * d * 4, hipMemcpyHostToDevice, s));
-    }
-    // the native route reads the metric's query norms; the widened one computes
-    // its own from the widened rows
-    float *qn = (metric != kMetricDot && route.kind == Route::kBf16Native) ? (float *)(b + off_qn) : nullptr;
-    {
-      Timed t("round_norms_bf16", s);
-      HIP_TRY(launch_round_norms_bf16((const float *)(b + off_qf), m, d, d, (uint16_t *)(b + off_qb), db,
-                                      metric == kMetricCosine ? qn : nullptr, nullptr,
-                                      metric == kMetricEuclidean ? qn : nullptr, nullptr, s));
-    }
-    *oi = (uint32_t *)(b + off_i);
-    *os = (float *)(b + off_s);
-    return topk_bf16_device_impl(route, (const uint16_t *)(b + off_qb), db, m, x.rows_as<uint16_t>(), db, n, d, k, metric,
-                                 0u, *oi, *os, b + off_w, ws_need, s, dev, qn, shard_norms<float>(h, x, metric));
-  });
+  TopkRoute route;
+  size_t off_qb = 0, off_qn = 0;
+  return corpus_topk(
+      h, PMM_DTYPE_BF16, q, m, k, metric, out_idx, out_score,
+      [&](const HostCall<float> &f, Layout &L) {
+        // the rounded rows, and the query norms outside the route's workspace
+        // (topk_bf16_native zeroes its top)
+        off_qb = L.take((size_t)m * h->dp * 2), off_qn = L.take((size_t)m * 4);
+        // the route pmm_topk_f32_ex's bf16 branch asks for, so the same kernels run
+        route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_BF16, g_dev[f.dev].cus, true, true);
+        return route.total;
+      },
+      [&](const HostCall<float> &f) -> int {
+        const CorpusShard &x = h->shards[0];
+        const int64_t d = h->d, db = h->dp;
+        uint16_t *qb = (uint16_t *)(f.b + off_qb);
+        // the native route reads the metric's query norms; the widened one computes
+        // its own from the widened rows
+        float *qn = (metric != kMetricDot && route.kind == Route::kBf16Native) ? (float *)(f.b + off_qn) : nullptr;
+        {
+          Timed t("round_norms_bf16", f.s);
+          HIP_TRY(launch_round_norms_bf16((const float *)f.q, m, d, d, qb, db, metric == kMetricCosine ? qn : nullptr,
+                                          nullptr, metric == kMetricEuclidean ? qn : nullptr, nullptr, f.s));
+        }
+        return topk_bf16_device_impl(route, qb, db, m, x.rows_as<uint16_t>(), db, h->n, d, k, metric, 0u, f.oi, f.os, f.w,
+                                     f.ws_bytes, f.s, f.dev, qn, shard_norms<float>(h, x, metric));
+      });
 }
 
 // ---- int8 rows (DESIGN.md §4d "Int8 rows") ----
@@ -4355,26 +4361,15 @@ int pmm_topk_i8(const int8_t *q, int64_t m, const int8_t *c, int64_t n, int64_t 
   if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
   // (a device list does not shard int8 rows: the call runs on its first device)
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_I8, d);
   const I8Route route = route_i8(m, n, d, k);
-  size_t off_q = 0, off_c = al256((size_t)m * dp), off_i = off_c + al256((size_t)n * dp);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
-  void *base;
-  if ((rc = arena(dev, s, off_w + route.total, &base))) return rc;
-  char *b = (char *)base;
-  if ((rc = upload_padded(b + off_q, q, m, d, dp, 1, s))) return rc;
-  if ((rc = upload_padded(b + off_c, c, n, d, dp, 1, s))) return rc;
-  uint32_t *oi = (uint32_t *)(b + off_i);
-  double *os = (double *)(b + off_s);
-  if ((rc = topk_i8_device_impl(route, (const int8_t *)(b + off_q), dp, m, (const int8_t *)(b + off_c), dp, n, d, k,
-                                metric, 0u, oi, os, b + off_w, s)))
-    return rc;
-  return download_lists(out_idx, out_score, oi, os, m, k, s);
+  return host_topk(
+      nullptr, HostRows{q, m, d, dp, 1}, HostRows{c, n, d, dp, 1}, m, k, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) { return route.total; },
+      [&](const HostCall<double> &f) {
+        return topk_i8_device_impl(route, (const int8_t *)f.q, dp, m, (const int8_t *)f.c, dp, n, d, k, metric, 0u, f.oi,
+                                   f.os, f.w, f.s);
+      });
 }
 
 int pmm_corpus_create_i8(const int8_t *c, int64_t n, int64_t d, pmm_corpus **out) {
@@ -4383,33 +4378,18 @@ int pmm_corpus_create_i8(const int8_t *c, int64_t n, int64_t d, pmm_corpus **out
 
 int pmm_topk_i8_corpus(const pmm_corpus *h, const int8_t *q, int64_t m, int64_t k, int metric, uint32_t *out_idx,
                        double *out_score) {
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (h->partitioned()) return partitioned_handle(h);
-  if (h->dtype != PMM_DTYPE_I8) return wrong_handle(h);
-  int rc = validate_i8(m, h->n, h->d, k, metric);
-  if (rc) return rc;
-  if (m == 0 || k == 0) return PMM_OK;
-  if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  const int64_t dp = h->dp, n = h->n;
-  const I8Route route = route_i8(m, n, h->d, k);
-  size_t off_q = 0, off_i = al256((size_t)m * dp);
-  size_t off_s = off_i + al256((size_t)m * k * 4), off_w = off_s + al256((size_t)m * k * 8);
-  void *base;
-  if ((rc = arena(dev, s, off_w + route.total, &base))) return rc;
-  char *b = (char *)base;
-  if ((rc = upload_padded(b + off_q, q, m, h->d, dp, 1, s))) return rc;
-  uint32_t *oi = (uint32_t *)(b + off_i);
-  double *os = (double *)(b + off_s);
-  if ((rc = topk_i8_device_impl(route, (const int8_t *)(b + off_q), dp, m, x.rows_as<int8_t>(), dp, n, h->d, k, metric,
-                                0u, oi, os, b + off_w, s, (const uint32_t *)x.norms, (const float *)x.norms + n)))
-    return rc;
-  return download_lists(out_idx, out_score, oi, os, m, k, s);
+  I8Route route;
+  return corpus_topk(
+      h, PMM_DTYPE_I8, q, m, k, metric, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) {
+        route = route_i8(m, h->n, h->d, k);
+        return route.total;
+      },
+      [&](const HostCall<double> &f) {
+        const CorpusShard &x = h->shards[0];
+        return topk_i8_device_impl(route, (const int8_t *)f.q, h->dp, m, x.rows_as<int8_t>(), h->dp, h->n, h->d, k, metric,
+                                   0u, f.oi, f.os, f.w, f.s, (const uint32_t *)x.norms, (const float *)x.norms + h->n);
+      });
 }
 
 int pmm_timing_enable(int enable) {
