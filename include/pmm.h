@@ -222,10 +222,11 @@ int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, 
 
 /* The bf16 compute path over device-resident bf16 rows (bit patterns, e.g. a
  * torch.bfloat16 tensor): d is the logical dimension; ldq / ldc >=
- * roundup(d, 128), multiples of 8, columns past d zero-filled, 16-byte-aligned
- * bases (any d and k: past the bf16 kernels' limits, the widened f32 path of
- * PMM_COMPUTE_BF16).  Scores are f32; k may exceed n as in
- * pmm_topk_f32_device. */
+ * roundup(d, 128), multiples of 8, columns d..roundup(d, 128)-1 zero-filled,
+ * 16-byte-aligned bases (any d and k: past the bf16 kernels' limits, the
+ * widened f32 path of PMM_COMPUTE_BF16).  As for f32 rows, whatever lies in a
+ * row's stride at and past the padded width is the caller's: it is never
+ * read.  Scores are f32; k may exceed n as in pmm_topk_f32_device. */
 int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16_t *c,
                          int64_t ldc, int64_t n, int64_t d, int64_t k, int metric,
                          uint32_t index_base, uint32_t *out_idx, float *out_score,

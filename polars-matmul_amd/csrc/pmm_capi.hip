@@ -206,6 +206,17 @@ int arena(int dev, hipStream_t s, size_t bytes, void **p) {
     HIP_TRY(hipMalloc(&a.p, want));
     a.bytes = want;
   }
+  // debug knob (read per call, so a test can toggle it): PMM_ARENA_POISON = a
+  // byte value, decimal or 0x..: the whole slot, slack included, is filled with
+  // it on this use's stream, behind the waits above and ahead of everything the
+  // caller enqueues, so a call that reads scratch it has not written reads the
+  // poison instead of an earlier call's leftovers.  Every entry acquires the
+  // arena once per call and per device, so no fill lands on bytes still in use.
+  if (const char *pe = getenv("PMM_ARENA_POISON")) {
+    char *end = nullptr;
+    const long v = strtol(pe, &end, 0);
+    if (end != pe) HIP_TRY(hipMemsetAsync(a.p, (int)(v & 0xFF), a.bytes, s));
+  }
   *p = a.p;
   return PMM_OK;
 }

@@ -130,6 +130,7 @@ def run_in_exact_workspace(m, n, d, k, metric, compute, q, c, ld, index_base=0):
     tq[:, :d] = torch.from_numpy(q).to(dev).to(dt)
     tc[:, :d] = torch.from_numpy(c).to(dev).to(dt)
     wb = _native.workspace_bytes(m, n, d, k, metric, compute)
+    # (zeroed: this test owns the size; tests/test_gpu_dirty_scratch.py owns the contents)
     ws = torch.zeros(wb, dtype=torch.uint8, device=dev)
     oi = torch.empty((m, k), dtype=torch.int32, device=dev)
     osc = torch.empty((m, k), dtype=torch.float32, device=dev)
