@@ -620,6 +620,50 @@ int pmm_range_f32_corpus(const pmm_corpus *corpus, const float *q, int64_t m, fl
                          int64_t cap, int64_t *out_offsets /* m + 1 */, uint32_t *out_idx, float *out_score,
                          int64_t *total);
 
+/* Candidate search: exact top-k of every query row over its OWN list of
+ * corpus rows (host queries and lists in, host results out; any k >= 1, since
+ * k only cuts a sorted list).  Row i's candidates are cand_ids[cand_offsets[i]
+ * .. cand_offsets[i + 1]): corpus row numbers, strictly ascending within a
+ * row, each below n.  Its result is the first out_len[i] = min(k, count_i)
+ * entries of the ranked list of exactly those rows, in the total order of
+ * every pmm_topk_* entry (best first, NaN last, equal scores to the lower
+ * index; -0.0 and +0.0 tie and a returned zero carries the reference's sign):
+ * the index and score bits pmm_topk_f32 returns on the candidate rows alone,
+ * its indices mapped through the list.  Row stride k in out_idx / out_score;
+ * the slots past out_len[i] hold index 0xFFFFFFFF and score +0.0 (the grouped
+ * entries' convention).  An empty list gives out_len[i] = 0; a list of every
+ * row gives pmm_topk_f32_corpus' list.
+ * One launch scores every (row, candidate) pair: a workgroup takes one query
+ * row and up to 256 of its candidates, a lane one pair -- the f32 path's
+ * K-ordered fmaf chain over exactly d elements and its epilogue on the
+ * handle's norms -- with the candidate rows gathered 128 bytes per eight
+ * lanes through LDS, two K chunks of loads in flight.  The keys (ordered
+ * score | ~id) land in the lists' own CSR layout and are sorted by the range
+ * search's kernels: up to 128 keys in a wave, up to PMM_RANGE_SORT_MAX (8192;
+ * read per call, can only be lowered) in a workgroup's LDS; a longer list is
+ * cut into pieces of that size, each sorted, and its best min(k, count) keys
+ * merged by rank counting.  One more launch decodes the first out_len[i] keys
+ * of every row into the planes and fills the rest.  The screen image is never
+ * used.
+ * Errors.  Null corpus, q, cand_offsets or an output, null cand_ids with a
+ * non-empty list, negative m, k < 1, a bad metric, cand_offsets that do not
+ * start at 0 or that descend, a list longer than n: PMM_ERR_ARG before any
+ * device call.  A list that is not strictly ascending or holds an id >= n is
+ * found on the device (such an id is clamped before it forms an address) and
+ * reported after the call's wait as PMM_ERR_ARG naming the case; the lists are
+ * then unspecified.  m = 0: PMM_OK.
+ * Serves a plain f32 handle of one shard.  A derived (pmm_corpus_subset_*) or
+ * partitioned handle: PMM_ERR_ARG (list the candidates in the parent's row
+ * numbers and search the parent); an f64, bf16 or int8 handle: PMM_ERR_ARG; a
+ * sharded handle: PMM_ERR_UNSUPPORTED.  Thread-safe like the other handle
+ * entries (the calling thread's stream and arena, one arena acquisition);
+ * synchronises once before it returns.  No reference counterpart. */
+int pmm_topk_f32_candidates(const pmm_corpus *corpus, const float *q, int64_t m,
+                            const int64_t *cand_offsets /* m + 1 */, const uint32_t *cand_ids,
+                            int64_t k, int metric,
+                            uint32_t *out_idx /* m * k */, float *out_score /* m * k */,
+                            uint32_t *out_len /* m */);
+
 /* Per-kernel timing on the launch stream (hipEvents around each launch).
  * enable=1 starts recording; pmm_timing_read returns the summed milliseconds
  * and launch count of kernels whose name contains `kernel` since the last

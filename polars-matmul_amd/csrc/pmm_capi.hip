@@ -4256,6 +4256,212 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   return PMM_OK;
 }
 
+// Candidate search (DESIGN.md §4d "Candidate lists"): score every (row,
+// candidate) pair into the CSR key layout of the range search, sort each
+// row's segment with its kernels, cut at k and decode into the [m][k] planes.
+int pmm_topk_f32_candidates(const pmm_corpus *h, const float *q, int64_t m, const int64_t *cand_offsets,
+                            const uint32_t *cand_ids, int64_t k, int metric, uint32_t *out_idx, float *out_score,
+                            uint32_t *out_len) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (m < 0) return fail(PMM_ERR_ARG, "negative size (m=%lld)", (long long)m);
+  if (k < 1) return fail(PMM_ERR_ARG, "k must be >= 1 (got %lld)", (long long)k);
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (h->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16", "int8"};
+    return fail(PMM_ERR_ARG, "candidate search takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
+  }
+  if (h->partitioned())
+    return fail(PMM_ERR_ARG, "candidate search takes a plain f32 handle: this one is partitioned "
+                             "(pmm_corpus_partition); list the candidates in its parent's row numbers and search the parent");
+  if (h->map)
+    return fail(PMM_ERR_ARG, "candidate search takes a plain f32 handle: this one is derived (pmm_corpus_subset_*); "
+                             "list the candidates in its parent's row numbers and search the parent");
+  if (h->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED,
+                "a device-sharded corpus (%d shards) has no candidate search: use a handle of one shard",
+                (int)h->shards.size());
+  if ((rc = validate_sizes(m, h->n, h->d, 0, false))) return rc;
+  if (m == 0) return PMM_OK;
+  if (!q || !cand_offsets || !out_idx || !out_score || !out_len) return fail(PMM_ERR_ARG, "null argument");
+  const int64_t n = h->n, d = h->d, dp = h->dp;
+  if (cand_offsets[0] != 0)
+    return fail(PMM_ERR_ARG, "cand_offsets must start at 0 (cand_offsets[0] = %lld)", (long long)cand_offsets[0]);
+  for (int64_t i = 0; i < m; i++) {
+    const int64_t c = cand_offsets[i + 1] - cand_offsets[i];
+    if (c < 0)
+      return fail(PMM_ERR_ARG, "cand_offsets must not descend: cand_offsets[%lld] = %lld follows %lld",
+                  (long long)(i + 1), (long long)cand_offsets[i + 1], (long long)cand_offsets[i]);
+    if (c > n)
+      return fail(PMM_ERR_ARG, "row %lld lists %lld candidates, the corpus has %lld rows: its ids cannot be strictly "
+                               "ascending", (long long)i, (long long)c, (long long)n);
+  }
+  const int64_t total = cand_offsets[m];
+  if (total > 0 && !cand_ids) return fail(PMM_ERR_ARG, "null argument");
+  if (m > (int64_t(1) << 40) / k)
+    return fail(PMM_ERR_ARG, "m * k out of range (m=%lld k=%lld): clip k to the longest list first", (long long)m,
+                (long long)k);
+
+  // Host tables.  Units of the score pass: a row's candidates 256 at a time.
+  // Pieces of the sort: a row of up to smax keys is one piece, a longer one is
+  // cut into pieces of smax, each sorted on its own; a cut row's best
+  // min(k, count) keys are then merged into a second key array behind the first.
+  const int64_t smax = range_sort_max();
+  std::vector<CandUnit> units;
+  std::vector<int64_t> po, src((size_t)m);
+  std::vector<int> mid;  // pieces of 129 .. smax keys
+  std::vector<CandPiece> cut;
+  int64_t mid_max = 0, ltotal = 0;
+  po.push_back(0);
+  for (int64_t i = 0; i < m; i++) {
+    const int64_t o = cand_offsets[i], c = cand_offsets[i + 1] - o;
+    for (int64_t u = 0; u < c; u += kCandUnit) units.push_back(CandUnit{(uint32_t)i, (uint32_t)u});
+    src[(size_t)i] = o;
+    const int64_t T = c > smax ? cdiv(c, smax) : 1;
+    if (T > 1) {
+      src[(size_t)i] = total + ltotal;
+      const int64_t kout = std::min(k, c);
+      for (int64_t t = 0; t < T; t++)
+        cut.push_back(CandPiece{(uint32_t)(po.size() - 1 + t), (uint32_t)(po.size() - 1), (uint32_t)T, (uint32_t)kout,
+                                ltotal});
+      ltotal += kout;
+    }
+    for (int64_t t = 0; t < T; t++) {
+      const int64_t len = std::min(smax, c - t * smax);
+      if (len > kRangeWaveMax) {
+        mid.push_back((int)(po.size() - 1));
+        mid_max = std::max(mid_max, len);
+      }
+      po.push_back(o + t * smax + len);
+    }
+  }
+  const int64_t npieces = (int64_t)po.size() - 1;
+  if ((int64_t)units.size() > INT32_MAX || npieces > INT32_MAX)
+    return fail(PMM_ERR_ARG, "too many candidates for one call (%lld): split the query rows", (long long)total);
+
+  const CorpusShard &x = h->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  // arena: queries | query norms | flag | offsets | ids | units | piece bounds
+  // | piece list | cut pieces | key sources | keys, merged keys | the planes
+  Layout L;
+  const size_t off_q = L.take((size_t)m * dp * 4);
+  const size_t off_qn = L.take((size_t)m * 4);
+  const size_t off_flag = L.take(4);
+  const size_t off_offs = L.take((size_t)(m + 1) * 8);
+  const size_t off_ids = L.take((size_t)total * 4);
+  const size_t off_units = L.take(units.size() * sizeof(CandUnit));
+  const size_t off_po = L.take(cut.empty() ? 0 : (size_t)(npieces + 1) * 8);
+  const size_t off_mid = L.take(mid.size() * 4);
+  const size_t off_cut = L.take(cut.size() * sizeof(CandPiece));
+  const size_t off_src = L.take((size_t)m * 8);
+  const size_t off_keys = L.take((size_t)(total + ltotal) * 8);
+  const size_t off_oi = L.take((size_t)m * k * 4);
+  const size_t off_os = L.take((size_t)m * k * 4);
+  const size_t off_len = L.take((size_t)m * 4);
+  void *base;
+  if ((rc = arena(dev, s, L.off, &base))) return rc;
+  char *b = (char *)base;
+  const float *dq = (const float *)(b + off_q);
+  if ((rc = upload_padded(b + off_q, q, m, d, dp, 4, s))) return rc;
+  HIP_TRY(hipMemsetAsync(b + off_flag, 0, 4, s));
+  int64_t *d_offs = (int64_t *)(b + off_offs);
+  // (without a cut row the pieces are the rows)
+  const int64_t *d_po = cut.empty() ? d_offs : (const int64_t *)(b + off_po);
+  {
+    Timed t("h2d", s);
+    HIP_TRY(hipMemcpyAsync(d_offs, cand_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + off_src, src.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+    if (total > 0) {
+      HIP_TRY(hipMemcpyAsync(b + off_ids, cand_ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(b + off_units, units.data(), units.size() * sizeof(CandUnit), hipMemcpyHostToDevice, s));
+    }
+    if (!cut.empty()) {
+      HIP_TRY(hipMemcpyAsync(b + off_po, po.data(), po.size() * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(b + off_cut, cut.data(), cut.size() * sizeof(CandPiece), hipMemcpyHostToDevice, s));
+    }
+    if (!mid.empty()) HIP_TRY(hipMemcpyAsync(b + off_mid, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, s));
+  }
+  float *qn = (float *)(b + off_qn);
+  if (metric != kMetricDot) {
+    Timed t("norms_f32", s);
+    HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+  }
+  unsigned long long *keys = (unsigned long long *)(b + off_keys);
+  CandScoreArgs sa{};
+  sa.q = dq;
+  sa.c = x.rows_as<float>();
+  sa.qn = qn;
+  sa.cn = shard_norms<float>(h, x, metric);
+  sa.offsets = d_offs;
+  sa.ids = (const uint32_t *)(b + off_ids);
+  sa.unit = (const CandUnit *)(b + off_units);
+  sa.units = (int)units.size();
+  sa.ldq = dp;
+  sa.ldc = dp;
+  sa.n = (uint32_t)n;
+  sa.d = (int)d;
+  sa.metric = metric;
+  sa.keys = keys;
+  sa.flag = (unsigned *)(b + off_flag);
+  {
+    Timed t("cand_score", s);
+    HIP_TRY(launch_cand_score(sa, s));
+  }
+  if (total > 0) {
+    Timed t("range_sort_wave", s);
+    HIP_TRY(launch_range_sort_wave(keys, d_po, (int)npieces, s));
+  }
+  if (!mid.empty()) {
+    Timed t("range_sort_block", s);
+    HIP_TRY(launch_range_sort_block(keys, d_po, (const int *)(b + off_mid), (int)mid.size(), next_pow2((int)mid_max),
+                                    s));
+  }
+  if (!cut.empty()) {
+    Timed t("cand_merge", s);
+    HIP_TRY(launch_cand_merge(keys, d_po, (const CandPiece *)(b + off_cut), (int)cut.size(), keys + total, s));
+  }
+  CandDecodeArgs da{};
+  da.keys = keys;
+  da.src = (const int64_t *)(b + off_src);
+  da.offsets = d_offs;
+  da.m = (int)m;
+  da.metric = metric;
+  da.d = (int)d;
+  da.k = k;
+  da.q = dq;
+  da.c = sa.c;
+  da.qn = qn;
+  da.cn = sa.cn;
+  da.ldq = dp;
+  da.ldc = dp;
+  da.out_idx = (uint32_t *)(b + off_oi);
+  da.out_score = (float *)(b + off_os);
+  da.out_len = (uint32_t *)(b + off_len);
+  {
+    Timed t("cand_decode", s);
+    HIP_TRY(launch_cand_decode(da, s));
+  }
+  unsigned flag = 0u;
+  {
+    Timed t("d2h", s);
+    HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_len, da.out_len, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&flag, sa.flag, 4, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag & 2u)
+    return fail(PMM_ERR_ARG, "a candidate id is not a row of the corpus (n=%lld)", (long long)n);
+  if (flag & 1u)
+    return fail(PMM_ERR_ARG, "candidate ids must be strictly ascending within a row (a row repeats or descends)");
+  return PMM_OK;
+}
+
 int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,
                               float *norm, float *inv_norm, float *rel, uint32_t *unsafe, uint32_t *scalars,
                               void *stream) {

@@ -178,6 +178,51 @@ struct RangeDecodeArgs {
 };
 // keys -> (index, score) by the top-k epilogue's rules
 hipError_t launch_range_decode(const RangeDecodeArgs &a, hipStream_t s);
+// ---- candidate search: per-row candidate lists (pmm_candidates.hip) ----
+// One work unit of the score pass = one workgroup: query row `row` against
+// its candidates [start, start + kCandUnit) (places in the row's list).
+constexpr int kCandUnit = 256;
+struct CandUnit {
+  uint32_t row, start;
+};
+struct CandScoreArgs {
+  const float *q, *c;        // queries (row stride ldq) and the handle's rows (ldc), zero-padded to a multiple of 32
+  const float *qn, *cn;      // cosine: norms, euclidean: squared norms; dot: unused
+  const int64_t *offsets;    // m + 1 list bounds (device)
+  const uint32_t *ids;       // the lists
+  const CandUnit *unit;      // device table, one entry per workgroup
+  int units;
+  int64_t ldq, ldc;
+  uint32_t n;                // corpus rows
+  int d, metric;
+  unsigned long long *keys;  // [offsets[m]]: okey32(rank value) << 32 | ~id, laid out as the lists
+  unsigned *flag;            // |= 1: a list does not ascend strictly, |= 2: an id >= n (zeroed by the caller)
+};
+// keys[offsets[i] + j] = the composite of (query row i, corpus row ids[offsets[i] + j])
+hipError_t launch_cand_score(const CandScoreArgs &a, hipStream_t s);
+// A list longer than the in-LDS sort is cut into pieces that are sorted on
+// their own (launch_range_sort_*, over the piece bounds).  Piece `self` of the
+// row's pieces [first, first + T): the row's best kout keys go to dst[dst ..).
+struct CandPiece {
+  uint32_t self, first, T, kout;
+  int64_t dst;
+};
+hipError_t launch_cand_merge(const unsigned long long *keys, const int64_t *piece_offsets, const CandPiece *pieces,
+                             int npieces, unsigned long long *dst, hipStream_t s);
+struct CandDecodeArgs {
+  const unsigned long long *keys;  // sorted; row i's best keys start at keys[src[i]]
+  const int64_t *src;
+  const int64_t *offsets;          // m + 1 list bounds (device): row i has offsets[i + 1] - offsets[i] candidates
+  int m, metric, d;
+  int64_t k;
+  // what a +0.0 cosine or dot score's sign is recomputed from (see range_decode_kernel)
+  const float *q, *c, *qn, *cn;
+  int64_t ldq, ldc;
+  uint32_t *out_idx;               // [m][k], unused slots 0xFFFFFFFF
+  float *out_score;                // [m][k], unused slots +0.0
+  uint32_t *out_len;               // [m]: min(k, candidates)
+};
+hipError_t launch_cand_decode(const CandDecodeArgs &a, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, int loader, hipStream_t s);
 // Threshold seeding: gthr[row] = (k-th best composite of the row's ns
 // materialised scores S[row][0..ns)) - 1, one wave per row; ns <= kSeedMaxNs.

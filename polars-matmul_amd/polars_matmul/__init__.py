@@ -14,7 +14,10 @@ as a bf16 handle (half an f32 handle's HBM) while its Series is reused.
 device, and returns indices that number the full corpus.  ``groups=`` (an
 extension; ``by=`` / ``corpus_by=`` on the namespace) searches every query row
 only among the corpus rows that carry its own label, all labels in one call
-against a handle whose rows are stored group by group.  ``.pmm.within(corpus,
+against a handle whose rows are stored group by group.  ``candidates=`` (an
+extension, on all three) gives every query row its own list of corpus row ids
+-- the second stage of a hybrid or two-stage search -- and searches all rows in
+one call, exact f32 scores, on Float32 columns.  ``.pmm.within(corpus,
 threshold, metric)`` (an extension; ``within`` / ``_within`` without Polars) is
 range search: every corpus row whose score passes the threshold, as ragged
 lists, on Float32 columns.  The numerics run on MI355X through hand-written HIP
@@ -66,7 +69,7 @@ except Exception:  # polars is optional (not installable in this image)
 
 
 def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosine",
-         compute: Compute = "f32", subset=None, groups=None):
+         compute: Compute = "f32", subset=None, groups=None, candidates=None):
     """numpy-level top-k: returns (indices uint32 [m, k'], scores float64 [m, k'])
     with k' = min(k, len(corpus)); f32 compute iff both inputs are float32
     (src/matmul.rs:427), scores widened to f64 (src/matmul.rs:447).
@@ -82,10 +85,43 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     (per label on the host rows: a numpy corpus has no cached handle).
     k' = min(k, largest searched segment); a row whose segment is shorter (or
     empty: a null or unseen label) ends in unused slots -- index 0xFFFFFFFF,
-    score NaN.  Not together with ``subset``."""
+    score NaN.  Not together with ``subset``.
+    candidates (an extension): one list of corpus row ids per query row, as an
+    Arrow List array or a pair ``(offsets, ids)`` of numpy arrays; every query
+    is searched only among its own list, all rows in one call.  float32
+    inputs only.  k' = min(k, longest list); a shorter list ends in unused
+    slots -- index 0xFFFFFFFF, score NaN.  Not together with ``subset`` or
+    ``groups``."""
     q = np.asarray(queries)
     c = np.asarray(corpus)
     _native.check_compute(compute)
+    if candidates is not None:
+        from polars_matmul._polars_matmul import _candidates_f32_only, _check_candidates, _topk_candidates
+
+        if subset is not None or groups is not None:
+            raise ValueError("candidates= cannot be combined with subset= or groups=: "
+                             "leave the rows a query must not see out of its list")
+        if compute == "bf16":
+            raise _candidates_f32_only('compute="bf16" has no candidate search')
+        if q.dtype != np.float32 or c.dtype != np.float32:
+            raise _candidates_f32_only(f"got {q.dtype} queries and a {c.dtype} corpus")
+        if q.ndim != 2 or c.ndim != 2:
+            raise TypeError(f"expected 2-D arrays of embeddings, got shapes {q.shape} and {c.shape}")
+        cand = _check_candidates(candidates, q.shape[0], c.shape[0])
+        if q.shape[1] != c.shape[1]:
+            raise RuntimeError(
+                f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
+                f"right has {c.shape[1]} dimensional vectors"
+            )
+        kk = min(int(k), cand.maxlen)
+        if kk <= 0 or q.shape[0] == 0:
+            return np.zeros((q.shape[0], 0), dtype=np.uint32), np.zeros((q.shape[0], 0), dtype=np.float64)
+        cc = np.ascontiguousarray(c)
+        idx, sc, lens = _topk_candidates(np.ascontiguousarray(q), cc, None, cc, cand, kk,
+                                         _native.metric_from_str(metric))
+        sc = sc.astype(np.float64)
+        sc[np.arange(kk)[None, :] >= lens[:, None].astype(np.int64)] = np.nan
+        return idx, sc
     if groups is not None:
         if subset is not None:
             raise ValueError("groups= and subset= cannot be combined: give the rows to leave out a null label")
@@ -197,7 +233,8 @@ if pl is not None:
 
         def topk(self, corpus: "pl.Series", k: int, metric: Metric = "cosine",
                  compute: Compute = "f32", subset: "pl.Series | None" = None,
-                 by: "pl.Expr | str | None" = None, corpus_by: "pl.Series | None" = None) -> "pl.Expr":
+                 by: "pl.Expr | str | None" = None, corpus_by: "pl.Series | None" = None,
+                 candidates: "pl.Expr | str | None" = None) -> "pl.Expr":
             """Top-k matches per embedding: List[Struct{index: u32, score: f64}].
             compute="bf16" (an extension): both columns read as f32 and
             searched on the bf16 MFMA path, the corpus kept on the device as a
@@ -210,7 +247,14 @@ if pl is not None:
             expression or column name of the query frame, ``corpus_by`` a
             Series aligned with ``corpus``.  Every row is searched only among
             the corpus rows whose ``corpus_by`` equals its ``by`` (null matches
-            nothing); the lists are ragged, min(k, rows of that label) long."""
+            nothing); the lists are ragged, min(k, rows of that label) long.
+            candidates (an extension): an expression or column name of the
+            query frame holding one List of corpus row ids per row (any integer
+            type; a null list is empty).  Every row is searched only among its
+            own list -- a lexical retriever's hits, a cheaper search's 4 k best,
+            the documents it may see -- with exact f32 scores; the lists are
+            ragged, min(k, candidates) long.  Float32 columns only; not with
+            ``subset``, ``by`` or compute="bf16"."""
             if isinstance(corpus, pl.Expr):
                 raise TypeError(
                     "corpus must be a Polars Series, not an Expression. "
@@ -233,6 +277,19 @@ if pl is not None:
             extra = {} if compute == "f32" else {"compute": compute}
             if subset is not None:
                 extra["subset"] = subset
+            if candidates is not None:
+                if by is not None or subset is not None:
+                    raise ValueError("candidates= cannot be combined with subset= or by=: "
+                                     "leave the rows a query must not see out of its list")
+                # the embedding and its list travel as one struct column, as by= does
+                cand_expr = pl.col(candidates) if isinstance(candidates, str) else candidates
+                packed = pl.struct(self._expr.alias("embedding"), cand_expr.alias("candidates"))
+                return packed.map_batches(
+                    lambda s: _topk(s.struct.field("embedding"), corpus, k, metric,
+                                    candidates=s.struct.field("candidates"), **extra),
+                    is_elementwise=True,
+                    return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+                )
             if by is not None:
                 # the embedding and its label travel as one struct column: rows
                 # are independent, so the batches stay elementwise

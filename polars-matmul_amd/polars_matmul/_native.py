@@ -89,6 +89,7 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
     "pmm_range_f32_corpus",
+    "pmm_topk_f32_candidates",
     "pmm_topk_i8",
     "pmm_topk_i8_corpus",
     "pmm_topk_i8_device",
@@ -200,6 +201,7 @@ _SIGS = {
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_range_f32_corpus": ([_vp, _vp, _i64, ctypes.c_float, _i32, _i64, _vp, _vp, _vp,
                               ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_topk_f32_candidates": ([_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_topk_i8": ([_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
@@ -823,6 +825,35 @@ class DeviceCorpus:
         finally:
             self.release()
         return offsets, idx[:total.value], sc[:total.value]
+
+    def topk_candidates(self, q: np.ndarray, offsets, ids, k: int, metric: int):
+        """(idx uint32 (m, k), scores float32 (m, k), lens uint32 (m,)) of
+        pmm_topk_f32_candidates: row i searched only among the corpus rows
+        ``ids[offsets[i]:offsets[i + 1]]`` (strictly ascending row numbers of
+        this handle); its first ``lens[i]`` = min(k, count) slots are the exact
+        top-k there, the rest hold index 0xFFFFFFFF and score 0.  A plain f32
+        handle of one shard; the library's refusal raises ``PmmError``."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        m = q.shape[0]
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (m + 1,):
+            raise ValueError(f"one list per query row: {m} rows need {m + 1} offsets, got shape {offsets.shape}")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if ids.size < int(offsets[-1]):
+            raise ValueError(f"the offsets end at {int(offsets[-1])}, the ids hold {ids.size}")
+        k = int(k)
+        idx = np.empty((m, max(k, 0)), dtype=np.uint32)
+        sc = np.empty((m, max(k, 0)), dtype=np.float32)
+        lens = np.empty(m, dtype=np.uint32)
+        self.acquire()
+        try:
+            check(_lib.pmm_topk_f32_candidates(self._h, ptr(q), m, ptr(offsets), ptr(ids) if ids.size else None, k,
+                                               metric, ptr(idx), ptr(sc), ptr(lens)))
+        finally:
+            self.release()
+        return idx, sc, lens
 
     def _derived(self, h: ctypes.c_void_p) -> "DeviceCorpus":
         """The DeviceCorpus of a handle the library derived from this one."""

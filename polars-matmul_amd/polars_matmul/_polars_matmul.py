@@ -614,6 +614,148 @@ def _topk_grouped(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, com
     return idx, sc, lens
 
 
+# ---------------------------------------------------------------------------
+# candidates=: every query row brings its own list of corpus rows (an
+# extension: the second stage of a hybrid or two-stage search, per-row
+# permissions).  The lists are checked, sorted and de-duplicated on the host
+# in one vectorised pass and searched in ONE call on the cached f32 handle
+# (DeviceCorpus.topk_candidates); there is no per-row loop anywhere.
+# ---------------------------------------------------------------------------
+def _candidates_f32_only(what: str) -> TypeError:
+    return TypeError(
+        f"candidate search runs on Float32 columns ({what}); cast the embeddings first, e.g. "
+        "pl.col('embedding').cast(pl.List(pl.Float32)) or array.astype(numpy.float32)"
+    )
+
+
+class _Candidates:
+    """A checked ``candidates=`` argument in the library's form: ``offsets``
+    (int64, m + 1) and ``ids`` (uint32), every row's ids strictly ascending
+    and below n; ``maxlen`` is the longest list."""
+
+    __slots__ = ("offsets", "ids", "maxlen")
+
+    def __init__(self, offsets, ids):
+        self.offsets, self.ids = offsets, ids
+        self.maxlen = int(np.diff(offsets).max()) if offsets.size > 1 else 0
+
+
+def _check_candidates(candidates, m: int, n: int) -> _Candidates:
+    """TypeError for lists of the wrong kind, ValueError for a wrong number
+    of lists or an id that is null, negative or no row of the corpus (naming
+    the query row): all before any device work.  A null list is empty."""
+    if isinstance(candidates, (tuple, list)) and len(candidates) == 2 and all(
+            isinstance(x, np.ndarray) for x in candidates):
+        offsets, vals = candidates
+        if offsets.dtype.kind not in "iu" or vals.dtype.kind not in "iu":
+            raise TypeError(f"candidates (offsets, ids) must be integer arrays, got {offsets.dtype} and {vals.dtype}")
+        if offsets.ndim != 1 or vals.ndim != 1:
+            raise ValueError("candidates (offsets, ids) must be 1-D arrays")
+        if offsets.size != m + 1:
+            raise ValueError(f"candidates hold {max(offsets.size - 1, 0)} lists, the queries have {m} rows")
+        offsets = offsets.astype(np.int64)
+        lens = np.diff(offsets)
+        if offsets[0] != 0 or np.any(lens < 0) or offsets[-1] != vals.size:
+            raise ValueError("candidates offsets must start at 0, not descend and end at len(ids)")
+        null = None
+    else:
+        arr = candidates
+        if _is_polars_series(arr):
+            arr = arr.rechunk().to_arrow()
+        if isinstance(arr, pa.ChunkedArray):
+            arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
+        if not isinstance(arr, pa.Array):
+            raise TypeError("candidates must be a Series or Arrow List of integer row ids, or a pair (offsets, ids) "
+                            f"of numpy arrays, got {type(candidates).__name__}")
+        t = arr.type
+        if not (pa.types.is_list(t) or pa.types.is_large_list(t)) or not pa.types.is_integer(t.value_type):
+            raise TypeError(f"candidates must be a List of integer row ids, got {t}")
+        if len(arr) != m:
+            raise ValueError(f"candidates hold {len(arr)} lists, the queries have {m} rows")
+        raw = np.asarray(arr.offsets.to_numpy(zero_copy_only=False), dtype=np.int64)
+        lens = np.diff(raw)
+        if arr.null_count:  # a null list is empty (whatever extent it has)
+            valid = np.asarray(arr.is_valid().to_numpy(zero_copy_only=False), dtype=bool)
+            lens = np.where(valid, lens, 0)
+        lo, hi = (int(raw[0]), int(raw[-1])) if m else (0, 0)
+        child = arr.values.slice(lo, hi - lo)
+        null = np.asarray(child.is_null().to_numpy(zero_copy_only=False), dtype=bool) if child.null_count else None
+        vals = (child.fill_null(0) if child.null_count else child).to_numpy(zero_copy_only=False)
+        if int(lens.sum()) != vals.size:  # null lists with an extent: take the valid lists' values
+            pos = np.repeat(raw[:-1] - lo, lens) + (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens))
+            vals = vals[pos]
+            null = null[pos] if null is not None else None
+    rows = np.repeat(np.arange(m, dtype=np.int64), lens)
+    bad = (vals >= n) if vals.dtype.kind == "u" else ((vals < 0) | (vals >= n))
+    if null is not None:
+        bad = bad | null
+    if bad.any():
+        at = int(np.argmax(bad))
+        what = "null" if null is not None and null[at] else str(int(vals[at]))
+        raise ValueError(f"candidates of row {int(rows[at])} hold the id {what}: "
+                         f"not a row of the corpus ({n} rows)")
+    # one pass over the (row, id) pairs: sorted by row, then id, duplicates dropped
+    pairs = rows * np.int64(max(n, 1)) + vals.astype(np.int64)
+    if pairs.size > 1 and not np.all(np.diff(pairs) > 0):
+        pairs = np.unique(pairs)
+        rows = pairs // np.int64(max(n, 1))
+    offsets = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=m)[:m], out=offsets[1:])
+    ids = np.ascontiguousarray(pairs - rows * np.int64(max(n, 1)), dtype=np.uint32)
+    return _Candidates(offsets, ids)
+
+
+def _candidates_union(cand: _Candidates):
+    """(U, local): the sorted union of all listed ids and the lists renumbered
+    by their place in it -- a monotone map, so order and ties are kept."""
+    U = np.unique(cand.ids)
+    return U, np.searchsorted(U, cand.ids).astype(np.uint32)
+
+
+def _topk_candidates(q, c, original, rv, cand: _Candidates, kk: int, metric_id: int):
+    """(idx (m, kk), scores f32 (m, kk), lens (m,)): row i's first lens[i]
+    slots are its top-kk among its own candidates, indices numbering c.  On
+    the cached f32 handle of the corpus when there is one of one shard (one
+    GPU); else on a handle made for the call from the rows some list names
+    (their sorted union), the lists renumbered into it and the result mapped
+    back -- one search either way."""
+    dc = None
+    devs = _native.get_devices()
+    if len(devs) <= 1:
+        dc = _cached_corpus(original, rv, c, "f32")
+        if dc is not None and dc.shards != 1:
+            dc.release()
+            dc = None
+    if dc is not None:
+        try:
+            out = dc.topk_candidates(q, cand.offsets, cand.ids, kk, metric_id)
+            _reaccount_cache(dc)
+        finally:
+            dc.release()
+        return out
+    U, local = _candidates_union(cand)
+    rows = np.ascontiguousarray(c[U])
+    if len(devs) > 1:
+        # the entry takes a handle of one shard: made on the list's first device
+        with _cache_lock:
+            _native.set_devices(devs[:1])
+            try:
+                tmp = _native.DeviceCorpus(rows)
+            finally:
+                _native.set_devices(devs)
+    else:
+        tmp = _native.DeviceCorpus(rows)
+    tmp.acquire()
+    try:
+        idx, sc, lens = tmp.topk_candidates(q, cand.offsets, local, kk, metric_id)
+    finally:
+        tmp.release()
+        tmp.close()
+    used = idx != 0xFFFFFFFF
+    idx[used] = U[idx[used]]
+    return idx, sc, lens
+
+
 def _ragged_topk_arrow(idx: np.ndarray, scores: np.ndarray, lens: np.ndarray) -> pa.Array:
     """The lists' first lens[i] entries as LargeList<Struct>: no padding reaches Arrow."""
     keep = np.arange(idx.shape[1], dtype=np.int64)[None, :] < lens.astype(np.int64)[:, None]
@@ -689,7 +831,7 @@ def _wrap(arrow_arr: pa.Array, name: str, polars_out: bool):
 # ---------------------------------------------------------------------------
 # Public extension functions
 # ---------------------------------------------------------------------------
-def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
+def _topk(left, right, k, metric, compute="f32", subset=None, groups=None, candidates=None):
     """src/lib.rs:33-55 -> src/matmul.rs:473-519 topk_impl.  compute="bf16"
     (an extension): both columns are read as f32 whatever their dtype and
     searched on the bf16 path (the numpy-level ``topk``'s compute="bf16").
@@ -705,7 +847,14 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
     row is searched only among the corpus rows with its own label; a null label
     on either side matches nothing.  The lists are ragged: row i holds
     min(k, corpus rows of its label) entries, none when the corpus has no such
-    label.  Not together with ``subset``."""
+    label.  Not together with ``subset``.
+    candidates (an extension): one list of corpus row ids per row of ``left``
+    -- a Series or Arrow List / LargeList of any integer type (a null list is
+    empty), or a pair ``(offsets, ids)`` of numpy arrays.  Every query row is
+    searched only among its own list (sorted and de-duplicated here); a null
+    or negative id or one that is no row of ``right`` raises ValueError.  The
+    lists are ragged: row i holds min(k, its candidates) entries, exact f32
+    scores.  Float32 columns only; not together with ``subset`` or ``groups``."""
     k = _as_usize(k)
     if not isinstance(metric, str):
         raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
@@ -716,6 +865,16 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
     rv = _to_arrow(right)
     if groups is not None and subset is not None:
         raise ValueError("groups= and subset= cannot be combined: give the rows to leave out a null label")
+    cand = None
+    if candidates is not None:
+        if subset is not None or groups is not None:
+            raise ValueError("candidates= cannot be combined with subset= or groups=: "
+                             "leave the rows a query must not see out of its list")
+        if bf16:
+            raise _candidates_f32_only('compute="bf16" has no candidate search')
+        if not (_is_f32(lv) and _is_f32(rv)):
+            raise _candidates_f32_only("got a column of another type")
+        cand = _check_candidates(candidates, _nrows(lv), _nrows(rv))
     sel = _check_subset(subset, _nrows(rv)) if subset is not None else None
     grp = _check_groups(groups, _nrows(lv), _nrows(rv)) if groups is not None else None
     if _nrows(lv) == 0:  # src/matmul.rs:480-487
@@ -742,6 +901,18 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None):
         raise _dim_mismatch(q.shape[1], c.shape[1])
     kk = min(k, c.shape[0] if sel is None else sel.count)  # src/matmul.rs:443
     m = q.shape[0]
+    if cand is not None:
+        kk = min(k, cand.maxlen)  # the clip-to-n rule on the longest list
+        if kk == 0:
+            idx, sc = np.zeros((m, 0), dtype=np.uint32), np.zeros((m, 0), dtype=np.float64)
+            lens = np.zeros(m, dtype=np.uint32)
+        else:
+            _apply_devices_env()
+            idx, sc, lens = _topk_candidates(q, c, right, rv, cand, kk, metric_id)
+            t = _lap("device", t)
+        out = _wrap(_ragged_topk_arrow(idx, sc, lens), "topk", polars_out)
+        _lap("assemble", t)
+        return out
     if grp is not None:
         kk = min(k, grp.searched_max())  # the clip-to-n rule on the largest searched segment
         if kk == 0:
