@@ -664,6 +664,74 @@ int pmm_topk_f32_candidates(const pmm_corpus *corpus, const float *q, int64_t m,
                             uint32_t *out_idx /* m * k */, float *out_score /* m * k */,
                             uint32_t *out_len /* m */);
 
+/* Self search: one handle searched against itself -- near-duplicate pairs and
+ * the k-nearest-neighbour graph of its rows.  Neither entry takes queries: the
+ * handle's n rows are the query rows (nothing is uploaded) and, for the range
+ * entry, its cached norms are the query norms.  Both serve an f32 handle of
+ * one shard, plain or derived by pmm_corpus_subset_* (a derived handle returns
+ * the PARENT's row numbers; "row i" and "j > i" below are handle positions,
+ * and the map ascends, so they are parent order too).  A sharded handle:
+ * PMM_ERR_UNSUPPORTED; a partitioned handle: PMM_ERR_ARG (the text of
+ * pmm_topk_f32_corpus); an f64 or bf16 handle: PMM_ERR_ARG; an int8 handle:
+ * PMM_ERR_UNSUPPORTED (as pmm_range_f32_corpus).  Every argument check comes
+ * before the handle is read.  Thread-safe like the other handle entries;
+ * no reference counterpart.
+ *
+ * pmm_range_f32_self: row i's list is the list pmm_range_f32_corpus returns
+ * for query row i when the queries are the handle's own rows, without the
+ * entries at handle positions j <= i: each unordered pair {i, j} that passes
+ * the threshold appears once, under its lower row, and the diagonal never
+ * appears whatever its score.  Indices, score bits and the best-first order
+ * are that call's; so are the cap / total protocol (out_offsets has n + 1
+ * entries; total > cap writes no list; cap = 0 with null lists counts), the
+ * NaN-threshold refusal and the folding of the two zeros.  The score of
+ * (i, j) has the bits of the dropped (j, i) for all three metrics: the chain
+ * multiplies the same pairs in the same K order, and the epilogues join the
+ * two norms by one commutative IEEE operation (cosine their product,
+ * euclidean the sum of the squared norms); the definition does not lean on
+ * it.
+ * The emit pass is the range pass on a triangular schedule: query block b
+ * (BM rows) visits corpus tile t (BN columns) iff min(n, (t + 1) BN) - 1 >
+ * b BM, the comparison column > row runs only in the tiles that reach a
+ * wave's own rows, and everything else -- K order, staging, exact score -- is
+ * the range pass's (pmm_range_self_plan reports the schedule).  Binning,
+ * sorting and decoding are the range search's; a row with more hits than
+ * PMM_RANGE_SORT_MAX is cut into pieces of that size, each sorted, and merged
+ * by rank counting as the candidate search does (the handle's ordinary top-k
+ * does not know j > i).  n = 0 or 1: PMM_OK with empty lists.  Null corpus,
+ * out_offsets or total, negative cap, cap > 0 with a null list, a bad
+ * metric: PMM_ERR_ARG. */
+int pmm_range_f32_self(const pmm_corpus *corpus, float threshold, int metric, int64_t cap,
+                       int64_t *out_offsets /* n + 1 */, uint32_t *out_idx, float *out_score, int64_t *total);
+
+/* pmm_topk_f32_self: row i's list is the ranked list of all n rows for query
+ * row i (pmm_topk_f32_corpus' order: best first, NaN last, ties to the lower
+ * index) with row i itself removed and then cut at k; 1 <= k <= n - 1 (else
+ * PMM_ERR_ARG: clip k first; a handle of one row has no neighbours).  Row
+ * stride k in out_idx / out_score (n * k entries each).
+ * The handle's ordinary route for k + 1 runs with its rows as device-resident
+ * queries inside the one host-call frame (the screened route where the shape
+ * or PMM_F32_SCREEN selects it: bit-equal by construction), then one launch
+ * (one wave per row) copies each (k + 1)-list without the entry whose index
+ * is the row's own position -- or without the last entry when k + 1 others
+ * rank above the row, e.g. exact duplicates with lower row numbers or a NaN
+ * row.  The ranked list is a total order, so this is the definition for any
+ * tie or NaN placement; asking pmm_topk_f32_corpus for k + 1 and dropping
+ * rank 0 is not. */
+int pmm_topk_f32_self(const pmm_corpus *corpus, int64_t k, int metric, uint32_t *out_idx /* n * k */,
+                      float *out_score /* n * k */);
+
+/* The triangular schedule of pmm_range_f32_self's emit pass for n rows on a
+ * device of `cus` compute units (host only, no device is touched).
+ * variant_in: 0 (128 x 128 tiles) or 3 (256 x 256), or -1 to choose as the
+ * entry does without PMM_GEMM_VARIANT.  *variant: the tile variant;
+ * *block_tile_visits: the (query block, corpus tile) pairs the pass runs;
+ * *block_tile_full: the QB * T pairs pmm_range_f32_corpus runs for the same
+ * rows as queries.  n < 0, cus < 1, another variant_in or a null output:
+ * PMM_ERR_ARG. */
+int pmm_range_self_plan(int64_t n, int cus, int variant_in, int *variant, int64_t *block_tile_visits,
+                        int64_t *block_tile_full);
+
 /* Per-kernel timing on the launch stream (hipEvents around each launch).
  * enable=1 starts recording; pmm_timing_read returns the summed milliseconds
  * and launch count of kernels whose name contains `kernel` since the last

@@ -3997,6 +3997,18 @@ int pmm_topk_f64_corpus(const pmm_corpus *h, const double *q, int64_t m, int64_t
       });
 }
 
+// The route of m query rows on an f32 handle of one shard: the screened route
+// when the shape asks for it (screen_wanted, as the device entry's) and the
+// handle has, or can now build, its ScreenImage (*img); else the f32 kernel on
+// the cached norms, as for every other metric.
+static TopkRoute f32_handle_route(const pmm_corpus *h, int64_t m, int64_t k, int metric,
+                                  const HostCall<float> &f, const ScreenImage **img) {
+  TopkRoute route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, true, true, true);
+  *img = route.kind == Route::kF32Screened ? corpus_screen_image(h, f.s) : nullptr;
+  if (!*img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, false, false);
+  return route;
+}
+
 int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t k, int metric,
                         uint32_t *out_idx, float *out_score) {
   TopkRoute route;
@@ -4004,12 +4016,7 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
   return corpus_topk(
       h, PMM_DTYPE_F32, q, m, k, metric, out_idx, out_score,
       [&](const HostCall<float> &f, Layout &) {
-        // The screened route when the shape asks for it (screen_wanted, as the
-        // device entry's) and the handle has, or can now build, its ScreenImage;
-        // else the f32 kernel on the cached norms, as for every other metric.
-        route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, true, true, true);
-        img = route.kind == Route::kF32Screened ? corpus_screen_image(h, f.s) : nullptr;
-        if (!img) route = route_topk(m, h->n, h->d, k, metric, PMM_COMPUTE_F32, g_dev[f.dev].cus, false, false);
+        route = f32_handle_route(h, m, k, metric, f, &img);
         return route.total;
       },
       [&](const HostCall<float> &f) {
@@ -4023,11 +4030,14 @@ int pmm_topk_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, int64_t 
 // Range search.  The tile variant of the emit pass: the ones
 // the range mode is instantiated for, PMM_GEMM_VARIANT (per call) choosing
 // among them, else choose_variant's size rule between 128 x 128 and 256 x 256.
+static int range_variant_by_size(int64_t m, int64_t n, int cus) {
+  return cdiv(m, 256) * cdiv(n, 256) < 4 * (int64_t)cus ? 0 : 3;
+}
 static int range_variant(int64_t m, int64_t n, int cus) {
   const char *ev = getenv("PMM_GEMM_VARIANT");
   const int env = ev ? atoi(ev) : -1;
   if (env >= 0 && gemm_f32_range_variant(env)) return env;
-  return cdiv(m, 256) * cdiv(n, 256) < 4 * (int64_t)cus ? 0 : 3;
+  return range_variant_by_size(m, n, cus);
 }
 
 // The longest segment the in-LDS sort takes: kRangeSortMax, or a lower
@@ -4038,6 +4048,24 @@ static int64_t range_sort_max() {
   const int64_t v = e ? atoll(e) : 0;
   return (v >= kRangeWaveMax && v < kRangeSortMax) ? v : kRangeSortMax;
 }
+
+// What the range and self entries (`what`) refuse in a handle.
+static int range_handle(const pmm_corpus *h, const char *what) {
+  if (h->partitioned()) return partitioned_handle(h);
+  if (h->dtype == PMM_DTYPE_I8)
+    return fail(PMM_ERR_UNSUPPORTED, "%s takes an f32 handle: an int8 handle has no %s", what, what);
+  if (h->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16"};
+    return fail(PMM_ERR_ARG, "%s takes an f32 handle: this one holds %s rows", what, kRows[h->dtype]);
+  }
+  if (h->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no %s: use a handle of one shard",
+                (int)h->shards.size(), what);
+  return PMM_OK;
+}
+
+static int range_search(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
+                        int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total);
 
 int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
                          int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
@@ -4051,20 +4079,99 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   int rc = check_metric(metric);
   if (rc) return rc;
   if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
-  if (h->partitioned()) return partitioned_handle(h);
-  if (h->dtype == PMM_DTYPE_I8)
-    return fail(PMM_ERR_UNSUPPORTED, "range search takes an f32 handle: an int8 handle has no range search");
-  if (h->dtype != PMM_DTYPE_F32) {
-    static const char *const kRows[] = {"f32", "f64", "bf16"};
-    return fail(PMM_ERR_ARG, "range search takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
-  }
-  if (h->shards.size() != 1)
-    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no range search: use a handle of one shard",
-                (int)h->shards.size());
+  return range_search(h, q, m, threshold, metric, cap, out_offsets, out_idx, out_score, total);
+}
+
+int pmm_range_f32_self(const pmm_corpus *h, float threshold, int metric, int64_t cap, int64_t *out_offsets,
+                       uint32_t *out_idx, float *out_score, int64_t *total) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!out_offsets || !total) return fail(PMM_ERR_ARG, "null argument");
+  if (cap < 0) return fail(PMM_ERR_ARG, "negative size (cap=%lld)", (long long)cap);
+  if (cap > 0 && (!out_idx || !out_score))
+    return fail(PMM_ERR_ARG, "null argument: cap > 0 needs out_idx and out_score (cap = 0 is the count-only form)");
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
+  return range_search(h, nullptr, 0, threshold, metric, cap, out_offsets, out_idx, out_score, total);
+}
+
+int pmm_topk_f32_self(const pmm_corpus *h, int64_t k, int metric, uint32_t *out_idx, float *out_score) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!out_idx || !out_score) return fail(PMM_ERR_ARG, "null argument");
+  if (k < 1) return fail(PMM_ERR_ARG, "k must be >= 1 (got %lld)", (long long)k);
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if ((rc = range_handle(h, "self search"))) return rc;
+  const int64_t n = h->n;
+  if (k >= n)
+    return fail(PMM_ERR_ARG, "k (%lld) must be <= n - 1 (n = %lld): a row has n - 1 neighbours, clip k first",
+                (long long)k, (long long)n);
+  if ((rc = validate_sizes(n, n, h->d, k + 1, true))) return rc;
+  // The handle's route for k + 1 with its own rows as the (device-resident)
+  // queries, into lists of the entry's own; the drop-self pass writes the
+  // frame's k-lists from them, ahead of a derived handle's remap, so a row's
+  // own id is its position.
+  TopkRoute route;
+  const ScreenImage *img = nullptr;
+  size_t off_i1 = 0, off_s1 = 0;
+  return host_topk(
+      h, HostRows{}, HostRows{}, n, k, out_idx, out_score,
+      [&](const HostCall<float> &f, Layout &L) {
+        off_i1 = L.take((size_t)n * (k + 1) * 4), off_s1 = L.take((size_t)n * (k + 1) * 4);
+        route = f32_handle_route(h, n, k + 1, metric, f, &img);
+        return route.total;
+      },
+      [&](const HostCall<float> &f) -> int {
+        const CorpusShard &x = h->shards[0];
+        uint32_t *i1 = (uint32_t *)(f.b + off_i1);
+        float *s1 = (float *)(f.b + off_s1);
+        if (int rc2 = topk_f32_device_impl(route, x.rows_as<float>(), h->dp, n, x.rows_as<float>(), h->dp, n, h->d, k + 1,
+                                           metric, 0u, i1, s1, f.w, f.ws_bytes, f.s, f.dev,
+                                           shard_norms<float>(h, x, metric), false, img))
+          return rc2;
+        Timed t("drop_self", f.s);
+        HIP_TRY(launch_drop_self(i1, s1, n, k, f.oi, f.os, f.s));
+        return PMM_OK;
+      });
+}
+
+int pmm_range_self_plan(int64_t n, int cus, int variant_in, int *variant, int64_t *block_tile_visits,
+                        int64_t *block_tile_full) {
+  if (!variant || !block_tile_visits || !block_tile_full) return fail(PMM_ERR_ARG, "null argument");
+  if (n < 0 || n > INT32_MAX || cus < 1 || (variant_in != -1 && !gemm_f32_range_variant(variant_in)))
+    return fail(PMM_ERR_ARG, "bad self plan arguments (n=%lld cus=%d variant=%d: the variant is 0, 3 or -1)",
+                (long long)n, cus, variant_in);
+  const int v = variant_in >= 0 ? variant_in : range_variant_by_size(n, n, cus);
+  const int bm = gemm_f32_bm(v), bn = gemm_f32_bn(v);
+  const int64_t QB = cdiv(n, bm), T = cdiv(n, bn);
+  int64_t visits = 0;
+  for (int64_t b = 0; b < QB; b++) visits += T - self_first_tile((int)n, (int)(b * bm), bn, (int)T);
+  *variant = v;
+  *block_tile_visits = visits;
+  *block_tile_full = QB * T;
+  return PMM_OK;
+}
+
+// The body of both range entries, their arguments checked.  q = nullptr is the
+// self form: the handle's rows are the m = n query rows and its norms their
+// norms, nothing is uploaded, the emit pass runs the triangular schedule
+// (launch_gemm_f32_self) and a row records only its hits at positions above it.
+static int range_search(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
+                        int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
+  const bool self = q == nullptr;
+  int rc = range_handle(h, self ? "self search" : "range search");
+  if (rc) return rc;
+  if (self) m = h->n;
   if ((rc = validate_sizes(m, h->n, h->d, 0, false))) return rc;
   *total = 0;
   out_offsets[0] = 0;
   if (m == 0) return PMM_OK;
+  if (self && m == 1) {  // (one row has no pair)
+    out_offsets[1] = 0;
+    return PMM_OK;
+  }
 
   const CorpusShard &x = h->shards[0];
   int dev;
@@ -4078,13 +4185,19 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   p.variant = range_variant(m, n, cus);
   const int bn = gemm_f32_bn(p.variant);
   plan_units(m, n, gemm_f32_bm(p.variant), bn, cus, 0.5, 1 << 20, p);
-  // the record arena never needs more than m x n records
-  const uint64_t rcap = (uint64_t)std::min<int64_t>(cap, m * n);
+  // the record arena never needs more than m x n records (self: the pairs)
+  const uint64_t rcap = (uint64_t)std::min<int64_t>(cap, self ? n * (n - 1) / 2 : m * n);
+  // self: a row past the in-LDS sort is cut into pieces (below); of tot <= rcap
+  // keys, at most rcap / 128 pieces more than rows and rcap / 64 cut pieces
+  const size_t max_pieces = self ? (size_t)m + rcap / kRangeWaveMax + 1 : 0;
+  const size_t max_cut = self ? rcap / (kRangeWaveMax / 2) + 1 : 0;
 
   // arena: queries | [work counter, cursor | hit counts | bin cursors] (one
   // fill) | query norms | offsets | row list | survivor queues | records (key,
   // row) | binned keys; the decoded lists reuse the record keys' bytes
-  size_t off = al256((size_t)m * dp * 4);
+  // (self: no queries and no query norms; a piece list for the row list, and
+  // the piece bounds and cut pieces at the end)
+  size_t off = self ? 0 : al256((size_t)m * dp * 4);
   const size_t off_ctl = off;
   off += 256;
   const size_t off_hits = off;
@@ -4092,11 +4205,11 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   const size_t off_cur = off;
   off += al256((size_t)m * 4);
   const size_t off_qn = off;
-  off += al256((size_t)m * 4);
+  off += self ? 0 : al256((size_t)m * 4);
   const size_t off_offs = off;
   off += al256((size_t)(m + 1) * 8);
   const size_t off_rows = off;
-  off += al256((size_t)m * 4);
+  off += al256((self ? max_pieces : (size_t)m) * 4);
   const size_t off_wq = off;
   off += al256((size_t)p.grid * gemm_f32_nw(p.variant) * 32 * bn * 8);
   const size_t off_rkey = off;
@@ -4105,16 +4218,20 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   off += al256((size_t)rcap * 4);
   const size_t off_keys = off;
   off += al256((size_t)rcap * 8);
+  const size_t off_po = off;
+  off += al256((max_pieces + 1) * 8);
+  const size_t off_cut = off;
+  off += al256(max_cut * sizeof(CandPiece));
   void *base;
   if ((rc = arena(dev, s, off, &base))) return rc;
   char *b = (char *)base;
-  const float *dq = (const float *)b;
-  if ((rc = upload_padded(b, q, m, d, dp, 4, s))) return rc;
+  const float *dq = self ? x.rows_as<float>() : (const float *)b;
+  if (!self && (rc = upload_padded(b, q, m, d, dp, 4, s))) return rc;
   HIP_TRY(hipMemsetAsync(b + off_ctl, 0, off_qn - off_ctl, s));
-  float *qn = (float *)(b + off_qn);
-  if (metric != kMetricDot) {
+  const float *qn = self ? shard_norms<float>(h, x, metric) : (const float *)(b + off_qn);
+  if (!self && metric != kMetricDot) {
     Timed t("norms_f32", s);
-    HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+    HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, (float *)(b + off_qn), nullptr, s));
   }
   // the threshold's composite: okey32 of its ranking value (-0 folds onto +0,
   // so both zeros compare alike), index part 0 -- at or above it is a hit
@@ -4149,7 +4266,10 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   a.rkey = (unsigned long long *)(b + off_rkey);
   a.rrow = (uint32_t *)(b + off_rrow);
   a.rcap = rcap;
-  {
+  if (self) {
+    Timed t("gemm_f32_self", s);
+    HIP_TRY(launch_gemm_f32_self(a, p.variant, p.grid, s));
+  } else {
     Timed t("gemm_f32_range", s);
     HIP_TRY(launch_gemm_f32_range(a, p.variant, p.grid, s));
   }
@@ -4171,7 +4291,7 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   if (tot > cap || tot == 0) return PMM_OK;
 
   // rows by sort tier: (128, smax] in a workgroup's LDS, longer ones by the
-  // handle's ordinary top-k at the end
+  // handle's ordinary top-k at the end (self: cut into pieces, below)
   const int64_t smax = range_sort_max();
   std::vector<int> mid, longr;
   int64_t mid_max = 0;
@@ -4190,15 +4310,65 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
     Timed t("range_bin", s);
     HIP_TRY(launch_range_bin(a.rkey, a.rrow, tot, d_offs, (unsigned *)(b + off_cur), keys, s));
   }
+  // Self, with a row past the in-LDS sort: the handle's top-k does not know
+  // j > i, so such a row is cut into pieces of smax keys, every piece sorted by
+  // the same two kernels over the piece bounds, and the row's whole order
+  // merged by rank counting (the candidate search's cand_merge_kernel, kout =
+  // the row's count) into the record keys' bytes, free since the bin pass, and
+  // copied back to the row's segment.
+  std::vector<int64_t> po;
+  std::vector<CandPiece> cut;
+  const int64_t *d_po = d_offs;  // (without a cut row the pieces are the rows)
+  if (self && !longr.empty()) {
+    mid.clear();
+    mid_max = 0;
+    int64_t ltotal = 0;
+    po.push_back(0);
+    for (int64_t i = 0; i < m; i++) {
+      const int64_t o = out_offsets[i], c = (int64_t)hits[(size_t)i];
+      const int64_t T = c > smax ? cdiv(c, smax) : 1;
+      if (T > 1) {
+        for (int64_t t = 0; t < T; t++)
+          cut.push_back(CandPiece{(uint32_t)(po.size() - 1 + t), (uint32_t)(po.size() - 1), (uint32_t)T, (uint32_t)c,
+                                  ltotal});
+        ltotal += c;
+      }
+      for (int64_t t = 0; t < T; t++) {
+        const int64_t len = std::min(smax, c - t * smax);
+        if (len > kRangeWaveMax) {
+          mid.push_back((int)(po.size() - 1));
+          mid_max = std::max(mid_max, len);
+        }
+        po.push_back(o + t * smax + len);
+      }
+    }
+    if (po.size() > max_pieces + 1 || cut.size() > max_cut || po.size() - 1 > (size_t)INT32_MAX)
+      return fail(PMM_ERR_HIP, "self search: %zu pieces, %zu of cut rows, past the arena's tables", po.size() - 1,
+                  cut.size());
+    HIP_TRY(hipMemcpyAsync(b + off_po, po.data(), po.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + off_cut, cut.data(), cut.size() * sizeof(CandPiece), hipMemcpyHostToDevice, s));
+    d_po = (const int64_t *)(b + off_po);
+  }
   {
     Timed t("range_sort_wave", s);
-    HIP_TRY(launch_range_sort_wave(keys, d_offs, (int)m, s));
+    HIP_TRY(launch_range_sort_wave(keys, d_po, d_po == d_offs ? (int)m : (int)(po.size() - 1), s));
   }
   if (!mid.empty()) {
     HIP_TRY(hipMemcpyAsync(b + off_rows, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, s));
     Timed t("range_sort_block", s);
-    HIP_TRY(launch_range_sort_block(keys, d_offs, (const int *)(b + off_rows), (int)mid.size(),
+    HIP_TRY(launch_range_sort_block(keys, d_po, (const int *)(b + off_rows), (int)mid.size(),
                                     next_pow2((int)mid_max), s));
+  }
+  if (!cut.empty()) {
+    Timed t("cand_merge", s);
+    HIP_TRY(launch_cand_merge(keys, d_po, (const CandPiece *)(b + off_cut), (int)cut.size(), a.rkey, s));
+    int64_t lo = 0;
+    for (const int row : longr) {
+      const int64_t c = (int64_t)hits[(size_t)row];
+      HIP_TRY(hipMemcpyAsync(keys + out_offsets[row], a.rkey + lo, (size_t)c * 8, hipMemcpyDeviceToDevice, s));
+      lo += c;
+    }
+    longr.clear();  // (served)
   }
   RangeDecodeArgs da{};
   da.keys = keys;
@@ -4214,7 +4384,7 @@ int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float t
   da.cn = a.cn;
   da.ldq = dp;
   da.ldc = dp;
-  da.out_idx = (uint32_t *)(b + off_rkey);  // (the records are binned: their bytes are free)
+  da.out_idx = (uint32_t *)(b + off_rkey);  // (the records are binned, a cut row merged: their bytes are free)
   da.out_score = (float *)(b + off_rkey + (size_t)tot * 4);
   {
     Timed t("range_decode", s);

@@ -149,6 +149,18 @@ size_t gemm_f32_lds_bytes(int variant, int mode, int capg);
 // for the variants gemm_f32_range_variant names (0 and 3).
 bool gemm_f32_range_variant(int variant);
 hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hipStream_t s);
+// mode 3 = self (pmm_range_f32_self): range mode with the corpus rows as the
+// query rows (a.q = a.c, a.qn = a.cn, M = N), emitting only the pairs (row,
+// column > row).  Unit (split, block) runs the split's tiles t with
+// min(N, (t + 1) BN) - 1 > block * BM and is skipped when none is left; the
+// filter column > row runs in the tiles that reach a wave's own rows.
+hipError_t launch_gemm_f32_self(const GemmF32Args &a, int variant, int grid, hipStream_t s);
+// The first tile (of ntiles tiles of bn columns over n rows) a query block
+// starting at row0 visits in self mode, ntiles when it visits none: the rule is
+// monotone in t, and (t + 1) bn - 1 > row0 first holds at t = (row0 + 1) / bn.
+__host__ __device__ inline int self_first_tile(int n, int row0, int bn, int ntiles) {
+  return n - 1 > row0 ? (row0 + 1) / bn : ntiles;
+}
 // ---- range search: records -> per-row best-first lists (pmm_range.hip) ----
 // Segments of up to kRangeWaveMax keys sort in one wave's registers, up to
 // kRangeSortMax in one workgroup's LDS (64 KiB of keys).
@@ -178,6 +190,10 @@ struct RangeDecodeArgs {
 };
 // keys -> (index, score) by the top-k epilogue's rules
 hipError_t launch_range_decode(const RangeDecodeArgs &a, hipStream_t s);
+// out[row][0 .. k) = in[row][0 .. k] without the entry whose index is `row`
+// (or without the last one when there is none)
+hipError_t launch_drop_self(const uint32_t *in_idx, const float *in_score, int64_t m, int64_t k, uint32_t *out_idx,
+                            float *out_score, hipStream_t s);
 // ---- candidate search: per-row candidate lists (pmm_candidates.hip) ----
 // One work unit of the score pass = one workgroup: query row `row` against
 // its candidates [start, start + kCandUnit) (places in the row's list).

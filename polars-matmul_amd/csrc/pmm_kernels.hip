@@ -294,8 +294,18 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
       const int qbb = MODE == 0 ? a.QB - a.qb_full : a.QB;
       s = u2 / qbb;
       qb = (MODE == 0 ? a.qb_full : 0) + (u2 - s * qbb);
+      // self mode: the splits last to first, so the units that every block
+      // runs whole go out first and the ones the diagonal cuts short last
+      if (MODE == 3) s = a.S - 1 - s;
       t0 = s * a.tps;
       t1 = min(t0 + a.tps, a.ntiles);
+    }
+    if (MODE == 3) {
+      // self mode (queries = corpus rows): only tiles with a column above the
+      // block's first row, min(N, (t + 1) BN) - 1 > qb BM, hold a pair (row,
+      // column > row); the rule is monotone in t, so it clamps t0
+      t0 = max(t0, self_first_tile(a.N, qb * G::BM, G::BN, a.ntiles));
+      if (t0 >= t1) continue;  // (the whole workgroup: no barrier is pending)
     }
     const int wrow0 = qb * G::BM + rg * 32;
     const int seg = CSP ? 2 * s + half : s;  // this wave's candidate segment
@@ -315,7 +325,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         lo_w[lane] = prefilter_bound<METRIC>(t, qv);
         cnt_w[lane] = 0u;
       }
-      if (MODE == 2) {
+      if (MODE >= 2) {
         // range mode: the call's threshold composite for every row (its key is
         // never 0 or ~0, prefilter_bound's reserved values); the bound is fixed
         // for the unit, cnt_w counts the row's hits of this unit
@@ -718,13 +728,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
           n_surv += (uint64_t)qlen;
         }
         if (PMM_ABL(a.ablate) == 2) qlen = 0;  // ablation: pre-filter only
-        if (MODE == 2) {
+        if (MODE >= 2) {
           // ---- range epilogue, pass 2: every queued element re-scored exactly
           // and compared with the threshold composite (at or above it: a hit;
           // a NaN score's key 0 is below every threshold's).  The wave's hits
           // of a batch take consecutive record slots from one add on the global
           // cursor; a slot at or past the arena's capacity is counted, not
           // stored.  The rows' counts gather in LDS until the unit ends.
+          // Self mode: in a tile that reaches down to this wave's rows (a
+          // wave-uniform test) a hit is also above the diagonal, column > row;
+          // every other visited tile lies wholly above it.
+          const bool diag = MODE == 3 && col0 <= wrow0 + 31;
           if (qlen) {
             if (!G::CNL || qlen > a.qcap) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (G::CNL) wave_sync();
@@ -745,6 +759,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
                 const uint32_t key = okey32(METRIC == kMetricEuclidean ? -sc : sc);
                 comp = ((u64)key << 32) | (u64)(~(uint32_t)gcol);
                 hit = comp >= thr_w[rl];
+                if (diag) hit = hit && gcol > wrow0 + rl;
               }
               const u64 hm = __ballot(hit);
               if (hm) {
@@ -814,7 +829,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         if (grow < a.M) a.cnt[(int64_t)grow * a.S + seg] = cnt_w[lane];
       }
     }
-    if (MODE == 2) {
+    if (MODE >= 2) {
       // one add per row this unit touched
       wave_sync();
       if (lane < 32) {
@@ -903,23 +918,32 @@ hipError_t launch_gemm_f32(const GemmF32Args &a, int variant, int mode, int grid
   }
 }
 
-// Range mode (MODE 2; pmm_range_f32_corpus): the 128 x 128 and 256 x 256
-// variants, every metric.
-template <int NB, int NW, bool AK>
+// Range mode (MODE 2; pmm_range_f32_corpus) and self mode (MODE 3;
+// pmm_range_f32_self: the corpus rows are the query rows, pairs above the
+// diagonal only): the 128 x 128 and 256 x 256 variants, every metric.
+template <int NB, int NW, int MODE, bool AK>
 static hipError_t launch_gemm_f32_range_v(const GemmF32Args &a, int grid, size_t lds, hipStream_t s) {
-  if (a.metric == kMetricCosine) return launch_gemm_f32_t<NB, NW, 2, kMetricCosine, AK>(a, grid, lds, s);
-  if (a.metric == kMetricDot) return launch_gemm_f32_t<NB, NW, 2, kMetricDot, AK>(a, grid, lds, s);
-  return launch_gemm_f32_t<NB, NW, 2, kMetricEuclidean, AK>(a, grid, lds, s);
+  if (a.metric == kMetricCosine) return launch_gemm_f32_t<NB, NW, MODE, kMetricCosine, AK>(a, grid, lds, s);
+  if (a.metric == kMetricDot) return launch_gemm_f32_t<NB, NW, MODE, kMetricDot, AK>(a, grid, lds, s);
+  return launch_gemm_f32_t<NB, NW, MODE, kMetricEuclidean, AK>(a, grid, lds, s);
 }
 bool gemm_f32_range_variant(int variant) { return variant == 0 || variant == 3; }
-hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
-  if (variant == 3) return launch_gemm_f32_range_v<8, 8, false>(a, grid, gemm_f32_lds_bytes(3, 2, 0), s);
+template <int MODE>
+static hipError_t launch_gemm_f32_range_m(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
+  if (variant == 3) return launch_gemm_f32_range_v<8, 8, MODE, false>(a, grid, gemm_f32_lds_bytes(3, 2, 0), s);
   if (variant != 0) return hipErrorInvalidValue;
   // (resident query rows as launch_gemm_f32_small decides them)
   const size_t ak = gemm_f32_lds_bytes_ak(0, 2, 0, a.D >> 5);
   static const int ak_env = getenv("PMM_F32_AK") ? atoi(getenv("PMM_F32_AK")) : PMM_F32_AK;
-  if (ak_env && a.tps > 1 && ak <= 160 * 1024) return launch_gemm_f32_range_v<4, 4, true>(a, grid, ak, s);
-  return launch_gemm_f32_range_v<4, 4, false>(a, grid, gemm_f32_lds_bytes(0, 2, 0), s);
+  if (ak_env && a.tps > 1 && ak <= 160 * 1024) return launch_gemm_f32_range_v<4, 4, MODE, true>(a, grid, ak, s);
+  return launch_gemm_f32_range_v<4, 4, MODE, false>(a, grid, gemm_f32_lds_bytes(0, 2, 0), s);
+}
+hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
+  return launch_gemm_f32_range_m<2>(a, variant, grid, s);
+}
+hipError_t launch_gemm_f32_self(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
+  if (a.q != a.c || a.M != a.N || a.ldq != a.ldc) return hipErrorInvalidValue;
+  return launch_gemm_f32_range_m<3>(a, variant, grid, s);
 }
 
 // ===========================================================================

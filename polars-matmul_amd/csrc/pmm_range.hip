@@ -1,4 +1,5 @@
-// pmm_range.hip -- range search (pmm_range_f32_corpus): the
+// pmm_range.hip -- range search (pmm_range_f32_corpus, pmm_range_f32_self;
+// DESIGN.md §4d), with the self top-k's drop-self pass at the end: the
 // passes that turn the records the f32 GEMM's range mode emitted (composite
 // key + query row, in no order) into per-row, best-first lists.  Bin: every
 // key to its row's segment of the CSR layout.  Sort: a segment's keys are
@@ -103,6 +104,38 @@ __global__ __launch_bounds__(256) void range_decode_kernel(RangeDecodeArgs a) {
   }
 }
 
+// Self top-k (pmm_topk_f32_self): row i's ranked (k + 1)-list of the handle's
+// rows, searched with the rows themselves as queries, minus row i -- the entry
+// whose index is the row's own handle position (the lists are not yet mapped
+// to a derived handle's parent numbers), or the last entry when the row is not
+// in its list (k + 1 others rank above it).  The ranked list is a total
+// order, so what is left is the first k of the row's ranking without itself.
+// One wave per row, 64 entries at a time.
+__global__ __launch_bounds__(256) void drop_self_kernel(const uint32_t *__restrict__ in_idx,
+                                                        const float *__restrict__ in_score, int m, int k,
+                                                        uint32_t *__restrict__ out_idx,
+                                                        float *__restrict__ out_score) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (row >= m) return;  // (the whole wave)
+  const uint32_t *ii = in_idx + (int64_t)row * (k + 1);
+  const float *is = in_score + (int64_t)row * (k + 1);
+  int p = k;  // the place to drop
+  for (int j0 = 0; j0 <= k; j0 += 64) {
+    const int j = j0 + lane;
+    const u64 found = __ballot(j <= k && ii[j] == (uint32_t)row);
+    if (found) {
+      p = j0 + __builtin_ctzll(found);
+      break;
+    }
+  }
+  for (int j = lane; j < k; j += 64) {
+    const int src = j + (j >= p ? 1 : 0);
+    out_idx[(int64_t)row * k + j] = ii[src];
+    out_score[(int64_t)row * k + j] = is[src];
+  }
+}
+
 static unsigned range_grid(int64_t count) {
   const int64_t blocks = (count + 255) / 256;
   return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));
@@ -132,6 +165,14 @@ hipError_t launch_range_sort_block(unsigned long long *keys, const int64_t *offs
 hipError_t launch_range_decode(const RangeDecodeArgs &a, hipStream_t s) {
   if (a.total <= 0) return hipSuccess;
   range_decode_kernel<<<range_grid(a.total), 256, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_drop_self(const uint32_t *in_idx, const float *in_score, int64_t m, int64_t k, uint32_t *out_idx,
+                            float *out_score, hipStream_t s) {
+  if (m <= 0 || k <= 0) return hipSuccess;
+  if (m > INT32_MAX || k >= INT32_MAX) return hipErrorInvalidValue;
+  drop_self_kernel<<<(unsigned)((m + 3) / 4), 256, 0, s>>>(in_idx, in_score, (int)m, (int)k, out_idx, out_score);
   return hipGetLastError();
 }
 

@@ -20,7 +20,12 @@ extension, on all three) gives every query row its own list of corpus row ids
 one call, exact f32 scores, on Float32 columns.  ``.pmm.within(corpus,
 threshold, metric)`` (an extension; ``within`` / ``_within`` without Polars) is
 range search: every corpus row whose score passes the threshold, as ragged
-lists, on Float32 columns.  The numerics run on MI355X through hand-written HIP
+lists, on Float32 columns.  ``.pmm.within_self(threshold, metric)`` and
+``.pmm.topk_self(k, metric)`` (extensions; ``within_self`` / ``topk_self`` and
+``_within_self`` / ``_topk_self`` without Polars) search one column against
+itself -- every near-duplicate pair once, and the k-nearest-neighbour graph of
+its rows -- with the column's cached handle as its own query side.  The
+numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
 Usage:
@@ -50,14 +55,16 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     _check_subset,
     _matmul,
     _topk,
+    _topk_self,
     _within,
+    _within_self,
     get_devices,
     set_devices,
 )
 from polars_matmul import _native
 
 __version__ = "0.1.4"
-__all__ = ["PmmNamespace", "topk", "within", "matmul", "set_devices", "get_devices"]
+__all__ = ["PmmNamespace", "topk", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
 Compute = Literal["f32", "bf16"]
@@ -213,6 +220,64 @@ def within(queries: np.ndarray, corpus: np.ndarray, threshold: float, metric: Me
     return offsets, idx, sc.astype(np.float64)
 
 
+def _self_matrix(corpus) -> np.ndarray:
+    from polars_matmul._polars_matmul import _self_f32_only
+
+    c = np.asarray(corpus)
+    if c.dtype != np.float32:
+        raise _self_f32_only(f"got a {c.dtype} matrix")
+    if c.ndim != 2:
+        raise TypeError(f"expected a 2-D array of embeddings, got shape {c.shape}")
+    return c
+
+
+def within_self(corpus: np.ndarray, threshold: float, metric: Metric = "cosine", compute: Compute = "f32"):
+    """numpy-level self range search (an extension): the near-duplicate pairs
+    of one matrix.  Returns CSR arrays (offsets int64 [n + 1], indices uint32
+    [total], scores float64 [total]): row i's entries are ``within(corpus,
+    corpus, ...)``'s for row i without those at j <= i -- each pair once, under
+    its lower row, never a row with itself -- same scores, best first.  (The
+    dropped (j, i) has the same score bits as the kept (i, j), for every
+    metric.)  The rows are uploaded once, as the cached handle, and are their
+    own queries.  Float32 matrices only (Float64 input and compute="bf16" raise
+    TypeError); the corpus cache as in ``within``."""
+    from polars_matmul._polars_matmul import _self_device, _self_f32_only
+
+    if _native.check_compute(compute) == "bf16":
+        raise _self_f32_only('compute="bf16" has no self search')
+    c = _self_matrix(corpus)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    metric_id = _native.metric_from_str(metric)
+    if c.shape[0] == 0:
+        return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float64)
+    cc = np.ascontiguousarray(c)
+    offsets, idx, sc = _self_device(cc, cc, cc, lambda dc: dc.range_self(threshold, metric_id),
+                                    numpy_ok=cc is corpus)
+    return offsets, idx, sc.astype(np.float64)
+
+
+def topk_self(corpus: np.ndarray, k: int, metric: Metric = "cosine", compute: Compute = "f32"):
+    """numpy-level self top-k (an extension): the k-nearest-neighbour graph of
+    one matrix.  Returns (indices uint32 [n, k'], scores float64 [n, k']) with
+    k' = min(k, n - 1): row i's ranked list of all rows without row i itself --
+    not ``topk(corpus, corpus, k + 1)`` minus rank 0, which drops the wrong
+    entry when an exact duplicate with a lower row number ties with the row.
+    Float32 matrices only; the corpus cache as in ``within``."""
+    from polars_matmul._polars_matmul import _self_device, _self_f32_only
+
+    if _native.check_compute(compute) == "bf16":
+        raise _self_f32_only('compute="bf16" has no self search')
+    c = _self_matrix(corpus)
+    metric_id = _native.metric_from_str(metric)
+    if c.shape[0] == 0:
+        return np.zeros((0, 0), dtype=np.uint32), np.zeros((0, 0), dtype=np.float64)
+    cc = np.ascontiguousarray(c)
+    idx, sc = _self_device(cc, cc, cc, lambda dc: dc.topk_self(int(k), metric_id), numpy_ok=cc is corpus)
+    return idx, sc.astype(np.float64)
+
+
 def matmul(queries: np.ndarray, corpus: np.ndarray) -> np.ndarray:
     """numpy-level Q @ C^T on the GPU (f32 iff both inputs are float32)."""
     q = np.asarray(queries)
@@ -333,6 +398,42 @@ if pl is not None:
             return self._expr.map_batches(
                 lambda s: _within(s, corpus, threshold, metric, **extra),
                 is_elementwise=True,
+                return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def within_self(self, threshold: float, metric: Metric = "cosine", compute: Compute = "f32") -> "pl.Expr":
+            """Self range search (an extension): for every embedding the LATER
+            rows of the same column whose score with it is >= ``threshold``
+            (cosine, dot) or <= ``threshold`` (euclidean):
+            List[Struct{index: u32, score: f64}], best first -- every
+            near-duplicate pair of the column once, no row with itself.  The
+            column is uploaded once and is its own query side.  A row's list
+            depends on the whole column, so the expression is not elementwise.
+            Float32 columns only."""
+            if _native.check_compute(compute) == "bf16":
+                from polars_matmul._polars_matmul import _self_f32_only
+
+                raise _self_f32_only('compute="bf16" has no self search')
+            return self._expr.map_batches(
+                lambda s: _within_self(s, threshold, metric),
+                is_elementwise=False,
+                return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def topk_self(self, k: int, metric: Metric = "cosine", compute: Compute = "f32") -> "pl.Expr":
+            """Self top-k (an extension): for every embedding its min(k, n - 1)
+            best OTHER rows of the same column:
+            List[Struct{index: u32, score: f64}] -- the k-nearest-neighbour
+            graph.  The row itself is removed from its ranked list, so an exact
+            duplicate stays whichever of the two comes first.  Not
+            elementwise; Float32 columns only."""
+            if _native.check_compute(compute) == "bf16":
+                from polars_matmul._polars_matmul import _self_f32_only
+
+                raise _self_f32_only('compute="bf16" has no self search')
+            return self._expr.map_batches(
+                lambda s: _topk_self(s, k, metric),
+                is_elementwise=False,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
             )
 

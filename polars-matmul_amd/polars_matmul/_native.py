@@ -90,6 +90,9 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_bf16_corpus",
     "pmm_range_f32_corpus",
     "pmm_topk_f32_candidates",
+    "pmm_range_f32_self",
+    "pmm_topk_f32_self",
+    "pmm_range_self_plan",
     "pmm_topk_i8",
     "pmm_topk_i8_corpus",
     "pmm_topk_i8_device",
@@ -202,6 +205,10 @@ _SIGS = {
     "pmm_range_f32_corpus": ([_vp, _vp, _i64, ctypes.c_float, _i32, _i64, _vp, _vp, _vp,
                               ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_candidates": ([_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
+    "pmm_range_f32_self": ([_vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_topk_f32_self": ([_vp, _i64, _i32, _vp, _vp], _i32),
+    "pmm_range_self_plan": ([_i64, _i32, _i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_i8": ([_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
@@ -278,6 +285,16 @@ def get_devices():
     arr = (ctypes.c_int * max(1, n.value))()
     check(_lib.pmm_get_devices(arr, n.value, ctypes.byref(n)))
     return list(arr[:n.value])
+
+
+def range_self_plan(n: int, cus: int, variant: int = -1):
+    """The triangular schedule of the self range search's emit pass
+    (pmm_range_self_plan; pure, no GPU): (variant, block_tile_visits,
+    block_tile_full) for n rows on a device of ``cus`` compute units."""
+    v = ctypes.c_int(0)
+    visits, full = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.pmm_range_self_plan(n, cus, variant, ctypes.byref(v), ctypes.byref(visits), ctypes.byref(full)))
+    return int(v.value), int(visits.value), int(full.value)
 
 
 def shard_plan(devs, m: int, n: int, d: int, k: int, metric: int, compute: int = COMPUTE_F32,
@@ -825,6 +842,56 @@ class DeviceCorpus:
         finally:
             self.release()
         return offsets, idx[:total.value], sc[:total.value]
+
+    def range_self(self, threshold: float, metric: int, cap=None):
+        """(offsets int64 (n + 1,), idx uint32 (total,), scores float32
+        (total,)) of pmm_range_f32_self: the handle searched against itself,
+        each pair once.  Row i's entries are ``range(rows, ...)``'s for query
+        row i without those at positions j <= i (a derived handle returns its
+        parent's row numbers; positions are the handle's), same score bits,
+        best first.  No rows are uploaded.  The dropped (j, i) has the bits of
+        the kept (i, j) for every metric.  ``cap`` as for ``range``: default
+        ``RANGE_CAP_PER_ROW`` per row, at least ``RANGE_CAP_MIN``, at most
+        n (n - 1) / 2; repeated once with the exact total when too small."""
+        n = self.n
+        pairs = n * (n - 1) // 2
+        if cap is None:
+            cap = max(self.RANGE_CAP_MIN, self.RANGE_CAP_PER_ROW * n)
+        cap = max(0, min(int(cap), pairs))
+        offsets = np.empty(n + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        self.acquire()
+        try:
+            while True:
+                idx = np.empty(cap, dtype=np.uint32)
+                sc = np.empty(cap, dtype=np.float32)
+                check(_lib.pmm_range_f32_self(self._h, float(threshold), metric, cap, ptr(offsets),
+                                              ptr(idx) if cap else None, ptr(sc) if cap else None,
+                                              ctypes.byref(total)))
+                if total.value <= cap:
+                    break
+                cap = total.value  # too small: once more, with room
+        finally:
+            self.release()
+        return offsets, idx[:total.value], sc[:total.value]
+
+    def topk_self(self, k: int, metric: int):
+        """(idx uint32 (n, k'), scores float32 (n, k')) of pmm_topk_f32_self:
+        row i's k' = min(k, n - 1) best other rows of the handle -- its ranked
+        list of all rows without itself, so an exact duplicate with a lower row
+        number is kept and the row itself dropped.  No rows are uploaded."""
+        n = self.n
+        k = max(0, min(int(k), n - 1))
+        idx = np.empty((n, k), dtype=np.uint32)
+        sc = np.empty((n, k), dtype=np.float32)
+        if k == 0:  # (a handle of one row: empty lists)
+            return idx, sc
+        self.acquire()
+        try:
+            check(_lib.pmm_topk_f32_self(self._h, k, metric, ptr(idx), ptr(sc)))
+        finally:
+            self.release()
+        return idx, sc
 
     def topk_candidates(self, q: np.ndarray, offsets, ids, k: int, metric: int):
         """(idx uint32 (m, k), scores float32 (m, k), lens uint32 (m,)) of

@@ -1054,6 +1054,99 @@ def _within(left, right, threshold, metric, subset=None, compute="f32"):
     return _wrap(_csr_arrow(offsets, idx, sc), "within", polars_out)
 
 
+# ---------------------------------------------------------------------------
+# Self search (an extension; no reference counterpart): one column against
+# itself -- near-duplicate pairs (``_within_self``) and the k-nearest-neighbour
+# graph of its rows (``_topk_self``).  The column's cached f32 handle is its
+# own query side (include/pmm.h pmm_range_f32_self, pmm_topk_f32_self): nothing
+# but the corpus is uploaded, and that once.
+# ---------------------------------------------------------------------------
+def _self_f32_only(what: str) -> TypeError:
+    return TypeError(
+        f"self search runs on Float32 columns ({what}); cast the embeddings first, e.g. "
+        "pl.col('embedding').cast(pl.List(pl.Float32)) or array.astype(numpy.float32)"
+    )
+
+
+def _self_device(c, original, rv, run, numpy_ok: bool = False):
+    """``run(handle)`` on the cached f32 handle of c, or on one made for the
+    call when c is not cacheable.  With a device list the handle is sharded and
+    the library's unsupported error surfaces."""
+    dc = _cached_corpus(original, rv, c, "f32", numpy_ok)
+    own = dc is None
+    if own:
+        dc = _native.DeviceCorpus(c).acquire()
+    try:
+        out = run(dc)
+        if not own:
+            _reaccount_cache(dc)
+        return out
+    finally:
+        dc.release()
+        if own:
+            dc.close()
+
+
+def _self_column(col, metric):
+    """(polars_out, arrow column) of a self entry's Float32 column."""
+    if not isinstance(metric, str):
+        raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
+    polars_out = _is_polars_series(col)
+    rv = _to_arrow(col)
+    if not _is_f32(rv):
+        raise _self_f32_only("got a column of another type")
+    return polars_out, rv
+
+
+def _self_metric(metric: str) -> int:
+    try:
+        return _native.metric_from_str(metric)
+    except _native.PmmError as e:  # src/metrics.rs:25 text
+        raise _compute_error(str(e)) from None
+
+
+def _within_self(col, threshold, metric):
+    """Self range search (an extension): for every row i of ``col`` the rows
+    j > i whose score with it is >= ``threshold`` (cosine, dot) or <=
+    ``threshold`` (euclidean), as List[Struct{index: UInt32, score: Float64}]
+    named "within_self", best first, ragged: ``_within(col, col, ...)`` with
+    each pair kept once, under its lower row, and no row paired with itself.
+    (The dropped (j, i) has the same score bits, for every metric.)  Float32
+    columns only."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise TypeError(f"threshold must be a number, not {type(threshold).__name__}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    polars_out, rv = _self_column(col, metric)
+    if _nrows(rv) == 0:
+        return _wrap(pa.array([], type=pa.large_list(_TOPK_STRUCT)), "within_self", polars_out)
+    metric_id = _self_metric(metric)
+    c = _series_to_matrix(rv, np.float32)
+    _apply_devices_env()
+    offsets, idx, sc = _self_device(c, col, rv, lambda dc: dc.range_self(threshold, metric_id))
+    return _wrap(_csr_arrow(offsets, idx, sc), "within_self", polars_out)
+
+
+def _topk_self(col, k, metric):
+    """Self top-k (an extension): for every row of ``col`` its min(k, n - 1)
+    best OTHER rows, as List[Struct{index: UInt32, score: Float64}] named
+    "topk_self": the row's ranked list of the whole column without the row
+    itself -- so an exact duplicate stays, whichever of the two has the lower
+    row number.  A column of one row gives one empty list.  Float32 columns
+    only."""
+    k = _as_usize(k)
+    polars_out, rv = _self_column(col, metric)
+    n = _nrows(rv)
+    if n == 0:
+        return _wrap(pa.array([], type=pa.large_list(_TOPK_STRUCT)), "topk_self", polars_out)
+    metric_id = _self_metric(metric)
+    c = _series_to_matrix(rv, np.float32)
+    _apply_devices_env()
+    idx, sc = _self_device(c, col, rv, lambda dc: dc.topk_self(k, metric_id))
+    return _wrap(_topk_arrow(idx, sc.astype(np.float64), n, idx.shape[1]), "topk_self", polars_out)
+
+
 def _matmul(left, right):
     """src/lib.rs:15-30 -> src/matmul.rs:295-417 matmul_impl."""
     polars_out = _is_polars_series(left)
