@@ -732,6 +732,30 @@ int pmm_topk_f32_self(const pmm_corpus *corpus, int64_t k, int metric, uint32_t 
 int pmm_range_self_plan(int64_t n, int cus, int variant_in, int *variant, int64_t *block_tile_visits,
                         int64_t *block_tile_full);
 
+/* The sort plan of ragged key lists -- what pmm_range_f32_self (cap =
+ * INT64_MAX) and pmm_topk_f32_candidates (cap = k) lay out before they sort
+ * (host only, no device is touched).  offsets: the m + 1 ascending bounds of
+ * the segments, from 0.  A segment of up to smax keys is one piece; a longer
+ * one is cut into ceil(count / smax) pieces of smax keys, the last one
+ * shorter.  Every piece is sorted on its own; a cut segment's best
+ * min(cap, count) keys are then merged to the merged-key array.
+ * piece_offsets: the pieces' bounds (pieces + 1 entries); mid: the pieces of
+ * more than 128 keys, ascending (the workgroup sort's; the others sort in one
+ * wave); cut: one record per piece of a cut segment, segment by segment --
+ * piece `self` of the segment's pieces [first, first + count), whose best
+ * kout keys go to the merged keys [dst, dst + kout); counts[5]: pieces,
+ * entries of mid, the longest piece in mid (0: none), entries of cut, merged
+ * keys in all.  Room the caller gives: m + offsets[m] / smax pieces in each of
+ * the three (one more bound in piece_offsets).  smax outside [128, 8192],
+ * cap < 1, offsets that descend or do not start at 0, a null pointer:
+ * PMM_ERR_ARG. */
+typedef struct pmm_sort_piece {
+  uint32_t self, first, count, kout;
+  int64_t dst;
+} pmm_sort_piece;
+int pmm_sort_plan(const int64_t *offsets, int64_t m, int64_t smax, int64_t cap, int64_t *piece_offsets, int *mid,
+                  pmm_sort_piece *cut, int64_t *counts);
+
 /* Per-kernel timing on the launch stream (hipEvents around each launch).
  * enable=1 starts recording; pmm_timing_read returns the summed milliseconds
  * and launch count of kernels whose name contains `kernel` since the last

@@ -3027,6 +3027,29 @@ static int corpus_topk(const pmm_corpus *h, int dtype, const Row *q, int64_t m, 
   return host_topk(h, qr, HostRows{}, m, k, out_idx, out_score, plan, run);
 }
 
+// The opening of a list-valued entry (grouped, range and self, candidate
+// search) on a handle of one shard: the shard's device, this thread's stream
+// on it and the device's CU count.  run(body): the part of the entry that
+// uploads from the frame's own vectors (or downloads into them) -- a failure
+// in it waits for the stream before the frame, and those vectors, go.
+struct ShardCall {
+  int dev = 0, cus = 0;
+  DevScope scope;
+  hipStream_t s = nullptr;
+  int open(const pmm_corpus *h) {
+    if (int rc = ensure_device(&dev, &scope, h->shards[0].device)) return rc;
+    if (int rc = thread_stream(dev, &s)) return rc;
+    cus = g_dev[dev].cus;
+    return PMM_OK;
+  }
+  template <typename Body>
+  int run(Body body) {
+    const int rc = body();
+    if (rc) (void)hipStreamSynchronize(s);
+    return rc;
+  }
+};
+
 // ---------------------------------------------------------------------------
 // Grouped search: every query row is searched inside its own
 // group's segment of a partitioned handle.
@@ -3135,12 +3158,10 @@ static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const ui
                                     (uint32_t)std::min<int64_t>(kGroupedRows, p.mq - r0)});
   }
   const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
-  const int cus = g_dev[dev].cus;
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const int dev = f.dev, cus = f.cus;
+  const hipStream_t s = f.s;
   // The loop pairs' routes and the largest workspace and short-list staging among them.
   std::vector<TopkRoute> routes;
   size_t ws_need = 0, tmp_entries = 0;
@@ -3181,7 +3202,7 @@ static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const ui
   memcpy(htab.data() + mk, glen.data(), (size_t)mk * 4);
   if (!units.empty()) memcpy(htab.data() + 2 * mk, units.data(), units.size() * sizeof(GroupedUnit));
   // (from here on a failure waits for the stream: the uploads read this frame's vectors)
-  auto run = [&]() -> int {
+  return f.run([&]() -> int {
     {
       Timed t("h2d", s);
       HIP_TRY(hipMemcpyAsync(tab, htab.data(), tab_words * 4, hipMemcpyHostToDevice, s));
@@ -3258,10 +3279,7 @@ static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const ui
       HIP_TRY(hipMemcpyAsync(out_len, ol, (size_t)m * 4, hipMemcpyDeviceToHost, s));
     }
     return download_lists(out_idx, out_score, oi, os, m, k, s);
-  };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(s);
-  return rc;
+  });
 }
 
 // ===========================================================================
@@ -4064,36 +4082,17 @@ static int range_handle(const pmm_corpus *h, const char *what) {
   return PMM_OK;
 }
 
-static int range_search(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
-                        int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total);
+static int range_search(const pmm_corpus *h, bool self, const float *q, int64_t m, float threshold, int metric,
+                        int64_t cap, int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total);
 
 int pmm_range_f32_corpus(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
                          int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
-  // every argument check before the handle is read or a device touched
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (!q || !out_offsets || !total) return fail(PMM_ERR_ARG, "null argument");
-  if (m < 0 || cap < 0)
-    return fail(PMM_ERR_ARG, "negative size (m=%lld cap=%lld)", (long long)m, (long long)cap);
-  if (cap > 0 && (!out_idx || !out_score))
-    return fail(PMM_ERR_ARG, "null argument: cap > 0 needs out_idx and out_score (cap = 0 is the count-only form)");
-  int rc = check_metric(metric);
-  if (rc) return rc;
-  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
-  return range_search(h, q, m, threshold, metric, cap, out_offsets, out_idx, out_score, total);
+  return range_search(h, false, q, m, threshold, metric, cap, out_offsets, out_idx, out_score, total);
 }
 
 int pmm_range_f32_self(const pmm_corpus *h, float threshold, int metric, int64_t cap, int64_t *out_offsets,
                        uint32_t *out_idx, float *out_score, int64_t *total) {
-  // every argument check before the handle is read or a device touched
-  if (!h) return fail(PMM_ERR_ARG, "null corpus");
-  if (!out_offsets || !total) return fail(PMM_ERR_ARG, "null argument");
-  if (cap < 0) return fail(PMM_ERR_ARG, "negative size (cap=%lld)", (long long)cap);
-  if (cap > 0 && (!out_idx || !out_score))
-    return fail(PMM_ERR_ARG, "null argument: cap > 0 needs out_idx and out_score (cap = 0 is the count-only form)");
-  int rc = check_metric(metric);
-  if (rc) return rc;
-  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
-  return range_search(h, nullptr, 0, threshold, metric, cap, out_offsets, out_idx, out_score, total);
+  return range_search(h, true, nullptr, 0, threshold, metric, cap, out_offsets, out_idx, out_score, total);
 }
 
 int pmm_topk_f32_self(const pmm_corpus *h, int64_t k, int metric, uint32_t *out_idx, float *out_score) {
@@ -4154,15 +4153,115 @@ int pmm_range_self_plan(int64_t n, int cus, int variant_in, int *variant, int64_
   return PMM_OK;
 }
 
-// The body of both range entries, their arguments checked.  q = nullptr is the
-// self form: the handle's rows are the m = n query rows and its norms their
-// norms, nothing is uploaded, the emit pass runs the triangular schedule
-// (launch_gemm_f32_self) and a row records only its hits at positions above it.
-static int range_search(const pmm_corpus *h, const float *q, int64_t m, float threshold, int metric, int64_t cap,
-                        int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
-  const bool self = q == nullptr;
-  int rc = range_handle(h, self ? "self search" : "range search");
+// The sort plan of ragged key lists (range, self and candidate search;
+// DESIGN.md §4d "Piece planner and sort driver"), from the m + 1 host bounds
+// of the segments.  A segment of up to smax keys is one piece; a longer one is
+// cut into pieces of smax (the last one shorter), each sorted on its own, and
+// its best min(cap, count) keys are merged to merged keys from `dst` on.
+struct SortPlan {
+  std::vector<int64_t> po;     // the piece bounds
+  std::vector<int> mid;        // the pieces of more than kRangeWaveMax keys: the block sort's
+  int64_t mid_max = 0;         // the longest of them
+  std::vector<CandPiece> cut;  // one per piece of a cut segment
+  int64_t merged = 0;          // the merged keys of all cut segments
+};
+static void plan_pieces(const int64_t *offsets, int64_t m, int64_t smax, int64_t cap, SortPlan &p) {
+  p.po.assign(1, 0);
+  for (int64_t i = 0; i < m; i++) {
+    const int64_t o = offsets[i], c = offsets[i + 1] - o;
+    const int64_t T = c > smax ? cdiv(c, smax) : 1, first = (int64_t)p.po.size() - 1;
+    if (T > 1) {
+      const int64_t kout = std::min(cap, c);
+      for (int64_t t = 0; t < T; t++)
+        p.cut.push_back(CandPiece{(uint32_t)(first + t), (uint32_t)first, (uint32_t)T, (uint32_t)kout, p.merged});
+      p.merged += kout;
+    }
+    for (int64_t t = 0; t < T; t++) {
+      const int64_t len = std::min(smax, c - t * smax);
+      if (len > kRangeWaveMax) {
+        p.mid.push_back((int)(first + t));
+        p.mid_max = std::max(p.mid_max, len);
+      }
+      p.po.push_back(o + t * smax + len);
+    }
+  }
+}
+
+// The sort of every segment of `keys` by a plan: the plan's tables to their
+// device places (d_po, d_cut: used only with a cut segment -- without one the
+// pieces are the m rows and the device offsets d_offs their bounds), the wave
+// and block sorts over the pieces, and the cut segments' merge into dst.  The
+// uploads read the plan: the caller runs this inside ShardCall::run.
+static int sort_segments(unsigned long long *keys, const int64_t *d_offs, int64_t m, const SortPlan &p, int64_t *d_po,
+                         int *d_mid, CandPiece *d_cut, unsigned long long *dst, hipStream_t s) {
+  const bool cut = !p.cut.empty();
+  if (cut) {
+    HIP_TRY(hipMemcpyAsync(d_po, p.po.data(), p.po.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_cut, p.cut.data(), p.cut.size() * sizeof(CandPiece), hipMemcpyHostToDevice, s));
+  }
+  const int64_t *bounds = cut ? d_po : d_offs;
+  {
+    Timed t("range_sort_wave", s);
+    HIP_TRY(launch_range_sort_wave(keys, bounds, cut ? (int)(p.po.size() - 1) : (int)m, s));
+  }
+  if (!p.mid.empty()) {
+    HIP_TRY(hipMemcpyAsync(d_mid, p.mid.data(), p.mid.size() * 4, hipMemcpyHostToDevice, s));
+    Timed t("range_sort_block", s);
+    HIP_TRY(launch_range_sort_block(keys, bounds, d_mid, (int)p.mid.size(), next_pow2((int)p.mid_max), s));
+  }
+  if (cut) {
+    Timed t("cand_merge", s);
+    HIP_TRY(launch_cand_merge(keys, bounds, d_cut, (int)p.cut.size(), dst, s));
+  }
+  return PMM_OK;
+}
+
+int pmm_sort_plan(const int64_t *offsets, int64_t m, int64_t smax, int64_t cap, int64_t *piece_offsets, int *mid,
+                  pmm_sort_piece *cut, int64_t *counts) {
+  static_assert(sizeof(pmm_sort_piece) == sizeof(CandPiece), "pmm.h states CandPiece's layout");
+  if (!offsets || !piece_offsets || !mid || !cut || !counts) return fail(PMM_ERR_ARG, "null argument");
+  bool ok = m >= 0 && smax >= kRangeWaveMax && smax <= kRangeSortMax && cap >= 1 && offsets[0] == 0;
+  for (int64_t i = 0; ok && i < m; i++) ok = offsets[i + 1] >= offsets[i];
+  if (!ok)
+    return fail(PMM_ERR_ARG, "bad sort plan arguments (m=%lld smax=%lld cap=%lld: smax in [%d, %d], cap >= 1, "
+                             "offsets ascending from 0)", (long long)m, (long long)smax, (long long)cap, kRangeWaveMax,
+                kRangeSortMax);
+  SortPlan p;
+  plan_pieces(offsets, m, smax, cap, p);
+  std::copy(p.po.begin(), p.po.end(), piece_offsets);
+  std::copy(p.mid.begin(), p.mid.end(), mid);
+  memcpy(cut, p.cut.data(), p.cut.size() * sizeof(CandPiece));
+  const int64_t n[5] = {(int64_t)p.po.size() - 1, (int64_t)p.mid.size(), p.mid_max, (int64_t)p.cut.size(), p.merged};
+  std::copy(n, n + 5, counts);
+  return PMM_OK;
+}
+
+// What both range entries check before the handle is read or a device touched
+// (the self form has no q and no m).
+static int range_args(const pmm_corpus *h, bool self, const float *q, int64_t m, float threshold, int metric,
+                      int64_t cap, const int64_t *out_offsets, const uint32_t *out_idx, const float *out_score,
+                      const int64_t *total) {
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if ((!self && !q) || !out_offsets || !total) return fail(PMM_ERR_ARG, "null argument");
+  if (!self && (m < 0 || cap < 0))
+    return fail(PMM_ERR_ARG, "negative size (m=%lld cap=%lld)", (long long)m, (long long)cap);
+  if (cap < 0) return fail(PMM_ERR_ARG, "negative size (cap=%lld)", (long long)cap);
+  if (cap > 0 && (!out_idx || !out_score))
+    return fail(PMM_ERR_ARG, "null argument: cap > 0 needs out_idx and out_score (cap = 0 is the count-only form)");
+  if (int rc = check_metric(metric)) return rc;
+  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
+  return PMM_OK;
+}
+
+// The body of both range entries.  The self form: the handle's rows are the
+// m = n query rows and its norms their norms, nothing is uploaded, the emit
+// pass runs the triangular schedule (launch_gemm_f32_self) and a row records
+// only its hits at positions above it.
+static int range_search(const pmm_corpus *h, bool self, const float *q, int64_t m, float threshold, int metric,
+                        int64_t cap, int64_t *out_offsets, uint32_t *out_idx, float *out_score, int64_t *total) {
+  int rc = range_args(h, self, q, m, threshold, metric, cap, out_offsets, out_idx, out_score, total);
   if (rc) return rc;
+  if ((rc = range_handle(h, self ? "self search" : "range search"))) return rc;
   if (self) m = h->n;
   if ((rc = validate_sizes(m, h->n, h->d, 0, false))) return rc;
   *total = 0;
@@ -4174,17 +4273,14 @@ static int range_search(const pmm_corpus *h, const float *q, int64_t m, float th
   }
 
   const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const hipStream_t s = f.s;
   const int64_t n = h->n, d = h->d, dp = h->dp;
-  const int cus = g_dev[dev].cus;
   Plan p;
-  p.variant = range_variant(m, n, cus);
+  p.variant = range_variant(m, n, f.cus);
   const int bn = gemm_f32_bn(p.variant);
-  plan_units(m, n, gemm_f32_bm(p.variant), bn, cus, 0.5, 1 << 20, p);
+  plan_units(m, n, gemm_f32_bm(p.variant), bn, f.cus, 0.5, 1 << 20, p);
   // the record arena never needs more than m x n records (self: the pairs)
   const uint64_t rcap = (uint64_t)std::min<int64_t>(cap, self ? n * (n - 1) / 2 : m * n);
   // self: a row past the in-LDS sort is cut into pieces (below); of tot <= rcap
@@ -4197,36 +4293,25 @@ static int range_search(const pmm_corpus *h, const float *q, int64_t m, float th
   // row) | binned keys; the decoded lists reuse the record keys' bytes
   // (self: no queries and no query norms; a piece list for the row list, and
   // the piece bounds and cut pieces at the end)
-  size_t off = self ? 0 : al256((size_t)m * dp * 4);
-  const size_t off_ctl = off;
-  off += 256;
-  const size_t off_hits = off;
-  off += al256((size_t)m * 4);
-  const size_t off_cur = off;
-  off += al256((size_t)m * 4);
-  const size_t off_qn = off;
-  off += self ? 0 : al256((size_t)m * 4);
-  const size_t off_offs = off;
-  off += al256((size_t)(m + 1) * 8);
-  const size_t off_rows = off;
-  off += al256((self ? max_pieces : (size_t)m) * 4);
-  const size_t off_wq = off;
-  off += al256((size_t)p.grid * gemm_f32_nw(p.variant) * 32 * bn * 8);
-  const size_t off_rkey = off;
-  off += al256((size_t)rcap * 8);
-  const size_t off_rrow = off;
-  off += al256((size_t)rcap * 4);
-  const size_t off_keys = off;
-  off += al256((size_t)rcap * 8);
-  const size_t off_po = off;
-  off += al256((max_pieces + 1) * 8);
-  const size_t off_cut = off;
-  off += al256(max_cut * sizeof(CandPiece));
+  Layout L;
+  const size_t off_q = L.take(self ? 0 : (size_t)m * dp * 4);
+  const size_t off_ctl = L.take(256);
+  const size_t off_hits = L.take((size_t)m * 4);
+  const size_t off_cur = L.take((size_t)m * 4);
+  const size_t off_qn = L.take(self ? 0 : (size_t)m * 4);
+  const size_t off_offs = L.take((size_t)(m + 1) * 8);
+  const size_t off_rows = L.take((self ? max_pieces : (size_t)m) * 4);
+  const size_t off_wq = L.take((size_t)p.grid * gemm_f32_nw(p.variant) * 32 * bn * 8);
+  const size_t off_rkey = L.take((size_t)rcap * 8);
+  const size_t off_rrow = L.take((size_t)rcap * 4);
+  const size_t off_keys = L.take((size_t)rcap * 8);
+  const size_t off_po = L.take((max_pieces + 1) * 8);
+  const size_t off_cut = L.take(max_cut * sizeof(CandPiece));
   void *base;
-  if ((rc = arena(dev, s, off, &base))) return rc;
+  if ((rc = arena(f.dev, s, L.off, &base))) return rc;
   char *b = (char *)base;
-  const float *dq = self ? x.rows_as<float>() : (const float *)b;
-  if (!self && (rc = upload_padded(b, q, m, d, dp, 4, s))) return rc;
+  const float *dq = self ? x.rows_as<float>() : (const float *)(b + off_q);
+  if (!self && (rc = upload_padded(b + off_q, q, m, d, dp, 4, s))) return rc;
   HIP_TRY(hipMemsetAsync(b + off_ctl, 0, off_qn - off_ctl, s));
   const float *qn = self ? shard_norms<float>(h, x, metric) : (const float *)(b + off_qn);
   if (!self && metric != kMetricDot) {
@@ -4273,129 +4358,91 @@ static int range_search(const pmm_corpus *h, const float *q, int64_t m, float th
     Timed t("gemm_f32_range", s);
     HIP_TRY(launch_gemm_f32_range(a, p.variant, p.grid, s));
   }
-  // the count: the rows' hits and the cursor, the call's one wait before the lists
+  // (from here on a failure waits for the stream: the copies read and write this frame's vectors)
   std::vector<uint32_t> hits((size_t)m);
   unsigned long long cursor = 0;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(hits.data(), a.rhits, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&cursor, a.rcur, 8, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int64_t i = 0; i < m; i++) out_offsets[i + 1] = out_offsets[i] + (int64_t)hits[(size_t)i];
-  const int64_t tot = out_offsets[m];
-  if ((unsigned long long)tot != cursor)
-    return fail(PMM_ERR_HIP, "range search: the rows' counts (%lld) and the record cursor (%llu) disagree",
-                (long long)tot, cursor);
-  *total = tot;
-  if (tot > cap || tot == 0) return PMM_OK;
+  SortPlan plan;
+  std::vector<int> longr;  // the rows the handle's ordinary top-k serves at the end
+  rc = f.run([&]() -> int {
+    // the count: the rows' hits and the cursor, the call's one wait before the lists
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(hits.data(), a.rhits, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&cursor, a.rcur, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < m; i++) out_offsets[i + 1] = out_offsets[i] + (int64_t)hits[(size_t)i];
+    const int64_t tot = out_offsets[m];
+    if ((unsigned long long)tot != cursor)
+      return fail(PMM_ERR_HIP, "range search: the rows' counts (%lld) and the record cursor (%llu) disagree",
+                  (long long)tot, cursor);
+    *total = tot;
+    if (tot > cap || tot == 0) return PMM_OK;
 
-  // rows by sort tier: (128, smax] in a workgroup's LDS, longer ones by the
-  // handle's ordinary top-k at the end (self: cut into pieces, below)
-  const int64_t smax = range_sort_max();
-  std::vector<int> mid, longr;
-  int64_t mid_max = 0;
-  for (int64_t i = 0; i < m; i++) {
-    const int64_t c = (int64_t)hits[(size_t)i];
-    if (c > smax) longr.push_back((int)i);
-    else if (c > kRangeWaveMax) {
-      mid.push_back((int)i);
-      mid_max = std::max(mid_max, c);
-    }
-  }
-  int64_t *d_offs = (int64_t *)(b + off_offs);
-  unsigned long long *keys = (unsigned long long *)(b + off_keys);
-  HIP_TRY(hipMemcpyAsync(d_offs, out_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
-  {
-    Timed t("range_bin", s);
-    HIP_TRY(launch_range_bin(a.rkey, a.rrow, tot, d_offs, (unsigned *)(b + off_cur), keys, s));
-  }
-  // Self, with a row past the in-LDS sort: the handle's top-k does not know
-  // j > i, so such a row is cut into pieces of smax keys, every piece sorted by
-  // the same two kernels over the piece bounds, and the row's whole order
-  // merged by rank counting (the candidate search's cand_merge_kernel, kout =
-  // the row's count) into the record keys' bytes, free since the bin pass, and
-  // copied back to the row's segment.
-  std::vector<int64_t> po;
-  std::vector<CandPiece> cut;
-  const int64_t *d_po = d_offs;  // (without a cut row the pieces are the rows)
-  if (self && !longr.empty()) {
-    mid.clear();
-    mid_max = 0;
-    int64_t ltotal = 0;
-    po.push_back(0);
-    for (int64_t i = 0; i < m; i++) {
-      const int64_t o = out_offsets[i], c = (int64_t)hits[(size_t)i];
-      const int64_t T = c > smax ? cdiv(c, smax) : 1;
-      if (T > 1) {
-        for (int64_t t = 0; t < T; t++)
-          cut.push_back(CandPiece{(uint32_t)(po.size() - 1 + t), (uint32_t)(po.size() - 1), (uint32_t)T, (uint32_t)c,
-                                  ltotal});
-        ltotal += c;
-      }
-      for (int64_t t = 0; t < T; t++) {
-        const int64_t len = std::min(smax, c - t * smax);
-        if (len > kRangeWaveMax) {
-          mid.push_back((int)(po.size() - 1));
-          mid_max = std::max(mid_max, len);
+    // Rows by sort tier: up to 128 keys in a wave, up to smax in a workgroup's
+    // LDS.  A longer row goes to the handle's ordinary top-k at the end; self,
+    // whose pairs j > i that top-k does not know, cuts it into pieces instead
+    // (plan_pieces, cap = the row's count), merges the row's whole order into
+    // the record keys' bytes, free since the bin pass, and copies it back.
+    const int64_t smax = range_sort_max();
+    if (self) {
+      plan_pieces(out_offsets, m, smax, INT64_MAX, plan);
+      if (plan.po.size() > max_pieces + 1 || plan.cut.size() > max_cut || plan.po.size() - 1 > (size_t)INT32_MAX)
+        return fail(PMM_ERR_HIP, "self search: %zu pieces, %zu of cut rows, past the arena's tables",
+                    plan.po.size() - 1, plan.cut.size());
+    } else {
+      for (int64_t i = 0; i < m; i++) {
+        const int64_t c = (int64_t)hits[(size_t)i];
+        if (c > smax) longr.push_back((int)i);
+        else if (c > kRangeWaveMax) {
+          plan.mid.push_back((int)i);
+          plan.mid_max = std::max(plan.mid_max, c);
         }
-        po.push_back(o + t * smax + len);
       }
     }
-    if (po.size() > max_pieces + 1 || cut.size() > max_cut || po.size() - 1 > (size_t)INT32_MAX)
-      return fail(PMM_ERR_HIP, "self search: %zu pieces, %zu of cut rows, past the arena's tables", po.size() - 1,
-                  cut.size());
-    HIP_TRY(hipMemcpyAsync(b + off_po, po.data(), po.size() * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + off_cut, cut.data(), cut.size() * sizeof(CandPiece), hipMemcpyHostToDevice, s));
-    d_po = (const int64_t *)(b + off_po);
-  }
-  {
-    Timed t("range_sort_wave", s);
-    HIP_TRY(launch_range_sort_wave(keys, d_po, d_po == d_offs ? (int)m : (int)(po.size() - 1), s));
-  }
-  if (!mid.empty()) {
-    HIP_TRY(hipMemcpyAsync(b + off_rows, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, s));
-    Timed t("range_sort_block", s);
-    HIP_TRY(launch_range_sort_block(keys, d_po, (const int *)(b + off_rows), (int)mid.size(),
-                                    next_pow2((int)mid_max), s));
-  }
-  if (!cut.empty()) {
-    Timed t("cand_merge", s);
-    HIP_TRY(launch_cand_merge(keys, d_po, (const CandPiece *)(b + off_cut), (int)cut.size(), a.rkey, s));
-    int64_t lo = 0;
-    for (const int row : longr) {
-      const int64_t c = (int64_t)hits[(size_t)row];
-      HIP_TRY(hipMemcpyAsync(keys + out_offsets[row], a.rkey + lo, (size_t)c * 8, hipMemcpyDeviceToDevice, s));
-      lo += c;
+    int64_t *d_offs = (int64_t *)(b + off_offs);
+    unsigned long long *keys = (unsigned long long *)(b + off_keys);
+    HIP_TRY(hipMemcpyAsync(d_offs, out_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+    {
+      Timed t("range_bin", s);
+      HIP_TRY(launch_range_bin(a.rkey, a.rrow, tot, d_offs, (unsigned *)(b + off_cur), keys, s));
     }
-    longr.clear();  // (served)
-  }
-  RangeDecodeArgs da{};
-  da.keys = keys;
-  da.total = tot;
-  da.offsets = d_offs;
-  da.m = (int)m;
-  da.metric = metric;
-  da.d = (int)d;
-  da.map = h->map;
-  da.q = dq;
-  da.c = a.c;
-  da.qn = qn;
-  da.cn = a.cn;
-  da.ldq = dp;
-  da.ldc = dp;
-  da.out_idx = (uint32_t *)(b + off_rkey);  // (the records are binned, a cut row merged: their bytes are free)
-  da.out_score = (float *)(b + off_rkey + (size_t)tot * 4);
-  {
-    Timed t("range_decode", s);
-    HIP_TRY(launch_range_decode(da, s));
-  }
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
+    if (int rc2 = sort_segments(keys, d_offs, m, plan, (int64_t *)(b + off_po), (int *)(b + off_rows),
+                                (CandPiece *)(b + off_cut), a.rkey, s))
+      return rc2;
+    for (const CandPiece &c : plan.cut)  // a cut row's merged order, back to its segment
+      if (c.self == c.first)
+        HIP_TRY(hipMemcpyAsync(keys + plan.po[c.first], a.rkey + c.dst, (size_t)c.kout * 8, hipMemcpyDeviceToDevice,
+                               s));
+    RangeDecodeArgs da{};
+    da.keys = keys;
+    da.total = tot;
+    da.offsets = d_offs;
+    da.m = (int)m;
+    da.metric = metric;
+    da.d = (int)d;
+    da.map = h->map;
+    da.q = dq;
+    da.c = a.c;
+    da.qn = qn;
+    da.cn = a.cn;
+    da.ldq = dp;
+    da.ldc = dp;
+    da.out_idx = (uint32_t *)(b + off_rkey);  // (the records are binned, a cut row merged: their bytes are free)
+    da.out_score = (float *)(b + off_rkey + (size_t)tot * 4);
+    {
+      Timed t("range_decode", s);
+      HIP_TRY(launch_range_decode(da, s));
+    }
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  });
+  if (rc) return rc;
 
   // Segments past the in-LDS sort: the row's list is the first count entries
   // of its top-k list with k = count (the defining property), so those rows go
@@ -4474,48 +4521,31 @@ int pmm_topk_f32_candidates(const pmm_corpus *h, const float *q, int64_t m, cons
                 (long long)k);
 
   // Host tables.  Units of the score pass: a row's candidates 256 at a time.
-  // Pieces of the sort: a row of up to smax keys is one piece, a longer one is
-  // cut into pieces of smax, each sorted on its own; a cut row's best
-  // min(k, count) keys are then merged into a second key array behind the first.
+  // The sort plan (plan_pieces, cap = k): a cut row's best min(k, count) keys
+  // are merged into a second key array behind the first, where its key source
+  // then points.
   const int64_t smax = range_sort_max();
+  SortPlan plan;
+  plan_pieces(cand_offsets, m, smax, k, plan);
   std::vector<CandUnit> units;
-  std::vector<int64_t> po, src((size_t)m);
-  std::vector<int> mid;  // pieces of 129 .. smax keys
-  std::vector<CandPiece> cut;
-  int64_t mid_max = 0, ltotal = 0;
-  po.push_back(0);
+  std::vector<int64_t> src(cand_offsets, cand_offsets + m);
+  size_t ci = 0;  // (plan.cut holds the cut rows' pieces in row order)
   for (int64_t i = 0; i < m; i++) {
-    const int64_t o = cand_offsets[i], c = cand_offsets[i + 1] - o;
+    const int64_t c = cand_offsets[i + 1] - cand_offsets[i];
     for (int64_t u = 0; u < c; u += kCandUnit) units.push_back(CandUnit{(uint32_t)i, (uint32_t)u});
-    src[(size_t)i] = o;
-    const int64_t T = c > smax ? cdiv(c, smax) : 1;
-    if (T > 1) {
-      src[(size_t)i] = total + ltotal;
-      const int64_t kout = std::min(k, c);
-      for (int64_t t = 0; t < T; t++)
-        cut.push_back(CandPiece{(uint32_t)(po.size() - 1 + t), (uint32_t)(po.size() - 1), (uint32_t)T, (uint32_t)kout,
-                                ltotal});
-      ltotal += kout;
-    }
-    for (int64_t t = 0; t < T; t++) {
-      const int64_t len = std::min(smax, c - t * smax);
-      if (len > kRangeWaveMax) {
-        mid.push_back((int)(po.size() - 1));
-        mid_max = std::max(mid_max, len);
-      }
-      po.push_back(o + t * smax + len);
+    if (c > smax) {
+      src[(size_t)i] = total + plan.cut[ci].dst;
+      ci += plan.cut[ci].T;
     }
   }
-  const int64_t npieces = (int64_t)po.size() - 1;
+  const int64_t npieces = (int64_t)plan.po.size() - 1;
   if ((int64_t)units.size() > INT32_MAX || npieces > INT32_MAX)
     return fail(PMM_ERR_ARG, "too many candidates for one call (%lld): split the query rows", (long long)total);
 
   const CorpusShard &x = h->shards[0];
-  int dev;
-  DevScope scope;
-  if ((rc = ensure_device(&dev, &scope, x.device))) return rc;
-  hipStream_t s;
-  if ((rc = thread_stream(dev, &s))) return rc;
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const hipStream_t s = f.s;
   // arena: queries | query norms | flag | offsets | ids | units | piece bounds
   // | piece list | cut pieces | key sources | keys, merged keys | the planes
   Layout L;
@@ -4525,106 +4555,96 @@ int pmm_topk_f32_candidates(const pmm_corpus *h, const float *q, int64_t m, cons
   const size_t off_offs = L.take((size_t)(m + 1) * 8);
   const size_t off_ids = L.take((size_t)total * 4);
   const size_t off_units = L.take(units.size() * sizeof(CandUnit));
-  const size_t off_po = L.take(cut.empty() ? 0 : (size_t)(npieces + 1) * 8);
-  const size_t off_mid = L.take(mid.size() * 4);
-  const size_t off_cut = L.take(cut.size() * sizeof(CandPiece));
+  const size_t off_po = L.take(plan.cut.empty() ? 0 : (size_t)(npieces + 1) * 8);
+  const size_t off_mid = L.take(plan.mid.size() * 4);
+  const size_t off_cut = L.take(plan.cut.size() * sizeof(CandPiece));
   const size_t off_src = L.take((size_t)m * 8);
-  const size_t off_keys = L.take((size_t)(total + ltotal) * 8);
+  const size_t off_keys = L.take((size_t)(total + plan.merged) * 8);
   const size_t off_oi = L.take((size_t)m * k * 4);
   const size_t off_os = L.take((size_t)m * k * 4);
   const size_t off_len = L.take((size_t)m * 4);
   void *base;
-  if ((rc = arena(dev, s, L.off, &base))) return rc;
+  if ((rc = arena(f.dev, s, L.off, &base))) return rc;
   char *b = (char *)base;
   const float *dq = (const float *)(b + off_q);
   if ((rc = upload_padded(b + off_q, q, m, d, dp, 4, s))) return rc;
-  HIP_TRY(hipMemsetAsync(b + off_flag, 0, 4, s));
-  int64_t *d_offs = (int64_t *)(b + off_offs);
-  // (without a cut row the pieces are the rows)
-  const int64_t *d_po = cut.empty() ? d_offs : (const int64_t *)(b + off_po);
-  {
-    Timed t("h2d", s);
-    HIP_TRY(hipMemcpyAsync(d_offs, cand_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + off_src, src.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
-    if (total > 0) {
-      HIP_TRY(hipMemcpyAsync(b + off_ids, cand_ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(b + off_units, units.data(), units.size() * sizeof(CandUnit), hipMemcpyHostToDevice, s));
-    }
-    if (!cut.empty()) {
-      HIP_TRY(hipMemcpyAsync(b + off_po, po.data(), po.size() * 8, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(b + off_cut, cut.data(), cut.size() * sizeof(CandPiece), hipMemcpyHostToDevice, s));
-    }
-    if (!mid.empty()) HIP_TRY(hipMemcpyAsync(b + off_mid, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, s));
-  }
-  float *qn = (float *)(b + off_qn);
-  if (metric != kMetricDot) {
-    Timed t("norms_f32", s);
-    HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
-  }
-  unsigned long long *keys = (unsigned long long *)(b + off_keys);
-  CandScoreArgs sa{};
-  sa.q = dq;
-  sa.c = x.rows_as<float>();
-  sa.qn = qn;
-  sa.cn = shard_norms<float>(h, x, metric);
-  sa.offsets = d_offs;
-  sa.ids = (const uint32_t *)(b + off_ids);
-  sa.unit = (const CandUnit *)(b + off_units);
-  sa.units = (int)units.size();
-  sa.ldq = dp;
-  sa.ldc = dp;
-  sa.n = (uint32_t)n;
-  sa.d = (int)d;
-  sa.metric = metric;
-  sa.keys = keys;
-  sa.flag = (unsigned *)(b + off_flag);
-  {
-    Timed t("cand_score", s);
-    HIP_TRY(launch_cand_score(sa, s));
-  }
-  if (total > 0) {
-    Timed t("range_sort_wave", s);
-    HIP_TRY(launch_range_sort_wave(keys, d_po, (int)npieces, s));
-  }
-  if (!mid.empty()) {
-    Timed t("range_sort_block", s);
-    HIP_TRY(launch_range_sort_block(keys, d_po, (const int *)(b + off_mid), (int)mid.size(), next_pow2((int)mid_max),
-                                    s));
-  }
-  if (!cut.empty()) {
-    Timed t("cand_merge", s);
-    HIP_TRY(launch_cand_merge(keys, d_po, (const CandPiece *)(b + off_cut), (int)cut.size(), keys + total, s));
-  }
-  CandDecodeArgs da{};
-  da.keys = keys;
-  da.src = (const int64_t *)(b + off_src);
-  da.offsets = d_offs;
-  da.m = (int)m;
-  da.metric = metric;
-  da.d = (int)d;
-  da.k = k;
-  da.q = dq;
-  da.c = sa.c;
-  da.qn = qn;
-  da.cn = sa.cn;
-  da.ldq = dp;
-  da.ldc = dp;
-  da.out_idx = (uint32_t *)(b + off_oi);
-  da.out_score = (float *)(b + off_os);
-  da.out_len = (uint32_t *)(b + off_len);
-  {
-    Timed t("cand_decode", s);
-    HIP_TRY(launch_cand_decode(da, s));
-  }
+  // (from here on a failure waits for the stream: the copies read and write this frame's vectors)
   unsigned flag = 0u;
-  {
-    Timed t("d2h", s);
-    HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_len, da.out_len, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&flag, sa.flag, 4, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
+  rc = f.run([&]() -> int {
+    HIP_TRY(hipMemsetAsync(b + off_flag, 0, 4, s));
+    int64_t *d_offs = (int64_t *)(b + off_offs);
+    {
+      Timed t("h2d", s);
+      HIP_TRY(hipMemcpyAsync(d_offs, cand_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(b + off_src, src.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+      if (total > 0) {
+        HIP_TRY(hipMemcpyAsync(b + off_ids, cand_ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b + off_units, units.data(), units.size() * sizeof(CandUnit), hipMemcpyHostToDevice,
+                               s));
+      }
+    }
+    float *qn = (float *)(b + off_qn);
+    if (metric != kMetricDot) {
+      Timed t("norms_f32", s);
+      HIP_TRY(launch_norms_f32(dq, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+    }
+    unsigned long long *keys = (unsigned long long *)(b + off_keys);
+    CandScoreArgs sa{};
+    sa.q = dq;
+    sa.c = x.rows_as<float>();
+    sa.qn = qn;
+    sa.cn = shard_norms<float>(h, x, metric);
+    sa.offsets = d_offs;
+    sa.ids = (const uint32_t *)(b + off_ids);
+    sa.unit = (const CandUnit *)(b + off_units);
+    sa.units = (int)units.size();
+    sa.ldq = dp;
+    sa.ldc = dp;
+    sa.n = (uint32_t)n;
+    sa.d = (int)d;
+    sa.metric = metric;
+    sa.keys = keys;
+    sa.flag = (unsigned *)(b + off_flag);
+    {
+      Timed t("cand_score", s);
+      HIP_TRY(launch_cand_score(sa, s));
+    }
+    if (total > 0)
+      if (int rc2 = sort_segments(keys, d_offs, m, plan, (int64_t *)(b + off_po), (int *)(b + off_mid),
+                                  (CandPiece *)(b + off_cut), keys + total, s))
+        return rc2;
+    CandDecodeArgs da{};
+    da.keys = keys;
+    da.src = (const int64_t *)(b + off_src);
+    da.offsets = d_offs;
+    da.m = (int)m;
+    da.metric = metric;
+    da.d = (int)d;
+    da.k = k;
+    da.q = dq;
+    da.c = sa.c;
+    da.qn = qn;
+    da.cn = sa.cn;
+    da.ldq = dp;
+    da.ldc = dp;
+    da.out_idx = (uint32_t *)(b + off_oi);
+    da.out_score = (float *)(b + off_os);
+    da.out_len = (uint32_t *)(b + off_len);
+    {
+      Timed t("cand_decode", s);
+      HIP_TRY(launch_cand_decode(da, s));
+    }
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_len, da.out_len, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&flag, sa.flag, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  });
+  if (rc) return rc;
   if (flag & 2u)
     return fail(PMM_ERR_ARG, "a candidate id is not a row of the corpus (n=%lld)", (long long)n);
   if (flag & 1u)

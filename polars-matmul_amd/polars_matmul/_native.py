@@ -93,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "pmm_range_f32_self",
     "pmm_topk_f32_self",
     "pmm_range_self_plan",
+    "pmm_sort_plan",
     "pmm_topk_i8",
     "pmm_topk_i8_corpus",
     "pmm_topk_i8_device",
@@ -209,6 +210,7 @@ _SIGS = {
     "pmm_topk_f32_self": ([_vp, _i64, _i32, _vp, _vp], _i32),
     "pmm_range_self_plan": ([_i64, _i32, _i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
                              ctypes.POINTER(ctypes.c_int64)], _i32),
+    "pmm_sort_plan": ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
     "pmm_topk_i8": ([_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_i8_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
@@ -295,6 +297,22 @@ def range_self_plan(n: int, cus: int, variant: int = -1):
     visits, full = ctypes.c_int64(0), ctypes.c_int64(0)
     check(_lib.pmm_range_self_plan(n, cus, variant, ctypes.byref(v), ctypes.byref(visits), ctypes.byref(full)))
     return int(v.value), int(visits.value), int(full.value)
+
+
+SORT_PIECE = np.dtype([("self", "<u4"), ("first", "<u4"), ("T", "<u4"), ("kout", "<u4"), ("dst", "<i8")])
+
+
+def sort_plan(offsets, smax: int, cap: int):
+    """The sort plan of ragged key lists (pmm_sort_plan; pure, no GPU):
+    (piece bounds, block-sort pieces, the longest of them, the cut segments'
+    pieces as SORT_PIECE records, the merged total)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    m = offsets.size - 1
+    room = m + int(offsets[-1]) // max(int(smax), 1) + 1  # no plan has more pieces
+    po, mid, cut = np.empty(room + 1, np.int64), np.empty(room, np.int32), np.empty(room, SORT_PIECE)
+    n = np.zeros(5, np.int64)
+    check(_lib.pmm_sort_plan(ptr(offsets), m, int(smax), int(cap), ptr(po), ptr(mid), ptr(cut), ptr(n)))
+    return po[:n[0] + 1], mid[:n[1]], int(n[2]), cut[:n[3]], int(n[4])
 
 
 def shard_plan(devs, m: int, n: int, d: int, k: int, metric: int, compute: int = COMPUTE_F32,
@@ -823,19 +841,25 @@ class DeviceCorpus:
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError("dimension mismatch")
         m = q.shape[0]
+        return self._range(m, m * self.n, cap, lambda *out: _lib.pmm_range_f32_corpus(
+            self._h, ptr(q), m, float(threshold), metric, *out))
+
+    def _range(self, rows: int, most: int, cap, call):
+        """The range entries' cap protocol: ``call(cap, offsets, idx, scores,
+        total)`` with room for ``cap`` entries (default: the class constants;
+        at most ``most``), once more with the exact total when too small."""
         if cap is None:
-            cap = max(self.RANGE_CAP_MIN, self.RANGE_CAP_PER_ROW * m)
-        cap = max(0, min(int(cap), m * self.n))
-        offsets = np.empty(m + 1, dtype=np.int64)
+            cap = max(self.RANGE_CAP_MIN, self.RANGE_CAP_PER_ROW * rows)
+        cap = max(0, min(int(cap), most))
+        offsets = np.empty(rows + 1, dtype=np.int64)
         total = ctypes.c_int64(0)
         self.acquire()
         try:
             while True:
                 idx = np.empty(cap, dtype=np.uint32)
                 sc = np.empty(cap, dtype=np.float32)
-                check(_lib.pmm_range_f32_corpus(self._h, ptr(q), m, float(threshold), metric, cap, ptr(offsets),
-                                                ptr(idx) if cap else None, ptr(sc) if cap else None,
-                                                ctypes.byref(total)))
+                check(call(cap, ptr(offsets), ptr(idx) if cap else None, ptr(sc) if cap else None,
+                           ctypes.byref(total)))
                 if total.value <= cap:
                     break
                 cap = total.value  # too small: once more, with room
@@ -854,26 +878,8 @@ class DeviceCorpus:
         ``RANGE_CAP_PER_ROW`` per row, at least ``RANGE_CAP_MIN``, at most
         n (n - 1) / 2; repeated once with the exact total when too small."""
         n = self.n
-        pairs = n * (n - 1) // 2
-        if cap is None:
-            cap = max(self.RANGE_CAP_MIN, self.RANGE_CAP_PER_ROW * n)
-        cap = max(0, min(int(cap), pairs))
-        offsets = np.empty(n + 1, dtype=np.int64)
-        total = ctypes.c_int64(0)
-        self.acquire()
-        try:
-            while True:
-                idx = np.empty(cap, dtype=np.uint32)
-                sc = np.empty(cap, dtype=np.float32)
-                check(_lib.pmm_range_f32_self(self._h, float(threshold), metric, cap, ptr(offsets),
-                                              ptr(idx) if cap else None, ptr(sc) if cap else None,
-                                              ctypes.byref(total)))
-                if total.value <= cap:
-                    break
-                cap = total.value  # too small: once more, with room
-        finally:
-            self.release()
-        return offsets, idx[:total.value], sc[:total.value]
+        return self._range(n, n * (n - 1) // 2, cap, lambda *out: _lib.pmm_range_f32_self(
+            self._h, float(threshold), metric, *out))
 
     def topk_self(self, k: int, metric: int):
         """(idx uint32 (n, k'), scores float32 (n, k')) of pmm_topk_f32_self:
