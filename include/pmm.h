@@ -340,6 +340,7 @@ typedef struct pmm_corpus pmm_corpus;
 #define PMM_DTYPE_F64 1
 #define PMM_DTYPE_BF16 2
 #define PMM_DTYPE_I8 3
+#define PMM_DTYPE_BITS 4
 
 int pmm_corpus_create_f32(const float *c, int64_t n, int64_t d, pmm_corpus **out);
 /* An f64 corpus: rows kept in f64 (stride roundup(d, 16), zero-padded) with
@@ -364,7 +365,7 @@ int pmm_corpus_create_bf16(const float *c, int64_t n, int64_t d, pmm_corpus **ou
  * pmm_corpus_partition and pmm_range_f32_corpus refuse it with
  * PMM_ERR_UNSUPPORTED. */
 int pmm_corpus_create_i8(const int8_t *c, int64_t n, int64_t d, pmm_corpus **out);
-/* PMM_DTYPE_F32, PMM_DTYPE_F64, PMM_DTYPE_BF16 or PMM_DTYPE_I8. */
+/* PMM_DTYPE_F32, PMM_DTYPE_F64, PMM_DTYPE_BF16, PMM_DTYPE_I8 or PMM_DTYPE_BITS. */
 int pmm_corpus_dtype(const pmm_corpus *corpus, int *dtype);
 int pmm_corpus_destroy(pmm_corpus *corpus);
 int pmm_corpus_info(const pmm_corpus *corpus, int64_t *n, int64_t *d, int *device);
@@ -579,6 +580,94 @@ size_t pmm_topk_i8_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, i
 int pmm_topk_i8_device(const int8_t *q, int64_t ldq, int64_t m, const int8_t *c, int64_t ldc, int64_t n, int64_t d,
                        int64_t k, int metric, uint32_t index_base, uint32_t *out_idx, double *out_score,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Bit rows (binary embeddings: the sign of each component) and the exact
+ * Hamming top-k.  A bit row is w >= 1 bytes = D = 8 w bits; bit j is
+ * (byte[j >> 3] >> (j & 7)) & 1, least significant bit first (numpy's
+ * packbits(bitorder="little"), Arrow's bitmap order); no partial bytes.  The
+ * score of query row i and corpus row j is popcount(q_i XOR c_j), an integer
+ * in 0 .. D returned as f64 (exact); LOWER is better.  Row i's list holds the
+ * k corpus rows of least distance, ascending by (distance, corpus index): a
+ * tie at any place, the k-th included, goes to the lower index.
+ *   For 0/1 vectors popcount(a AND b) is the dot product and the distance is
+ * Pq + Pc - 2 dot (P: a row's popcount), so the scan runs on the int8 MFMA
+ * (v_mfma_i32_16x16x64_i8) over bytes expanded from the bits in LDS, with the
+ * int8 scan's euclidean key.
+ *   Limits.  w <= 8192, else PMM_ERR_UNSUPPORTED.  k <= 1024 takes the MFMA
+ * scan; a larger k expands both sides to 0/1 f64 rows on the device and takes
+ * the f64 path's euclidean search, whose score s gives rint(s * s): the same
+ * lists.  That route is for small corpora: the expansion takes
+ * (m + n) * roundup(8 w, 16) * 8 bytes of workspace, 512 times the packed rows
+ * (8 GB for 1M rows of 128 bytes; pmm_topk_bits_workspace_bytes states it), and
+ * a call whose workspace does not fit fails in the allocation with
+ * PMM_ERR_HIP.  A query row whose candidate buffer overflows is scanned again in
+ * chunks that cannot overflow, the same lists again.  k = 0, m = 0 and k > n
+ * as pmm_topk_f64.  Under pmm_set_devices the entries run on the list's first
+ * device (bit rows are not sharded).  Every entry synchronises the stream
+ * before it returns.
+ * ------------------------------------------------------------------------- */
+
+/* Sign packing on the device: bit j of output row r is 1 iff x[r * ldx + j] >
+ * 0.0f -- +0, -0, negatives, -inf and NaN give 0, subnormals follow their
+ * sign, +inf gives 1 -- for j < d; each row's roundup(ceil(d / 8), 8) bytes
+ * are written whole, the bits from d up as zeros; bytes past them are left.
+ * x: device f32 rows, any 4-byte-aligned address, ldx >= d floats; out: device
+ * rows of ld_out bytes, ld_out >= roundup(ceil(d / 8), 8) and a multiple of 8,
+ * 8-byte-aligned.  rows = 0 is PMM_OK.  Asynchronous on `stream`. */
+int pmm_pack_sign_device(const float *x, int64_t ldx, int64_t rows, int64_t d, uint8_t *out, int64_t ld_out,
+                         void *stream);
+
+/* A bit corpus: n host rows of w packed bytes, kept at stride roundup(w, 16)
+ * bytes (zero-padded: the search kernel's staging group) with one u32
+ * popcount per row: n * roundup(w, 16) + 4 n bytes (pmm_corpus_bytes returns
+ * it).  Never sharded.  pmm_corpus_subset_*, pmm_corpus_partition, the range,
+ * self and candidate entries refuse it as they refuse an int8 handle, and the
+ * other pmm_topk_*_corpus entries name pmm_topk_bits_corpus. */
+int pmm_corpus_create_bits(const uint8_t *c, int64_t n, int64_t w, pmm_corpus **out);
+
+/* The bit corpus of a resident f32 handle's rows: their signs (the rule of
+ * pmm_pack_sign_device, w = ceil(d / 8)) packed on the device from the rows
+ * the parent already holds -- no upload -- with the popcounts from the same
+ * pass; the bytes pmm_corpus_create_bits makes of the same bits.  The parent:
+ * an f32 handle of one shard, plain or derived by pmm_corpus_subset_* (the
+ * index map is copied, + 4 n bytes, so the lists number the original corpus).
+ * A partitioned, f64, bf16, int8 or bit parent: PMM_ERR_ARG; a sharded one:
+ * PMM_ERR_UNSUPPORTED.  The result is independent of the parent. */
+int pmm_corpus_sign_bits(const pmm_corpus *f32_parent, pmm_corpus **out);
+
+/* The rows of a bit corpus handle copied to the host: out takes n x w bytes,
+ * row-major without padding (pmm_corpus_info gives n and w).  With
+ * pmm_corpus_sign_bits this packs a resident f32 corpus on the device and
+ * returns the bytes.  A handle of other rows: PMM_ERR_ARG. */
+int pmm_corpus_bits_rows(const pmm_corpus *corpus, uint8_t *out);
+
+/* Hamming top-k of host rows: q (m x w), c (n x w) packed bytes, row-major;
+ * out_idx / out_score m x k. */
+int pmm_topk_bits(const uint8_t *q, int64_t m, const uint8_t *c, int64_t n, int64_t w, int64_t k, uint32_t *out_idx,
+                  double *out_score);
+
+/* pmm_topk_bits against a bit corpus handle, the same lists: host queries of
+ * the handle's w bytes in, host results out, 0 <= k <= n.  A handle of other
+ * rows: PMM_ERR_ARG naming the entry that serves it. */
+int pmm_topk_bits_corpus(const pmm_corpus *corpus, const uint8_t *q, int64_t m, int64_t k, uint32_t *out_idx,
+                         double *out_score);
+
+/* Bytes of workspace pmm_topk_bits_device needs for this problem: the one
+ * route decision (MFMA scan or expanded f64 search) the call then follows,
+ * with the environment as it is now.  Touches no device.  0 for an empty or
+ * refused problem. */
+size_t pmm_topk_bits_workspace_bytes(int64_t m, int64_t n, int64_t w, int64_t k);
+
+/* The same top-k over device rows on the caller's stream: ldq / ldc are row
+ * strides in bytes, multiples of 16 and >= roundup(w, 16), bytes past w
+ * zero-filled, 16-byte-aligned bases; out_idx / out_score device buffers of
+ * m * k entries, indices offset by index_base.  workspace: NULL (a per-thread
+ * cached buffer) or workspace_bytes >= pmm_topk_bits_workspace_bytes at a
+ * 256-byte-aligned address. */
+int pmm_topk_bits_device(const uint8_t *q, int64_t ldq, int64_t m, const uint8_t *c, int64_t ldc, int64_t n, int64_t w,
+                         int64_t k, uint32_t index_base, uint32_t *out_idx, double *out_score, void *workspace,
+                         size_t workspace_bytes, void *stream);
 
 /* Range search: every corpus row whose score passes a threshold, for each
  * query row (host queries in, host results out).  Corpus row j is a hit of

@@ -270,6 +270,8 @@ RowKind row_kind(int dtype) {
     case PMM_DTYPE_BF16: return RowKind{2, kBf16DAlign, 4, 4, 2};
     // int8: [u32 sum of squares | f32 1 / sqrt(sum)]; the i8 entries read both by name
     case PMM_DTYPE_I8: return RowKind{1, kI8DAlign, 4, 2, 0};
+    // bit rows (d = w packed bytes): [u32 popcount]
+    case PMM_DTYPE_BITS: return RowKind{1, kBitsAlign, 4, 1, 0};
     default: return RowKind{4, 32, 4, 4, 2};
   }
 }
@@ -2596,6 +2598,202 @@ int validate_i8(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
   return PMM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Hamming top-k over bit rows (pmm_bits.hip; DESIGN.md §4d "Bit rows"): rows of
+// w packed bytes, the integer distance popcount(q ^ c) as an f64 score, lower
+// first, ties to the lower index.  One route per call, decided here: the
+// workspace is sized by it and the executor follows it.
+//   native   k <= kFusedMaxK: the chunked scan on the int8 MFMA with the
+//            euclidean key over the rows' popcounts; rows whose candidate
+//            buffer overflowed are gathered and scanned again in chunks of
+//            cap - k columns, which cannot overflow (a select leaves at most k
+//            entries), and their lists written to the rows' places;
+//   widened  otherwise: both sides expanded to 0/1 f64 rows in the workspace
+//            and searched by topk_f64_device_impl (euclidean); the score is
+//            rint(s * s).
+// ---------------------------------------------------------------------------
+struct BitsRoute {
+  bool native = false;
+  ChunkSchedule sched;  // native
+  size_t off_count = 0, off_qs = 0, off_cs = 0, off_tkey = 0, off_tidx = 0, off_cnt = 0, off_ovf = 0, off_rows = 0,
+         off_gq = 0, off_gqs = 0, off_cand = 0;
+  bool fused64 = false;  // widened: the f64 path's own route
+  int64_t dp64 = 0;
+  size_t off_q64 = 0, off_c64 = 0, off_w64 = 0;
+  size_t total = 0;
+};
+
+// The candidate-buffer capacity: chunk_cap's, which PMM_BITS_CAP (per call; a
+// power of two from 64 up, above k and below the rule's value) lowers, so that
+// a test reaches the overflow re-run with a small corpus.
+int bits_cap(int64_t k) {
+  const int cap = chunk_cap(k);
+  const char *e = getenv("PMM_BITS_CAP");
+  const int v = e ? atoi(e) : 0;
+  return (v >= 64 && v > k && v < cap && (v & (v - 1)) == 0) ? v : cap;
+}
+
+BitsRoute route_bits(int64_t m, int64_t n, int64_t w, int64_t k) {
+  BitsRoute r;
+  const int64_t dp = padded_dim(PMM_DTYPE_BITS, w);
+  r.native = k <= kFusedMaxK;
+  Layout L;
+  if (!r.native) {
+    r.dp64 = padded_dim(PMM_DTYPE_F64, 8 * w);
+    r.fused64 = f64_use_fused(m, n, k);
+    r.off_q64 = L.take((size_t)m * r.dp64 * 8);
+    r.off_c64 = L.take((size_t)n * r.dp64 * 8);
+    r.off_w64 = L.off;
+    r.total = L.off + f64_workspace_bytes(m, n, k, r.fused64);
+    return r;
+  }
+  r.sched = chunk_schedule(m, n, k, bits_cap(k));
+  const int64_t mc = r.sched.mc;
+  r.off_count = L.take(4);
+  r.off_qs = L.take((size_t)m * 4);
+  r.off_cs = L.take((size_t)n * 4);
+  r.off_tkey = L.take((size_t)mc * 4);
+  r.off_tidx = L.take((size_t)mc * 4);
+  r.off_cnt = L.take((size_t)mc * 4);
+  r.off_ovf = L.take((size_t)mc * 4);
+  r.off_rows = L.take((size_t)m * 4);
+  r.off_gq = L.take((size_t)m * dp);  // the re-run's gathered rows and their popcounts
+  r.off_gqs = L.take((size_t)m * 4);
+  r.off_cand = L.take((size_t)mc * r.sched.cap * 16);
+  r.total = L.off;
+  return r;
+}
+
+// The executor over the route's workspace w (route.total bytes).  dq / dc:
+// device rows of packed bytes, strides multiples of 16 and >= roundup(wb, 16),
+// zero-padded.  cs_pre: the corpus rows' popcounts already on the device (a
+// handle's), else nullptr.  Synchronises the stream (the overflow count is
+// read back).
+int topk_bits_device_impl(const BitsRoute &r, const uint8_t *dq, int64_t ldq, int64_t m, const uint8_t *dc,
+                          int64_t ldc, int64_t n, int64_t wb, int64_t k, uint32_t index_base, uint32_t *oi,
+                          double *os, char *w, hipStream_t s, const uint32_t *cs_pre = nullptr) {
+  if (!r.native) {
+    double *q64 = (double *)(w + r.off_q64), *c64 = (double *)(w + r.off_c64);
+    {
+      Timed t("widen_bits_f64", s);
+      HIP_TRY(launch_bits_widen(dq, ldq, m, (int)wb, q64, r.dp64, s));
+      HIP_TRY(launch_bits_widen(dc, ldc, n, (int)wb, c64, r.dp64, s));
+    }
+    if (int rc = topk_f64_device_impl(q64, r.dp64, m, c64, r.dp64, n, 8 * wb, k, kMetricEuclidean, index_base, oi, os,
+                                      w + r.off_w64, s, r.fused64))
+      return rc;
+    HIP_TRY(launch_bits_square(os, m * k, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  }
+  const int64_t dp = padded_dim(PMM_DTYPE_BITS, wb);
+  unsigned *count = (unsigned *)(w + r.off_count);
+  uint32_t *qs = (uint32_t *)(w + r.off_qs), *cs = (uint32_t *)(w + r.off_cs);
+  int *rows = (int *)(w + r.off_rows);
+  uint32_t *tkey = (uint32_t *)(w + r.off_tkey), *tidx = (uint32_t *)(w + r.off_tidx);
+  unsigned *cnt = (unsigned *)(w + r.off_cnt), *ovf = (unsigned *)(w + r.off_ovf);
+  Ent *cand = (Ent *)(w + r.off_cand);
+  HIP_TRY(hipMemsetAsync(count, 0, 4, s));
+  {
+    Timed t("bits_popcount", s);
+    HIP_TRY(launch_bits_popcount(dq, m, ldq, (int)dp, qs, s));
+    if (cs_pre) {
+      cs = (uint32_t *)cs_pre;
+    } else {
+      HIP_TRY(launch_bits_popcount(dc, n, ldc, (int)dp, cs, s));
+    }
+  }
+  const ChunkSchedule &sched = r.sched;
+  // One scan of `mq` rows (q, their popcounts pq) in passes of sched.mc.  map
+  // nullptr: the schedule's growing chunks, lists to rows r0 .. of oi / os,
+  // overflowed rows collected; map: the re-run of the gathered rows map[i], in
+  // chunks of cap - k columns.
+  auto scan = [&](const uint8_t *q, int64_t ld, const uint32_t *pq, int64_t mq, const int *map) -> int {
+    for (int64_t r0 = 0; r0 < mq; r0 += sched.mc) {
+      const int rws = (int)std::min<int64_t>(sched.mc, mq - r0);
+      HIP_TRY(launch_i8_reset(tkey, tidx, cnt, ovf, rws, s));
+      I8TopkArgs a{};
+      a.q = (const int8_t *)(q + r0 * ld);
+      a.c = (const int8_t *)dc;
+      a.qs = pq + r0;
+      a.cs = cs;
+      a.ldq = ld;
+      a.ldc = ldc;
+      a.M = rws;
+      a.D = (int)dp;
+      a.metric = kMetricEuclidean;
+      a.tkey = tkey;
+      a.tidx = tidx;
+      a.cnt = cnt;
+      a.cand = cand;
+      a.cap = sched.cap;
+      I8SelArgs sa{};
+      sa.cand = cand;
+      sa.cnt = cnt;
+      sa.cap = sched.cap;
+      sa.M = rws;
+      sa.k = (int)k;
+      sa.P = sched.cap;
+      sa.tkey = tkey;
+      sa.tidx = tidx;
+      sa.ovf = ovf;
+      sa.metric = kMetricEuclidean;  // (the select's exact rule: the k-th entry itself)
+      sa.qs = pq + r0;
+      sa.cs = cs;
+      sa.index_base = index_base;
+      sa.out_idx = map ? oi : oi + r0 * k;
+      sa.out_score = map ? os : os + r0 * k;
+      int64_t seen = 0, chunk = map ? sched.cap - k : sched.s0;
+      while (seen < n) {
+        const int64_t cc = std::min<int64_t>(chunk, n - seen);
+        a.col0 = (int)seen;
+        a.ncol = (int)cc;
+        {
+          Timed t("gemm_bits_topk", s);
+          HIP_TRY(launch_gemm_bits_topk(a, s));
+        }
+        seen += cc;
+        if (seen < n) {
+          Timed t("select_bits", s);
+          HIP_TRY(launch_i8_select(sa, s));
+        } else {
+          Timed t("bits_finish", s);
+          HIP_TRY(launch_bits_finish(sa, map ? map + r0 : nullptr, s));
+        }
+        if (!map) chunk = seen * sched.g;
+      }
+      if (!map) HIP_TRY(launch_i8_collect(ovf, rws, (int)r0, count, rows, s));
+    }
+    return PMM_OK;
+  };
+  if (int rc = scan(dq, ldq, qs, m, nullptr)) return rc;
+  // rows that dropped candidates: again, in chunks that cannot overflow
+  unsigned nov = 0;
+  HIP_TRY(hipMemcpyAsync(&nov, count, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (nov) {
+    uint8_t *gq = (uint8_t *)(w + r.off_gq);
+    uint32_t *gqs = (uint32_t *)(w + r.off_gqs);
+    {
+      Timed t("bits_gather", s);
+      HIP_TRY(launch_bits_gather(dq, ldq, rows, nov, gq, dp, qs, gqs, s));
+    }
+    if (int rc = scan(gq, dp, gqs, nov, rows)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return PMM_OK;
+}
+
+// What every bit-row entry checks before it touches a device.
+int validate_bits(int64_t m, int64_t n, int64_t w, int64_t k) {
+  int rc = validate_sizes(m, n, w, k, true);
+  if (rc) return rc;
+  if (w > kBitsMaxW)
+    return fail(PMM_ERR_UNSUPPORTED, "bit rows take w <= %d bytes (got %lld): split wider rows and add the distances",
+                kBitsMaxW, (long long)w);
+  return PMM_OK;
+}
+
 }  // namespace
 
 // Device-resident corpus (pmm_corpus_*): padded f32 rows in HBM plus the
@@ -2723,9 +2921,9 @@ static const ScreenImage *corpus_screen_image(const pmm_corpus *h, hipStream_t s
 // A handle serves the one top-k entry of its row type: the others refuse it
 // and name that entry.
 static int wrong_handle(const pmm_corpus *h) {
-  static const char *const kRows[] = {"f32", "f64", "bf16", "int8"};
+  static const char *const kRows[] = {"f32", "f64", "bf16", "int8", "bit"};
   static const char *const kEntry[] = {"pmm_topk_f32_corpus", "pmm_topk_f64_corpus", "pmm_topk_bf16_corpus",
-                                       "pmm_topk_i8_corpus"};
+                                       "pmm_topk_i8_corpus", "pmm_topk_bits_corpus"};
   return fail(PMM_ERR_ARG, "the corpus handle holds %s rows: use %s", kRows[h->dtype], kEntry[h->dtype]);
 }
 
@@ -2761,6 +2959,9 @@ static int check_subset_parent(const pmm_corpus *p, pmm_corpus **out) {
                 (int)p->shards.size());
   if (p->dtype == PMM_DTYPE_I8)
     return fail(PMM_ERR_UNSUPPORTED, "an int8 corpus handle has no subsets and no partitions: pmm_topk_i8_corpus searches "
+                                     "all of its rows");
+  if (p->dtype == PMM_DTYPE_BITS)
+    return fail(PMM_ERR_UNSUPPORTED, "a bit corpus handle has no subsets and no partitions: pmm_topk_bits_corpus searches "
                                      "all of its rows");
   return PMM_OK;
 }
@@ -2845,7 +3046,7 @@ static int subset_build(const pmm_corpus *p, uint32_t *map, int64_t s, unsigned 
 // the thread's lifetime), rounded with the norms of both metrics in one pass.
 static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const void *c, float *stage, hipStream_t s) {
   const int64_t d = h->d, dp = h->dp, n = x.n;
-  const size_t elem = h->dtype == PMM_DTYPE_F64 ? 8 : h->dtype == PMM_DTYPE_I8 ? 1 : 4;  // of the HOST rows
+  const size_t elem = h->dtype == PMM_DTYPE_F64 ? 8 : (h->dtype == PMM_DTYPE_I8 || h->dtype == PMM_DTYPE_BITS) ? 1 : 4;  // of the HOST rows
   const void *src = (const char *)c + (size_t)x.lo * d * elem;
   hipError_t e1, e2;
   if (h->dtype == PMM_DTYPE_BF16) {
@@ -2861,6 +3062,10 @@ static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const vo
     if (h->dtype == PMM_DTYPE_I8) {
       Timed t("norms_i8", s);
       e1 = launch_i8_norms(x.rows_as<int8_t>(), n, dp, (int)dp, (uint32_t *)x.norms, (float *)x.norms + n, s);
+      e2 = hipSuccess;
+    } else if (h->dtype == PMM_DTYPE_BITS) {
+      Timed t("bits_popcount", s);
+      e1 = launch_bits_popcount(x.rows_as<uint8_t>(), n, dp, (int)dp, (uint32_t *)x.norms, s);
       e2 = hipSuccess;
     } else if (h->dtype == PMM_DTYPE_F64) {
       double *nm = (double *)x.norms;
@@ -2893,9 +3098,10 @@ static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_cor
   DevScope scope;
   if ((rc = ensure_device(&dev, &scope, list_root()))) return rc;
   if (dtype == PMM_DTYPE_I8 && (rc = validate_i8(0, n, d, 0, kMetricDot))) return rc;  // (the dimension limit)
+  if (dtype == PMM_DTYPE_BITS && (rc = validate_bits(0, n, d, 0))) return rc;          // (the width limit)
   std::vector<int> devs = devices_snapshot();
-  // (an int8 handle is not sharded: it lives on the list's first device)
-  if (devs.size() <= 1 || dtype == PMM_DTYPE_I8) devs.assign(1, dev);
+  // (an int8 or bit handle is not sharded: it lives on the list's first device)
+  if (devs.size() <= 1 || dtype == PMM_DTYPE_I8 || dtype == PMM_DTYPE_BITS) devs.assign(1, dev);
   const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
   const RowKind rk = row_kind(dtype);
   pmm_corpus *h = new pmm_corpus();
@@ -3004,12 +3210,14 @@ static int corpus_topk(const pmm_corpus *h, int dtype, const Row *q, int64_t m, 
   if (!h) return fail(PMM_ERR_ARG, "null corpus");
   if (h->partitioned()) return partitioned_handle(h);
   if (h->dtype != dtype) return wrong_handle(h);
-  int rc = dtype == PMM_DTYPE_I8 ? validate_i8(m, h->n, h->d, k, metric) : validate_sizes(m, h->n, h->d, k, true);
+  int rc = dtype == PMM_DTYPE_I8     ? validate_i8(m, h->n, h->d, k, metric)
+           : dtype == PMM_DTYPE_BITS ? validate_bits(m, h->n, h->d, k)
+                                     : validate_sizes(m, h->n, h->d, k, true);
   if (rc) return rc;
   if ((rc = check_metric(metric))) return rc;
   if (m == 0 || k == 0) return PMM_OK;
   if ((rc = need_buffers(q, out_idx, out_score))) return rc;
-  if constexpr (!std::is_same<Row, int8_t>::value) {  // (an int8 handle has one shard)
+  if constexpr (!std::is_same<Row, int8_t>::value && !std::is_same<Row, uint8_t>::value) {  // (an int8 or bit handle has one shard)
     if (h->shards.size() > 1) {
       // (the f32 and bf16 shards run the fused top-k only; f64 has a path for every k)
       if (dtype != PMM_DTYPE_F64 && k > kFusedMaxK)
@@ -4070,8 +4278,9 @@ static int64_t range_sort_max() {
 // What the range and self entries (`what`) refuse in a handle.
 static int range_handle(const pmm_corpus *h, const char *what) {
   if (h->partitioned()) return partitioned_handle(h);
-  if (h->dtype == PMM_DTYPE_I8)
-    return fail(PMM_ERR_UNSUPPORTED, "%s takes an f32 handle: an int8 handle has no %s", what, what);
+  if (h->dtype == PMM_DTYPE_I8 || h->dtype == PMM_DTYPE_BITS)
+    return fail(PMM_ERR_UNSUPPORTED, "%s takes an f32 handle: %s handle has no %s", what,
+                h->dtype == PMM_DTYPE_I8 ? "an int8" : "a bit", what);
   if (h->dtype != PMM_DTYPE_F32) {
     static const char *const kRows[] = {"f32", "f64", "bf16"};
     return fail(PMM_ERR_ARG, "%s takes an f32 handle: this one holds %s rows", what, kRows[h->dtype]);
@@ -4486,7 +4695,7 @@ int pmm_topk_f32_candidates(const pmm_corpus *h, const float *q, int64_t m, cons
   int rc = check_metric(metric);
   if (rc) return rc;
   if (h->dtype != PMM_DTYPE_F32) {
-    static const char *const kRows[] = {"f32", "f64", "bf16", "int8"};
+    static const char *const kRows[] = {"f32", "f64", "bf16", "int8", "bit"};
     return fail(PMM_ERR_ARG, "candidate search takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
   }
   if (h->partitioned())
@@ -4796,6 +5005,178 @@ int pmm_topk_i8_corpus(const pmm_corpus *h, const int8_t *q, int64_t m, int64_t 
         const CorpusShard &x = h->shards[0];
         return topk_i8_device_impl(route, (const int8_t *)f.q, h->dp, m, x.rows_as<int8_t>(), h->dp, h->n, h->d, k, metric,
                                    0u, f.oi, f.os, f.w, f.s, (const uint32_t *)x.norms, (const float *)x.norms + h->n);
+      });
+}
+
+// ---- bit rows (DESIGN.md §4d "Bit rows") ----
+
+int pmm_pack_sign_device(const float *x, int64_t ldx, int64_t rows, int64_t d, uint8_t *out, int64_t ld_out,
+                         void *stream) {
+  if (rows < 0 || d < 0 || rows > INT32_MAX || d > INT32_MAX - 64)
+    return fail(PMM_ERR_ARG, "size out of range (rows=%lld d=%lld)", (long long)rows, (long long)d);
+  if (rows == 0) return PMM_OK;
+  if (d == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
+  if (int rc = need_buffers(x, out)) return rc;
+  const int64_t w8 = cdiv(d, 64) * 8;  // the bytes written per row: whole 8-byte words
+  if (ldx < d || ld_out < w8 || (ld_out & 7) || ((uintptr_t)x & 3) || ((uintptr_t)out & 7))
+    return fail(PMM_ERR_ARG,
+                "sign packing needs ldx >= d at a 4-byte-aligned address and ld_out >= roundup(ceil(d / 8), 8), a "
+                "multiple of 8, at an 8-byte-aligned address (d=%lld ldx=%lld ld_out=%lld)",
+                (long long)d, (long long)ldx, (long long)ld_out);
+  int dev;
+  if (int rc = ensure_device(&dev)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timed t("pack_sign", s);
+  HIP_TRY(launch_pack_sign(x, ldx, rows, (int)d, out, ld_out, nullptr, s));
+  return PMM_OK;
+}
+
+size_t pmm_topk_bits_workspace_bytes(int64_t m, int64_t n, int64_t w, int64_t k) {
+  if (m <= 0 || n <= 0 || w <= 0 || k <= 0 || w > kBitsMaxW) return 0;
+  return route_bits(m, n, w, k).total;
+}
+
+int pmm_topk_bits_device(const uint8_t *q, int64_t ldq, int64_t m, const uint8_t *c, int64_t ldc, int64_t n, int64_t w,
+                         int64_t k, uint32_t index_base, uint32_t *out_idx, double *out_score, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  int rc = validate_bits(m, n, w, k);
+  if (rc) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
+  const int64_t dp = padded_dim(PMM_DTYPE_BITS, w);
+  if (w == 0 || ldq < dp || ldc < dp || (ldq & 15) || (ldc & 15) || ((uintptr_t)q & 15) || ((uintptr_t)c & 15))
+    return fail(PMM_ERR_ARG,
+                "device bit rows need row strides >= roundup(w, 16) that are multiples of 16 (zero-padded) and "
+                "16-byte-aligned bases (w=%lld ldq=%lld ldc=%lld)",
+                (long long)w, (long long)ldq, (long long)ldc);
+  int dev;
+  if ((rc = ensure_device(&dev))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const BitsRoute route = route_bits(m, n, w, k);
+  void *ws = workspace;
+  if (ws) {
+    if (workspace_bytes < route.total || ((uintptr_t)ws & 255))
+      return fail(PMM_ERR_ARG, "the bit-row workspace needs %zu bytes at a 256-byte-aligned address (got %zu): size it "
+                               "with pmm_topk_bits_workspace_bytes", route.total, workspace_bytes);
+  } else if ((rc = arena(dev, s, route.total, &ws))) {
+    return rc;
+  }
+  rc = topk_bits_device_impl(route, q, ldq, m, c, ldc, n, w, k, index_base, out_idx, out_score, (char *)ws, s);
+  if (rc) return rc;
+  return workspace ? PMM_OK : arena_record(dev, s);
+}
+
+int pmm_topk_bits(const uint8_t *q, int64_t m, const uint8_t *c, int64_t n, int64_t w, int64_t k, uint32_t *out_idx,
+                  double *out_score) {
+  int rc = validate_bits(m, n, w, k);
+  if (rc) return rc;
+  if (m == 0 || k == 0) return PMM_OK;
+  if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
+  if (w == 0) return fail(PMM_ERR_ARG, "Zero-dimensional vectors");
+  if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
+  // (a device list does not shard bit rows: the call runs on its first device)
+  const int64_t dp = padded_dim(PMM_DTYPE_BITS, w);
+  const BitsRoute route = route_bits(m, n, w, k);
+  return host_topk(
+      nullptr, HostRows{q, m, w, dp, 1}, HostRows{c, n, w, dp, 1}, m, k, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) { return route.total; },
+      [&](const HostCall<double> &f) {
+        return topk_bits_device_impl(route, (const uint8_t *)f.q, dp, m, (const uint8_t *)f.c, dp, n, w, k, 0u, f.oi,
+                                     f.os, f.w, f.s);
+      });
+}
+
+int pmm_corpus_create_bits(const uint8_t *c, int64_t n, int64_t w, pmm_corpus **out) {
+  return corpus_create(PMM_DTYPE_BITS, c, n, w, out);
+}
+
+// The sign bits of a resident f32 handle's rows, packed on the device from the
+// handle's own rows (no upload) with the popcounts from the same pass.  A
+// derived parent's index map is copied, so the lists keep the numbering of
+// the parent's parent.
+int pmm_corpus_sign_bits(const pmm_corpus *p, pmm_corpus **out) {
+  if (!out) return fail(PMM_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (!p) return fail(PMM_ERR_ARG, "null corpus");
+  if (p->partitioned())
+    return fail(PMM_ERR_ARG, "the parent is a partitioned handle (pmm_corpus_partition): its rows are stored group by "
+                             "group; take the sign bits of its parent");
+  if (p->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16", "int8", "bit"};
+    return fail(PMM_ERR_ARG, "sign bits are taken from an f32 handle: this one holds %s rows", kRows[p->dtype]);
+  }
+  if (p->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no sign-bit handle: derive from a handle "
+                                     "of one shard", (int)p->shards.size());
+  const int64_t w = cdiv(p->d, 8);
+  int rc = validate_bits(0, p->n, w, 0);
+  if (rc) return rc;
+  const CorpusShard &px = p->shards[0];
+  int dev;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, px.device))) return rc;
+  hipStream_t s;
+  if ((rc = thread_stream(dev, &s))) return rc;
+  pmm_corpus *h = new pmm_corpus();
+  h->n = p->n;
+  h->d = w;
+  h->dp = padded_dim(PMM_DTYPE_BITS, w);
+  h->dtype = PMM_DTYPE_BITS;
+  h->shards.resize(1);
+  CorpusShard &x = h->shards[0];
+  x.device = px.device;
+  x.lo = 0;
+  x.n = p->n;
+  hipError_t e = hipMalloc(&x.rows, (size_t)x.n * h->dp);
+  if (e == hipSuccess) e = hipMalloc(&x.norms, (size_t)x.n * 4);
+  if (e == hipSuccess && p->map) e = hipMalloc(&h->map, (size_t)x.n * 4);
+  if (e != hipSuccess) {
+    pmm_corpus_destroy(h);
+    return fail(PMM_ERR_HIP, "sign-bit allocation failed on device %d: %s", px.device, hipGetErrorString(e));
+  }
+  // (the kernel writes roundup(w, 8) bytes of a row; the stride is roundup(w, 16))
+  if (h->dp != cdiv(w, 8) * 8) e = hipMemsetAsync(x.rows, 0, (size_t)x.n * h->dp, s);
+  if (e == hipSuccess) {
+    Timed t("pack_sign", s);
+    e = launch_pack_sign(px.rows_as<float>(), p->dp, p->n, (int)p->d, (uint8_t *)x.rows, h->dp, (uint32_t *)x.norms, s);
+  }
+  if (e == hipSuccess && p->map) e = hipMemcpyAsync(h->map, p->map, (size_t)x.n * 4, hipMemcpyDeviceToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) {
+    pmm_corpus_destroy(h);
+    return fail(PMM_ERR_HIP, "sign packing failed: %s", hipGetErrorString(e));
+  }
+  *out = h;
+  return PMM_OK;
+}
+
+int pmm_corpus_bits_rows(const pmm_corpus *h, uint8_t *out) {
+  if (!h || !out) return fail(PMM_ERR_ARG, "null argument");
+  if (h->dtype != PMM_DTYPE_BITS) return wrong_handle(h);
+  int dev, rc;
+  DevScope scope;
+  if ((rc = ensure_device(&dev, &scope, h->shards[0].device))) return rc;
+  // (hipMemcpy2D waits for the copy; the handle's rows were complete at creation)
+  HIP_TRY(hipMemcpy2D(out, (size_t)h->d, h->shards[0].rows, (size_t)h->dp, (size_t)h->d, (size_t)h->n,
+                      hipMemcpyDeviceToHost));
+  return PMM_OK;
+}
+
+int pmm_topk_bits_corpus(const pmm_corpus *h, const uint8_t *q, int64_t m, int64_t k, uint32_t *out_idx,
+                         double *out_score) {
+  BitsRoute route;
+  return corpus_topk(
+      h, PMM_DTYPE_BITS, q, m, k, kMetricEuclidean, out_idx, out_score,
+      [&](const HostCall<double> &, Layout &) {
+        route = route_bits(m, h->n, h->d, k);
+        return route.total;
+      },
+      [&](const HostCall<double> &f) {
+        const CorpusShard &x = h->shards[0];
+        return topk_bits_device_impl(route, (const uint8_t *)f.q, h->dp, m, x.rows_as<uint8_t>(), h->dp, h->n, h->d, k, 0u,
+                                     f.oi, f.os, f.w, f.s, (const uint32_t *)x.norms);
       });
 }
 

@@ -527,6 +527,29 @@ hipError_t launch_i8_widen(const int8_t *src, int64_t ld, const int *rows, int64
                            int64_t ldd, hipStream_t s);
 hipError_t launch_i8_scatter(const uint32_t *oi, const double *os, const int *rows, int64_t r, int k,
                              uint32_t *out_idx, double *out_score, hipStream_t s);
+// ---- bit rows (pmm_bits.hip) ----
+// Packed rows of w bytes (bit j = (byte[j >> 3] >> (j & 7)) & 1) at a stride
+// that is a multiple of kBitsAlign bytes, zero-padded: the search kernel's
+// staging group.  The MFMA scan takes w up to kBitsMaxW (no wider row is
+// served) and k up to kFusedMaxK; past that k both sides are expanded to 0/1
+// f64 rows and searched by the f64 path.  The scan reuses I8TopkArgs /
+// I8SelArgs with the euclidean key, D in packed bytes and qs / cs the rows'
+// popcounts, and launch_i8_select / _reset / _collect as they are.
+constexpr int kBitsAlign = 16;
+constexpr int kBitsMaxW = 8192;
+// rows of roundup(ceil(d / 8), 8) bytes written whole (ld_out a multiple of 8, out 8-byte aligned); pop optional
+hipError_t launch_pack_sign(const float *x, int64_t ldx, int64_t rows, int d, uint8_t *out, int64_t ld_out,
+                            uint32_t *pop, hipStream_t s);
+// pop[r] = the popcount of the first dp bytes (a multiple of 16) of row r
+hipError_t launch_bits_popcount(const uint8_t *a, int64_t rows, int64_t ld, int dp, uint32_t *pop, hipStream_t s);
+hipError_t launch_gemm_bits_topk(const I8TopkArgs &a, hipStream_t s);
+// the lists of buffer rows 0 .. a.M - 1 to output rows rows[r] (nullptr: r), scores the integer distances
+hipError_t launch_bits_finish(const I8SelArgs &a, const int *rows, hipStream_t s);
+hipError_t launch_bits_gather(const uint8_t *src, int64_t ld, const int *rows, int64_t r, uint8_t *dst, int64_t ldd,
+                              const uint32_t *ps, uint32_t *pd, hipStream_t s);
+hipError_t launch_bits_widen(const uint8_t *src, int64_t ld, int64_t r, int w, double *dst, int64_t ldd,
+                             hipStream_t s);
+hipError_t launch_bits_square(double *score, int64_t total, hipStream_t s);
 // full-row sort fallback for very large k
 hipError_t launch_rowsort_global(const void *scores, int64_t lds, int rows, int N, int is_f64,
                                  int metric, void *keys_ws, int P2, int k, uint32_t index_base,

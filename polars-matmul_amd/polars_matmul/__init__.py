@@ -58,13 +58,17 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     _topk_self,
     _within,
     _within_self,
+    _sign_bits,
+    _topk_hamming,
+    pack_sign,
     get_devices,
     set_devices,
 )
 from polars_matmul import _native
 
 __version__ = "0.1.4"
-__all__ = ["PmmNamespace", "topk", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices"]
+__all__ = ["PmmNamespace", "topk", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices",
+           "pack_sign", "topk_hamming"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
 Compute = Literal["f32", "bf16"]
@@ -171,6 +175,31 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     if ids is not None:
         idx = ids[idx]
     return idx, sc.astype(np.float64, copy=False)
+
+
+def topk_hamming(queries_u8: np.ndarray, corpus_u8: np.ndarray, k: int):
+    """numpy-level exact Hamming top-k (an extension) of packed bit rows --
+    (m, w) and (n, w) uint8, ``pack_sign``'s output: (indices uint32 [m, k'],
+    scores float64 [m, k']), k' = min(k, n), the integer distances
+    popcount(q XOR c), least first, ties to the lower index.  A numpy corpus
+    has no cached handle (as in ``topk``); ``_topk_hamming`` on an Arrow or
+    Polars column searches the cached bit handle of the corpus."""
+    from polars_matmul._polars_matmul import _bits_only
+
+    q, c = np.asarray(queries_u8), np.asarray(corpus_u8)
+    if q.dtype != np.uint8 or c.dtype != np.uint8:
+        raise _bits_only(f"got {q.dtype} queries and a {c.dtype} corpus")
+    if q.ndim != 2 or c.ndim != 2:
+        raise TypeError(f"expected 2-D arrays of packed bits, got shapes {q.shape} and {c.shape}")
+    if q.shape[1] != c.shape[1]:
+        raise RuntimeError(
+            f"Dimension mismatch: left has {q.shape[1]} dimensional vectors, "
+            f"right has {c.shape[1]} dimensional vectors"
+        )
+    kk = min(int(k), c.shape[0])
+    if kk <= 0 or q.shape[0] == 0:
+        return np.zeros((q.shape[0], 0), dtype=np.uint32), np.zeros((q.shape[0], 0), dtype=np.float64)
+    return _native.topk_bits_host(q, np.ascontiguousarray(c), kk)
 
 
 def within(queries: np.ndarray, corpus: np.ndarray, threshold: float, metric: Metric = "cosine", subset=None,
@@ -436,6 +465,33 @@ if pl is not None:
                 is_elementwise=False,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
             )
+
+        def topk_hamming(self, corpus: "pl.Series", k: int) -> "pl.Expr":
+            """Exact Hamming top-k (an extension) of a bit column -- UInt8
+            lists or arrays of packed bits, ``sign_bits``' output -- against a
+            bit corpus: List[Struct{index: u32, score: f64}], the k rows of
+            least distance popcount(row XOR corpus row), ascending by
+            (distance, index).  The cheap first stage of a two-stage search:
+            its ids feed ``topk(..., candidates=)``."""
+            if isinstance(corpus, pl.Expr):
+                raise TypeError(
+                    "corpus must be a Polars Series, not an Expression. "
+                    "Use corpus['column_name'] or corpus.get_column('column_name')."
+                )
+            return self._expr.map_batches(
+                lambda s: _topk_hamming(s, corpus, k),
+                is_elementwise=True,
+                return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def sign_bits(self) -> "pl.Expr":
+            """The sign of every component packed one bit per dimension (an
+            extension): Array[UInt8, ceil(d / 8)], bit j of a row set iff
+            component j is > 0.  Float32 columns only.  No ``return_dtype``
+            is declared: the width ceil(d / 8) comes from the rows' length,
+            which a List column's dtype does not carry, so a lazy frame learns
+            the column's type when the expression runs."""
+            return self._expr.map_batches(lambda s: _sign_bits(s), is_elementwise=True)
 
         def matmul(self, corpus: "pl.Series", flatten: bool = False) -> "pl.Expr":
             """All pairwise dot products: Array[f32|f64, N] per row, or one flat

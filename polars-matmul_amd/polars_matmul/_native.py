@@ -99,6 +99,14 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_i8_device",
     "pmm_topk_i8_workspace_bytes",
     "pmm_corpus_create_i8",
+    "pmm_pack_sign_device",
+    "pmm_corpus_create_bits",
+    "pmm_corpus_sign_bits",
+    "pmm_corpus_bits_rows",
+    "pmm_topk_bits",
+    "pmm_topk_bits_corpus",
+    "pmm_topk_bits_workspace_bytes",
+    "pmm_topk_bits_device",
     "pmm_timing_enable",
     "pmm_timing_reset",
     "pmm_timing_read",
@@ -216,6 +224,14 @@ _SIGS = {
     "pmm_topk_i8_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
     "pmm_topk_i8_workspace_bytes": ([_i64, _i64, _i64, _i64, _i32], _sz),
     "pmm_corpus_create_i8": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_pack_sign_device": ([_vp, _i64, _i64, _i64, _vp, _i64, _vp], _i32),
+    "pmm_corpus_create_bits": ([_vp, _i64, _i64, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_sign_bits": ([_vp, ctypes.POINTER(ctypes.c_void_p)], _i32),
+    "pmm_corpus_bits_rows": ([_vp, _vp], _i32),
+    "pmm_topk_bits": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp], _i32),
+    "pmm_topk_bits_corpus": ([_vp, _vp, _i64, _i64, _vp, _vp], _i32),
+    "pmm_topk_bits_workspace_bytes": ([_i64, _i64, _i64, _i64], _sz),
+    "pmm_topk_bits_device": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _u32, _vp, _vp, _vp, _sz, _vp], _i32),
     "pmm_timing_enable": ([_i32], _i32),
     "pmm_timing_reset": ([], _i32),
     "pmm_timing_read": (
@@ -376,6 +392,58 @@ def topk_i8_device(q_ptr: int, ldq: int, m: int, c_ptr: int, ldc: int, n: int, d
 
 def i8_workspace_bytes(m: int, n: int, d: int, k: int, metric: int) -> int:
     return int(_lib.pmm_topk_i8_workspace_bytes(m, n, d, k, metric))
+
+
+def _bit_rows(a, what: str, w=None) -> np.ndarray:
+    """``a`` as the bit-row entries take it: a C-contiguous 2-D uint8 array
+    (of ``w`` bytes a row when given), else the TypeError they raise."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or (w is not None and a.shape[1] != w):
+        width = "" if w is None else f" of {w} bytes a row"
+        raise TypeError(f"{what} takes a 2-D uint8 array of packed bits{width} (pack_sign makes one), "
+                        f"got {a.dtype} with shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def topk_bits_host(q: np.ndarray, c: np.ndarray, k: int):
+    """Host-buffer Hamming top-k of packed bit rows (pmm_topk_bits).  q: (m, w),
+    c: (n, w) uint8; 0 <= k <= n.  Returns (idx uint32 (m, k), scores float64
+    (m, k)): the integer distances, least first, ties to the lower index."""
+    q = _bit_rows(q, "topk_bits_host")
+    c = _bit_rows(c, "topk_bits_host")
+    if q.shape[1] != c.shape[1]:
+        raise ValueError("dimension mismatch")
+    m, w = q.shape
+    n = c.shape[0]
+    idx = np.empty((m, k), dtype=np.uint32)
+    sc = np.empty((m, k), dtype=np.float64)
+    check(_lib.pmm_topk_bits(ptr(q), m, ptr(c), n, w, k, ptr(idx), ptr(sc)))
+    return idx, sc
+
+
+def topk_bits_device(q_ptr: int, ldq: int, m: int, c_ptr: int, ldc: int, n: int, w: int, k: int,
+                     out_idx_ptr: int, out_score_ptr: int, *, index_base: int = 0, workspace: int = 0,
+                     workspace_bytes: int = 0, stream: int = 0) -> None:
+    """pmm_topk_bits_device over device pointers (row strides in bytes)."""
+    check(_lib.pmm_topk_bits_device(q_ptr, ldq, m, c_ptr, ldc, n, w, k, index_base, out_idx_ptr, out_score_ptr,
+                                    workspace or None, workspace_bytes, stream or None))
+
+
+def bits_workspace_bytes(m: int, n: int, w: int, k: int) -> int:
+    return int(_lib.pmm_topk_bits_workspace_bytes(m, n, w, k))
+
+
+def pack_sign_device(x_ptr: int, ldx: int, rows: int, d: int, out_ptr: int, ld_out: int, *, stream: int = 0) -> None:
+    """pmm_pack_sign_device over device pointers: ldx in floats, ld_out in
+    bytes (a multiple of 8, at least roundup(ceil(d / 8), 8))."""
+    check(_lib.pmm_pack_sign_device(x_ptr, ldx, rows, d, out_ptr, ld_out, stream or None))
+
+
+def bits_device_bytes(n: int, w: int) -> int:
+    """HBM a bit corpus of n rows of w packed bytes holds
+    (pmm_corpus_create_bits): the rows at stride roundup(w, 16) and a u32
+    popcount per row."""
+    return n * (-(-w // 16) * 16) + 4 * n
 
 
 class _PinnedBlock:
@@ -640,6 +708,7 @@ DTYPE_F32 = 0
 DTYPE_F64 = 1
 DTYPE_BF16 = 2
 DTYPE_I8 = 3
+DTYPE_BITS = 4
 
 _COMPUTE_MODES = ("f32", "bf16")
 
@@ -730,6 +799,9 @@ class DeviceCorpus:
     in flight, else when the last one releases it -- a cache may evict a
     handle while another thread is still searching it."""
 
+    is_bits = False  # a bit corpus (``bits`` / ``sign_bits``): ``d`` is the bytes of a row, ``topk`` takes no metric
+    _mapped = False  # a derived handle: it holds a uint32 index map beside its rows
+
     def __init__(self, c: np.ndarray, compute: str = "f32"):
         self.compute = check_compute(compute)
         bf16 = compute == "bf16"
@@ -757,18 +829,63 @@ class DeviceCorpus:
         if c.dtype != np.int8 or c.ndim != 2:
             raise TypeError(f"DeviceCorpus.int8 takes a 2-D int8 array, got {c.dtype} with shape {c.shape}")
         c = np.ascontiguousarray(c)
-        self = cls.__new__(cls)
-        self.compute = "f32"
-        self.dtype = np.dtype(np.int8)
         h = ctypes.c_void_p()
         check(_lib.pmm_corpus_create_i8(ptr(c), c.shape[0], c.shape[1], ctypes.byref(h)))
+        return cls._adopt(h, np.int8, c.shape[0], c.shape[1], corpus_device_bytes(c.shape[0], c.shape[1], np.int8))
+
+    @classmethod
+    def _adopt(cls, h, dtype, n: int, d: int, nbytes0: int) -> "DeviceCorpus":
+        """The DeviceCorpus of a native handle made outside ``__init__`` (n
+        rows of d elements of ``dtype``, compute "f32")."""
+        self = cls.__new__(cls)
+        self.compute = "f32"
+        self.dtype = np.dtype(dtype)
         self._h = h
         self._lock = threading.Lock()
         self._refs = 0
         self._closing = False
-        self.n, self.d = c.shape
-        self._nbytes0 = corpus_device_bytes(self.n, self.d, np.int8)
+        self.n, self.d = n, d
+        self._nbytes0 = nbytes0
         return self
+
+    @classmethod
+    def bits(cls, c: np.ndarray) -> "DeviceCorpus":
+        """A bit corpus (pmm_corpus_create_bits): rows of packed bits, ``d``
+        the bytes of a row.  ``topk(packed_queries, k)`` is then the exact
+        Hamming top-k: float64 distances, least first, ties to the lower
+        index."""
+        c = _bit_rows(c, "DeviceCorpus.bits")
+        h = ctypes.c_void_p()
+        check(_lib.pmm_corpus_create_bits(ptr(c), c.shape[0], c.shape[1], ctypes.byref(h)))
+        self = cls._adopt(h, np.uint8, c.shape[0], c.shape[1], bits_device_bytes(*c.shape))
+        self.is_bits = True
+        return self
+
+    def sign_bits(self) -> "DeviceCorpus":
+        """The bit corpus of this f32 handle's rows (pmm_corpus_sign_bits):
+        their signs packed on the device from the resident rows, no upload --
+        the handle ``DeviceCorpus.bits(pack_sign(c))`` makes.  On a
+        ``subset(sel)`` handle the lists keep the parent's row numbers."""
+        h = ctypes.c_void_p()
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_sign_bits(self._h, ctypes.byref(h)))
+        finally:
+            self.release()
+        w = -(-self.d // 8)  # (the same rows: n is this handle's; a derived parent's map is copied)
+        dc = DeviceCorpus._adopt(h, np.uint8, self.n, w, bits_device_bytes(self.n, w) + (4 * self.n if self._mapped else 0))
+        dc.is_bits, dc._mapped = True, self._mapped
+        return dc
+
+    def bit_rows(self) -> np.ndarray:
+        """A bit corpus' rows on the host (pmm_corpus_bits_rows): (n, d) uint8."""
+        out = np.empty((self.n, self.d), dtype=np.uint8)
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_bits_rows(self._h, ptr(out)))
+        finally:
+            self.release()
+        return out
 
     @property
     def nbytes(self) -> int:
@@ -798,9 +915,13 @@ class DeviceCorpus:
             if self._refs == 0 and self._closing:
                 self._destroy()
 
-    def topk(self, q: np.ndarray, k: int, metric: int):
+    def topk(self, q: np.ndarray, k: int, metric=None):
         """(idx uint32 (m, k), scores (m, k) in the corpus dtype); q is
         converted to the corpus dtype."""
+        if self.is_bits:  # (one score, the Hamming distance: no metric)
+            return self._topk_bits(q, k)
+        if metric is None:
+            raise TypeError("topk() needs a metric (only a bit corpus has none)")
         if self.dtype == np.int8 and np.asarray(q).dtype != np.int8:
             raise TypeError(f"an int8 corpus takes int8 queries, not {np.asarray(q).dtype}")
         q = np.ascontiguousarray(q, dtype=self.dtype)
@@ -816,6 +937,18 @@ class DeviceCorpus:
         self.acquire()
         try:
             check(fn(self._h, ptr(q), m, k, metric, ptr(idx), ptr(sc)))
+        finally:
+            self.release()
+        return idx, sc
+
+    def _topk_bits(self, q, k: int):
+        q = _bit_rows(q, "a bit corpus", self.d)
+        m = q.shape[0]
+        idx = np.empty((m, k), dtype=np.uint32)
+        sc = np.empty((m, k), dtype=np.float64)
+        self.acquire()
+        try:
+            check(_lib.pmm_topk_bits_corpus(self._h, ptr(q), m, k, ptr(idx), ptr(sc)))
         finally:
             self.release()
         return idx, sc
@@ -940,6 +1073,7 @@ class DeviceCorpus:
         check(_lib.pmm_corpus_info(h, ctypes.byref(n), None, None))
         dc.n = int(n.value)
         dc._nbytes0 = subset_device_bytes(dc.n, dc.d, dc.dtype, dc.compute)
+        dc._mapped = True
         return dc
 
     def subset(self, sel) -> "DeviceCorpus":

@@ -112,6 +112,16 @@ def _is_i8(arr) -> bool:
     return False
 
 
+def _is_u8(arr) -> bool:
+    """List[u8] / Array[u8, w] / a uint8 matrix: rows of packed bits."""
+    if isinstance(arr, np.ndarray):
+        return arr.dtype == np.uint8
+    t = arr.type
+    if pa.types.is_list(t) or pa.types.is_large_list(t) or pa.types.is_fixed_size_list(t):
+        return t.value_type == pa.uint8()
+    return False
+
+
 def _nrows(arr) -> int:
     return arr.shape[0] if isinstance(arr, np.ndarray) else len(arr)
 
@@ -120,6 +130,8 @@ def _values_numpy(values: pa.Array, np_dtype) -> np.ndarray:
     """Child values cast to the compute dtype, nulls -> 0.0 (src/matmul.rs:192, 224)."""
     if np_dtype == np.int8:  # (only int8 children come here: borrowed as they are)
         target, zero = pa.int8(), 0
+    elif np_dtype == np.uint8:  # (packed bit rows, _topk_hamming: only uint8 children)
+        target, zero = pa.uint8(), 0
     else:
         target, zero = (pa.float32() if np_dtype == np.float32 else pa.float64()), 0.0
     if values.type != target:
@@ -259,6 +271,14 @@ def _persistent_key(original, arrow):
     return _arrow_key(arrow)
 
 
+def _handle_bytes(c: np.ndarray, compute: str) -> int:
+    """HBM the cached handle of c holds; compute "bits" (the key mode of
+    ``_topk_hamming``, not a ``compute=`` value): c is packed bit rows."""
+    if compute == "bits":
+        return _native.bits_device_bytes(c.shape[0], c.shape[1])
+    return _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
+
+
 def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = False):
     """The cache key of this corpus, or None when it is not cacheable.
     numpy_ok (the numpy-level ``within``): a numpy matrix that is searched as
@@ -274,7 +294,7 @@ def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = Fals
         # a handle is sharded over the device list of its creation; an f32
         # and a bf16 handle of one column are two entries
         key = key + (c.dtype.str, tuple(_native.get_devices()), compute)
-    dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
+    dev_bytes = _handle_bytes(c, compute)
     if not _CACHE_ON or key is None or c.nbytes < _CACHE_MIN_BYTES or dev_bytes > _CACHE_BYTES:
         return None
     return key
@@ -286,7 +306,7 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: 
     key = _corpus_key(original, rv, c, compute, numpy_ok)
     if key is None:
         return None
-    dev_bytes = _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
+    dev_bytes = _handle_bytes(c, compute)
     with _cache_lock:
         hit = _cache.get(key)
         if hit is not None:
@@ -294,7 +314,8 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: 
             return hit[1].acquire()
         if not _fits_device(dev_bytes):
             return None
-        dc = (_native.DeviceCorpus.int8(c) if c.dtype == np.int8 and compute == "f32" else
+        dc = (_native.DeviceCorpus.bits(c) if compute == "bits" else
+              _native.DeviceCorpus.int8(c) if c.dtype == np.int8 and compute == "f32" else
               _native.DeviceCorpus(c) if compute == "f32" else _native.DeviceCorpus(c, compute=compute))
         _cache[key] = (rv, dc)
         total = sum(v[1].nbytes for v in _cache.values())
@@ -303,6 +324,17 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: 
             total -= old.nbytes
             old.close()  # freed now, or by its last in-flight user
         return dc.acquire()
+
+
+def _cache_hit(original, rv, c: np.ndarray, compute: str = "f32"):
+    """The ACQUIRED cached handle of this corpus when the cache holds one (the
+    caller releases it), else None: nothing is created or uploaded."""
+    key = _corpus_key(original, rv, c, compute)
+    if key is None:
+        return None
+    with _cache_lock:
+        hit = _cache.get(key)
+        return hit[1].acquire() if hit is not None else None
 
 
 def _reaccount_cache(used) -> None:
@@ -958,6 +990,94 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None, candi
     out = _wrap(_topk_arrow(idx, sc, m, kk), "topk", polars_out)
     _lap("assemble", t)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Bit columns (an extension; no reference counterpart): the sign of every
+# component packed one bit per dimension, searched by Hamming distance -- the
+# cheap first stage whose survivors ``candidates=`` re-scores exactly.
+# ---------------------------------------------------------------------------
+def pack_sign(x) -> np.ndarray:
+    """The sign bits of the rows of x, (rows, ceil(d / 8)) uint8: bit j of a
+    row -- (byte[j >> 3] >> (j & 7)) & 1 -- is 1 iff x[j] > 0, so both zeros,
+    negatives, -inf and NaN give 0; the bits from d up are 0.  The statement
+    the device packing (pmm_pack_sign_device) is tested against."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise TypeError(f"expected a 2-D array of embeddings, got shape {x.shape}")
+    return np.packbits(x > 0, axis=1, bitorder="little")
+
+
+def _bits_only(what: str) -> TypeError:
+    return TypeError(
+        f"Hamming search runs on UInt8 columns of packed bits ({what}); make them with .pmm.sign_bits() / "
+        "polars_matmul.pack_sign(array), or numpy.packbits(bits, axis=1, bitorder='little')"
+    )
+
+
+def _topk_hamming(left, right, k):
+    """Exact Hamming top-k of two bit columns: List[u8] / Array[u8, w] or uint8
+    matrices of w packed bytes a row (a null row reads as zeros).
+    List[Struct{index: u32, score: f64}] per row of ``left``: the min(k,
+    len(right)) rows of ``right`` of least distance popcount(l XOR r), ascending
+    by (distance, index)."""
+    k = _as_usize(k)
+    polars_out = _is_polars_series(left)
+    lv = _to_arrow(left)
+    rv = _to_arrow(right)
+    if not (_is_u8(lv) and _is_u8(rv)):
+        t = [str(a.dtype if isinstance(a, np.ndarray) else a.type) for a in (lv, rv)]
+        raise _bits_only(f"got {t[0]} and {t[1]}")
+    if _nrows(lv) == 0:
+        return _wrap(pa.array([], type=pa.large_list(_TOPK_STRUCT)), "topk_hamming", polars_out)
+    q = _series_to_matrix(lv, np.uint8)
+    c = _series_to_matrix(rv, np.uint8)
+    if q.shape[1] != c.shape[1]:
+        raise _dim_mismatch(q.shape[1], c.shape[1])
+    kk = min(k, c.shape[0])
+    m = q.shape[0]
+    if kk == 0:
+        idx, sc = np.zeros((m, 0), dtype=np.uint32), np.zeros((m, 0), dtype=np.float64)
+    else:
+        _apply_devices_env()
+        dc = _cached_corpus(right, rv, c, "bits")
+        if dc is not None:
+            try:
+                idx, sc = dc.topk(q, kk)
+            finally:
+                dc.release()
+        else:
+            idx, sc = _native.topk_bits_host(q, c, kk)
+    return _wrap(_topk_arrow(idx, sc, m, kk), "topk_hamming", polars_out)
+
+
+def _sign_bits(col):
+    """A Float32 column's sign bits as Array[u8, ceil(d / 8)] (``pack_sign`` of
+    its rows; a null row packs to zeros).  A column whose f32 handle is in the
+    corpus cache (a ``topk`` corpus) is packed on the device from the resident
+    rows (pmm_corpus_sign_bits) and only the bits come back; any other column
+    is packed with NumPy.  The same bytes either way."""
+    polars_out = _is_polars_series(col)
+    v = _to_arrow(col)
+    if not _is_f32(v):
+        t = str(v.dtype if isinstance(v, np.ndarray) else v.type)
+        raise TypeError(f"sign_bits takes a Float32 column (got {t}); cast the embeddings first, e.g. "
+                        "pl.col('embedding').cast(pl.List(pl.Float32)) or array.astype(numpy.float32)")
+    x = _series_to_matrix(v, np.float32)
+    dc = _cache_hit(col, v, x) if len(_native.get_devices()) <= 1 else None  # (a sharded handle has no sign bits)
+    if dc is not None:
+        try:
+            sb = dc.sign_bits()
+            try:
+                bits = sb.bit_rows()
+            finally:
+                sb.close()
+        finally:
+            dc.release()
+    else:
+        bits = pack_sign(x)
+    out = pa.FixedSizeListArray.from_arrays(pa.array(bits.reshape(-1), type=pa.uint8()), bits.shape[1])
+    return _wrap(out, "sign_bits", polars_out)
 
 
 # ---------------------------------------------------------------------------
