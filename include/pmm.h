@@ -753,6 +753,70 @@ int pmm_topk_f32_candidates(const pmm_corpus *corpus, const float *q, int64_t m,
                             uint32_t *out_idx /* m * k */, float *out_score /* m * k */,
                             uint32_t *out_len /* m */);
 
+/* Late interaction (ColBERT / ColPali style): multi-vector documents and the
+ * MaxSim score.  No reference counterpart.
+ *
+ * pmm_corpus_create_f32_docs: an ordinary f32 handle of one shard over the
+ * n_tokens token rows (the rows and norms of pmm_corpus_create_f32, so every
+ * existing entry serves it as the plain handle of its tokens and
+ * pmm_topk_f32_corpus on it is the token-level search) that also keeps the
+ * documents' bounds, on the host and on the device: document c is token rows
+ * [doc_offsets[c], doc_offsets[c + 1]).  The offsets start at 0, end at
+ * n_tokens and ascend strictly (no empty document), else PMM_ERR_ARG naming
+ * the position, before any device call.  Never sharded: with pmm_set_devices
+ * in effect the handle is made on the current device, as the int8 creator's.
+ * pmm_corpus_bytes counts the offsets; pmm_corpus_destroy frees them.  Handles
+ * derived from it (pmm_corpus_subset_*, pmm_corpus_partition,
+ * pmm_corpus_sign_bits) carry no documents. */
+int pmm_corpus_create_f32_docs(const float *tokens, int64_t n_tokens, int64_t d,
+                               const int64_t *doc_offsets /* n_docs + 1 */, int64_t n_docs, pmm_corpus **out);
+
+/* The documents of a handle: *n_docs (0 for a handle without documents) and,
+ * with doc_offsets_out and cap >= n_docs + 1, the n_docs + 1 bounds (a smaller
+ * cap copies nothing: call once with cap = 0 to size the array). */
+int pmm_corpus_docs(const pmm_corpus *corpus, int64_t *n_docs, int64_t *doc_offsets_out, int64_t cap);
+
+/* The largest padded dimension (roundup(d, 32)) the MaxSim kernel serves: its
+ * block of 32 query tokens (dp + 4 floats each) and four waves' document tiles
+ * must fit the CU's 160 KiB of LDS. */
+#define PMM_MAXSIM_MAX_DP 960
+
+/* MaxSim top-k over per-row lists of documents.  Query row i holds the tokens
+ * q_tokens[q_offsets[i] .. q_offsets[i + 1]) (d floats each, Lq_i >= 0 of
+ * them) and lists the documents cand_docs[cand_offsets[i] .. cand_offsets[i +
+ * 1]), strictly ascending, each below n_docs.  The score of (row, document):
+ *   s[t][j]  the engine's f32 pair score of query token t and document token
+ *            j (the K-ordered fmaf chain from +0.0f and, for cosine, the
+ *            epilogue on the two tokens' norms: pmm_topk_f32's bits);
+ *   mx[t]    fmaxf over j from -inf (a NaN pair score is ignored);
+ *   score    (((+0.0f + mx[0]) + mx[1]) + ...) in f32, in token order.
+ * The score is never -0.0.  Row i's result is its documents by (score
+ * descending, document ascending, a NaN score last), the first out_len[i] =
+ * min(k, listed documents) of them; a row without tokens has out_len[i] = 0.
+ * Planes as pmm_topk_f32_candidates': row stride k, the slots past out_len[i]
+ * hold index 0xFFFFFFFF and score +0.0.  metric: cosine or dot (a maximum over
+ * distances is no similarity: euclidean is PMM_ERR_ARG).
+ * One launch scores every pair -- a workgroup takes a query row and up to 64
+ * of its documents, a wave one document at a time on v_mfma_f32_32x32x2_f32
+ * with the max and the sum folded into the epilogue, so no Lq x Ld block
+ * leaves the registers -- into keys in the lists' own layout, which the range
+ * search's sorts and the candidate search's merge order (PMM_RANGE_SORT_MAX is
+ * honoured); one more launch decodes.
+ * Errors.  A null argument, k < 1, negative m, a bad metric or euclidean, a
+ * handle without documents, a derived, partitioned or non-f32 handle, offsets
+ * that do not start at 0 or that descend, a list longer than n_docs:
+ * PMM_ERR_ARG before the handle's device is touched.  A sharded handle, or a
+ * padded dimension above PMM_MAXSIM_MAX_DP: PMM_ERR_UNSUPPORTED.  A list that
+ * does not ascend strictly or holds an id >= n_docs is found on the device
+ * (the id is clamped before it forms an address) and reported after the wait
+ * as PMM_ERR_ARG; the lists are then unspecified.  m = 0: PMM_OK.  Thread-safe
+ * like the other handle entries; synchronises once before it returns. */
+int pmm_topk_f32_maxsim(const pmm_corpus *corpus, const float *q_tokens, const int64_t *q_offsets /* m + 1 */,
+                        int64_t m, const int64_t *cand_offsets /* m + 1 */, const uint32_t *cand_docs,
+                        int64_t k, int metric,
+                        uint32_t *out_idx /* m * k */, float *out_score /* m * k */,
+                        uint32_t *out_len /* m */);
+
 /* Self search: one handle searched against itself -- near-duplicate pairs and
  * the k-nearest-neighbour graph of its rows.  Neither entry takes queries: the
  * handle's n rows are the query rows (nothing is uploaded) and, for the range

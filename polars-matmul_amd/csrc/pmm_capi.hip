@@ -2844,6 +2844,13 @@ struct pmm_corpus {
   std::vector<int64_t> offsets;
   int64_t *d_offsets = nullptr;
   bool partitioned() const { return !offsets.empty(); }
+  // A multi-vector handle (pmm_corpus_create_f32_docs; DESIGN.md §4d
+  // "Multi-vector rows"): document c is rows [doc_offsets[c], doc_offsets[c +
+  // 1]), n_docs + 1 strictly ascending entries on the host, d_doc_offsets their
+  // copy on shard 0's device.  Empty: no documents.  Only pmm_topk_f32_maxsim
+  // reads them: every other entry sees the plain f32 handle of the rows.
+  std::vector<int64_t> doc_offsets;
+  int64_t *d_doc_offsets = nullptr;
 };
 
 static void free_screen_image(const ScreenImage *img) {
@@ -3086,7 +3093,7 @@ static int corpus_fill_shard(const pmm_corpus *h, const CorpusShard &x, const vo
 // The creator behind pmm_corpus_create_f32 / _f64 / _bf16 (c: f32 host rows
 // for bf16).  With a device list the rows are sharded over it: one contiguous
 // shard per listed device, at most n.
-static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_corpus **out) {
+static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_corpus **out, bool one_device = false) {
   if (!out) return fail(PMM_ERR_ARG, "null argument");
   *out = nullptr;
   int rc = validate_sizes(0, n, d, 0, false);
@@ -3100,8 +3107,8 @@ static int corpus_create(int dtype, const void *c, int64_t n, int64_t d, pmm_cor
   if (dtype == PMM_DTYPE_I8 && (rc = validate_i8(0, n, d, 0, kMetricDot))) return rc;  // (the dimension limit)
   if (dtype == PMM_DTYPE_BITS && (rc = validate_bits(0, n, d, 0))) return rc;          // (the width limit)
   std::vector<int> devs = devices_snapshot();
-  // (an int8 or bit handle is not sharded: it lives on the list's first device)
-  if (devs.size() <= 1 || dtype == PMM_DTYPE_I8 || dtype == PMM_DTYPE_BITS) devs.assign(1, dev);
+  // (an int8, bit or multi-vector handle is not sharded: it lives on the list's first device)
+  if (devs.size() <= 1 || dtype == PMM_DTYPE_I8 || dtype == PMM_DTYPE_BITS || one_device) devs.assign(1, dev);
   const int G = (int)std::min<int64_t>((int64_t)devs.size(), n);
   const RowKind rk = row_kind(dtype);
   pmm_corpus *h = new pmm_corpus();
@@ -3985,6 +3992,7 @@ int pmm_corpus_destroy(pmm_corpus *h) {
       free_screen_image(h->screen.exchange(nullptr, std::memory_order_acq_rel));
       if (h->map) (void)hipFree(h->map);
       if (h->d_offsets) (void)hipFree(h->d_offsets);
+      if (h->d_doc_offsets) (void)hipFree(h->d_doc_offsets);
     }
   }
   (void)hipSetDevice(cur);
@@ -4000,6 +4008,7 @@ int pmm_corpus_bytes(const pmm_corpus *h, size_t *bytes) {
   if (h->screen.load(std::memory_order_acquire)) b += screen_image_bytes(h->n, h->d);
   if (h->map) b += (size_t)h->n * 4;
   if (h->d_offsets) b += h->offsets.size() * 8;
+  if (h->d_doc_offsets) b += h->doc_offsets.size() * 8;
   *bytes = b;
   return PMM_OK;
 }
@@ -4858,6 +4867,247 @@ int pmm_topk_f32_candidates(const pmm_corpus *h, const float *q, int64_t m, cons
     return fail(PMM_ERR_ARG, "a candidate id is not a row of the corpus (n=%lld)", (long long)n);
   if (flag & 1u)
     return fail(PMM_ERR_ARG, "candidate ids must be strictly ascending within a row (a row repeats or descends)");
+  return PMM_OK;
+}
+
+// ---- multi-vector rows (DESIGN.md §4d "Multi-vector rows") ----
+
+int pmm_corpus_create_f32_docs(const float *tokens, int64_t n_tokens, int64_t d, const int64_t *doc_offsets,
+                               int64_t n_docs, pmm_corpus **out) {
+  if (!out) return fail(PMM_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (!tokens || !doc_offsets) return fail(PMM_ERR_ARG, "null argument");
+  if (n_docs < 1 || n_tokens < 1)
+    return fail(PMM_ERR_ARG, "a multi-vector corpus needs a document and a token (n_docs=%lld n_tokens=%lld)",
+                (long long)n_docs, (long long)n_tokens);
+  // every bound before any device call
+  if (doc_offsets[0] != 0)
+    return fail(PMM_ERR_ARG, "doc_offsets must start at 0 (doc_offsets[0] = %lld)", (long long)doc_offsets[0]);
+  for (int64_t c = 0; c < n_docs; c++)
+    if (doc_offsets[c + 1] <= doc_offsets[c])
+      return fail(PMM_ERR_ARG, "doc_offsets must ascend strictly (no empty document): doc_offsets[%lld] = %lld follows %lld",
+                  (long long)(c + 1), (long long)doc_offsets[c + 1], (long long)doc_offsets[c]);
+  if (doc_offsets[n_docs] != n_tokens)
+    return fail(PMM_ERR_ARG, "doc_offsets must end at n_tokens (doc_offsets[%lld] = %lld, n_tokens = %lld)",
+                (long long)n_docs, (long long)doc_offsets[n_docs], (long long)n_tokens);
+  pmm_corpus *h = nullptr;
+  int rc = corpus_create(PMM_DTYPE_F32, tokens, n_tokens, d, &h, true);
+  if (rc) return rc;
+  h->doc_offsets.assign(doc_offsets, doc_offsets + n_docs + 1);
+  int dev;
+  DevScope scope;
+  rc = ensure_device(&dev, &scope, h->shards[0].device);
+  if (!rc) {
+    hipError_t e = hipMalloc(&h->d_doc_offsets, (size_t)(n_docs + 1) * 8);
+    if (e == hipSuccess)
+      e = hipMemcpy(h->d_doc_offsets, h->doc_offsets.data(), (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(PMM_ERR_HIP, "document offsets failed on device %d: %s", dev, hipGetErrorString(e));
+  }
+  if (rc) {
+    pmm_corpus_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return PMM_OK;
+}
+
+int pmm_corpus_docs(const pmm_corpus *h, int64_t *n_docs, int64_t *doc_offsets_out, int64_t cap) {
+  if (!h || !n_docs) return fail(PMM_ERR_ARG, "null argument");
+  const int64_t nd = h->doc_offsets.empty() ? 0 : (int64_t)h->doc_offsets.size() - 1;
+  *n_docs = nd;
+  if (nd > 0 && doc_offsets_out && cap >= nd + 1)
+    std::copy(h->doc_offsets.begin(), h->doc_offsets.end(), doc_offsets_out);
+  return PMM_OK;
+}
+
+// Late-interaction search: candidate search's frame with the MaxSim scorer.
+// Every (row, listed document) pair is scored into the CSR key layout of the
+// lists, each row's segment sorted by the shared driver, cut at k and decoded.
+int pmm_topk_f32_maxsim(const pmm_corpus *h, const float *q_tokens, const int64_t *q_offsets, int64_t m,
+                        const int64_t *cand_offsets, const uint32_t *cand_docs, int64_t k, int metric,
+                        uint32_t *out_idx, float *out_score, uint32_t *out_len) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (m < 0) return fail(PMM_ERR_ARG, "negative size (m=%lld)", (long long)m);
+  if (k < 1) return fail(PMM_ERR_ARG, "k must be >= 1 (got %lld)", (long long)k);
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (metric == kMetricEuclidean)
+    return fail(PMM_ERR_ARG, "MaxSim takes cosine or dot: a maximum over euclidean distances is not a similarity");
+  if (h->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16", "int8", "bit"};
+    return fail(PMM_ERR_ARG, "MaxSim search takes an f32 multi-vector handle: this one holds %s rows", kRows[h->dtype]);
+  }
+  if (h->partitioned())
+    return fail(PMM_ERR_ARG, "MaxSim search takes a multi-vector handle (pmm_corpus_create_f32_docs): this one is "
+                             "partitioned (pmm_corpus_partition) and carries no documents; search its parent");
+  if (h->map)
+    return fail(PMM_ERR_ARG, "MaxSim search takes a multi-vector handle (pmm_corpus_create_f32_docs): this one is "
+                             "derived (pmm_corpus_subset_*) and carries no documents; search its parent");
+  if (h->doc_offsets.empty())
+    return fail(PMM_ERR_ARG, "MaxSim search takes a multi-vector handle: this one has no documents "
+                             "(pmm_corpus_create_f32_docs makes one)");
+  if (h->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED,
+                "a device-sharded corpus (%d shards) has no MaxSim search: use a handle of one shard",
+                (int)h->shards.size());
+  if (m > INT32_MAX) return fail(PMM_ERR_ARG, "size out of range (m=%lld)", (long long)m);
+  if (m == 0) return PMM_OK;
+  if (!q_offsets || !cand_offsets || !out_idx || !out_score || !out_len) return fail(PMM_ERR_ARG, "null argument");
+  const int64_t nd = (int64_t)h->doc_offsets.size() - 1, d = h->d, dp = h->dp;
+  if (q_offsets[0] != 0)
+    return fail(PMM_ERR_ARG, "q_offsets must start at 0 (q_offsets[0] = %lld)", (long long)q_offsets[0]);
+  if (cand_offsets[0] != 0)
+    return fail(PMM_ERR_ARG, "cand_offsets must start at 0 (cand_offsets[0] = %lld)", (long long)cand_offsets[0]);
+  for (int64_t i = 0; i < m; i++) {
+    if (q_offsets[i + 1] < q_offsets[i])
+      return fail(PMM_ERR_ARG, "q_offsets must not descend: q_offsets[%lld] = %lld follows %lld", (long long)(i + 1),
+                  (long long)q_offsets[i + 1], (long long)q_offsets[i]);
+    const int64_t c = cand_offsets[i + 1] - cand_offsets[i];
+    if (c < 0)
+      return fail(PMM_ERR_ARG, "cand_offsets must not descend: cand_offsets[%lld] = %lld follows %lld",
+                  (long long)(i + 1), (long long)cand_offsets[i + 1], (long long)cand_offsets[i]);
+    if (c > nd)
+      return fail(PMM_ERR_ARG, "row %lld lists %lld documents, the corpus has %lld: its ids cannot be strictly "
+                               "ascending", (long long)i, (long long)c, (long long)nd);
+  }
+  const int64_t tq = q_offsets[m], total = cand_offsets[m];
+  if (tq > INT32_MAX) return fail(PMM_ERR_ARG, "too many query tokens for one call (%lld): split the query rows", (long long)tq);
+  if ((tq > 0 && !q_tokens) || (total > 0 && !cand_docs)) return fail(PMM_ERR_ARG, "null argument");
+  if (m > (int64_t(1) << 40) / k)
+    return fail(PMM_ERR_ARG, "m * k out of range (m=%lld k=%lld): clip k to the longest list first", (long long)m,
+                (long long)k);
+  if (dp > kMaxsimMaxDp)
+    return fail(PMM_ERR_UNSUPPORTED, "MaxSim search serves a padded dimension up to %d (d = %lld pads to %lld)",
+                kMaxsimMaxDp, (long long)d, (long long)dp);
+  static_assert(kMaxsimMaxDp == PMM_MAXSIM_MAX_DP, "pmm.h states the kernel's limit");
+
+  // Host tables.  Units of the score pass: a row's documents kMaxsimRun at a
+  // time.  The sort plan (plan_pieces, cap = k) as candidate search's: a cut
+  // row's best min(k, count) keys are merged into a second key array behind
+  // the first, where its key source then points.
+  const int64_t smax = range_sort_max();
+  SortPlan plan;
+  plan_pieces(cand_offsets, m, smax, k, plan);
+  std::vector<CandUnit> units;
+  std::vector<int64_t> src(cand_offsets, cand_offsets + m);
+  size_t ci = 0;  // (plan.cut holds the cut rows' pieces in row order)
+  for (int64_t i = 0; i < m; i++) {
+    const int64_t c = cand_offsets[i + 1] - cand_offsets[i];
+    for (int64_t u = 0; u < c; u += kMaxsimRun) units.push_back(CandUnit{(uint32_t)i, (uint32_t)u});
+    if (c > smax) {
+      src[(size_t)i] = total + plan.cut[ci].dst;
+      ci += plan.cut[ci].T;
+    }
+  }
+  const int64_t npieces = (int64_t)plan.po.size() - 1;
+  if ((int64_t)units.size() > INT32_MAX || npieces > INT32_MAX)
+    return fail(PMM_ERR_ARG, "too many listed documents for one call (%lld): split the query rows", (long long)total);
+
+  const CorpusShard &x = h->shards[0];
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const hipStream_t s = f.s;
+  // arena: query tokens | their norms | flag | token bounds | list bounds | ids
+  // | units | piece bounds | piece list | cut pieces | key sources | keys,
+  // merged keys | the planes
+  Layout L;
+  const size_t off_q = L.take((size_t)tq * dp * 4);
+  const size_t off_qn = L.take((size_t)tq * 4);
+  const size_t off_flag = L.take(4);
+  const size_t off_qo = L.take((size_t)(m + 1) * 8);
+  const size_t off_offs = L.take((size_t)(m + 1) * 8);
+  const size_t off_ids = L.take((size_t)total * 4);
+  const size_t off_units = L.take(units.size() * sizeof(CandUnit));
+  const size_t off_po = L.take(plan.cut.empty() ? 0 : (size_t)(npieces + 1) * 8);
+  const size_t off_mid = L.take(plan.mid.size() * 4);
+  const size_t off_cut = L.take(plan.cut.size() * sizeof(CandPiece));
+  const size_t off_src = L.take((size_t)m * 8);
+  const size_t off_keys = L.take((size_t)(total + plan.merged) * 8);
+  const size_t off_oi = L.take((size_t)m * k * 4);
+  const size_t off_os = L.take((size_t)m * k * 4);
+  const size_t off_len = L.take((size_t)m * 4);
+  void *base;
+  if ((rc = arena(f.dev, s, L.off, &base))) return rc;
+  char *b = (char *)base;
+  const float *dq = (const float *)(b + off_q);
+  if ((rc = upload_padded(b + off_q, q_tokens, tq, d, dp, 4, s))) return rc;
+  // (from here on a failure waits for the stream: the copies read and write this frame's vectors)
+  unsigned flag = 0u;
+  rc = f.run([&]() -> int {
+    HIP_TRY(hipMemsetAsync(b + off_flag, 0, 4, s));
+    int64_t *d_offs = (int64_t *)(b + off_offs);
+    {
+      Timed t("h2d", s);
+      HIP_TRY(hipMemcpyAsync(b + off_qo, q_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d_offs, cand_offsets, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(b + off_src, src.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+      if (total > 0) {
+        HIP_TRY(hipMemcpyAsync(b + off_ids, cand_docs, (size_t)total * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b + off_units, units.data(), units.size() * sizeof(CandUnit), hipMemcpyHostToDevice,
+                               s));
+      }
+    }
+    float *qn = (float *)(b + off_qn);
+    if (metric == kMetricCosine && tq > 0) {
+      Timed t("norms_f32", s);
+      HIP_TRY(launch_norms_f32(dq, tq, d, dp, 0, qn, nullptr, s));
+    }
+    unsigned long long *keys = (unsigned long long *)(b + off_keys);
+    MaxsimScoreArgs sa{};
+    sa.q = dq;
+    sa.c = x.rows_as<float>();
+    sa.qn = qn;
+    sa.cn = shard_norms<float>(h, x, metric);
+    sa.q_offsets = (const int64_t *)(b + off_qo);
+    sa.doc_offsets = h->d_doc_offsets;
+    sa.offsets = d_offs;
+    sa.ids = (const uint32_t *)(b + off_ids);
+    sa.unit = (const CandUnit *)(b + off_units);
+    sa.units = (int)units.size();
+    sa.ldq = dp;
+    sa.ldc = dp;
+    sa.n_docs = (uint32_t)nd;
+    sa.dp = (int)dp;
+    sa.metric = metric;
+    sa.keys = keys;
+    sa.flag = (unsigned *)(b + off_flag);
+    {
+      Timed t("maxsim_score", s);
+      HIP_TRY(launch_maxsim_score(sa, s));
+    }
+    if (total > 0)
+      if (int rc2 = sort_segments(keys, d_offs, m, plan, (int64_t *)(b + off_po), (int *)(b + off_mid),
+                                  (CandPiece *)(b + off_cut), keys + total, s))
+        return rc2;
+    MaxsimDecodeArgs da{};
+    da.keys = keys;
+    da.src = (const int64_t *)(b + off_src);
+    da.offsets = d_offs;
+    da.q_offsets = sa.q_offsets;
+    da.m = (int)m;
+    da.k = k;
+    da.out_idx = (uint32_t *)(b + off_oi);
+    da.out_score = (float *)(b + off_os);
+    da.out_len = (uint32_t *)(b + off_len);
+    {
+      Timed t("maxsim_decode", s);
+      HIP_TRY(launch_maxsim_decode(da, s));
+    }
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_idx, da.out_idx, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_score, da.out_score, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(out_len, da.out_len, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&flag, sa.flag, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  });
+  if (rc) return rc;
+  if (flag & 2u) return fail(PMM_ERR_ARG, "a listed id is not a document of the corpus (n_docs=%lld)", (long long)nd);
+  if (flag & 1u)
+    return fail(PMM_ERR_ARG, "document ids must be strictly ascending within a row (a row repeats or descends)");
   return PMM_OK;
 }
 

@@ -239,6 +239,44 @@ struct CandDecodeArgs {
   uint32_t *out_len;               // [m]: min(k, candidates)
 };
 hipError_t launch_cand_decode(const CandDecodeArgs &a, hipStream_t s);
+// ---- late interaction: MaxSim over multi-vector documents (pmm_maxsim.hip) ----
+// One work unit of the score pass = one workgroup: query row `row` (all its
+// tokens, 32 at a time) against the documents at places [start, start +
+// kMaxsimRun) of its list (a CandUnit).  The kernel keeps a block of 32 query
+// tokens of dp + 4 floats and four waves' document tiles in LDS: the largest
+// padded dimension whose carve fits the CU's 160 KiB is kMaxsimMaxDp
+// (PMM_MAXSIM_MAX_DP in pmm.h).
+constexpr int kMaxsimRun = 64;
+constexpr int kMaxsimMaxDp = 960;
+struct MaxsimScoreArgs {
+  const float *q, *c;          // the query tokens (row stride ldq) and the handle's token rows (ldc), zero-padded to dp
+  const float *qn, *cn;        // cosine: the tokens' norms; dot: unused
+  const int64_t *q_offsets;    // m + 1 bounds of the rows' tokens in q (device)
+  const int64_t *doc_offsets;  // n_docs + 1 bounds of the documents' tokens in c (device), strictly ascending
+  const int64_t *offsets;      // m + 1 list bounds (device)
+  const uint32_t *ids;         // the lists: document numbers
+  const CandUnit *unit;        // device table, one entry per workgroup
+  int units;
+  int64_t ldq, ldc;
+  uint32_t n_docs;
+  int dp, metric;              // dp % 32 == 0, dp <= kMaxsimMaxDp; cosine or dot
+  unsigned long long *keys;    // [offsets[m]]: okey32(score) << 32 | ~document, laid out as the lists
+  unsigned *flag;              // |= 1: a list does not ascend strictly, |= 2: an id >= n_docs (zeroed by the caller)
+};
+size_t maxsim_lds_bytes(int dp);
+hipError_t launch_maxsim_score(const MaxsimScoreArgs &a, hipStream_t s);
+struct MaxsimDecodeArgs {
+  const unsigned long long *keys;  // sorted; row i's best keys start at keys[src[i]]
+  const int64_t *src;
+  const int64_t *offsets;          // m + 1 list bounds (device)
+  const int64_t *q_offsets;        // m + 1 token bounds (device): a row without tokens has length 0
+  int m;
+  int64_t k;
+  uint32_t *out_idx;               // [m][k], unused slots 0xFFFFFFFF
+  float *out_score;                // [m][k], unused slots +0.0
+  uint32_t *out_len;               // [m]
+};
+hipError_t launch_maxsim_decode(const MaxsimDecodeArgs &a, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, int loader, hipStream_t s);
 // Threshold seeding: gthr[row] = (k-th best composite of the row's ns
 // materialised scores S[row][0..ns)) - 1, one wave per row; ns <= kSeedMaxNs.

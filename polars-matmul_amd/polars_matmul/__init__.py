@@ -24,7 +24,11 @@ lists, on Float32 columns.  ``.pmm.within_self(threshold, metric)`` and
 ``.pmm.topk_self(k, metric)`` (extensions; ``within_self`` / ``topk_self`` and
 ``_within_self`` / ``_topk_self`` without Polars) search one column against
 itself -- every near-duplicate pair once, and the k-nearest-neighbour graph of
-its rows -- with the column's cached handle as its own query side.  The
+its rows -- with the column's cached handle as its own query side.
+``.pmm.topk_maxsim(docs, k, metric, candidates=)`` (an extension;
+``topk_maxsim`` / ``_topk_maxsim`` without Polars) is late-interaction search:
+both columns hold lists of token vectors and a pair scores MaxSim, the sum
+over the query's tokens of the best pair score in the document.  The
 numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
@@ -56,6 +60,7 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     _matmul,
     _topk,
     _topk_self,
+    _topk_maxsim,
     _within,
     _within_self,
     _sign_bits,
@@ -67,7 +72,7 @@ from polars_matmul._polars_matmul import (  # noqa: F401
 from polars_matmul import _native
 
 __version__ = "0.1.4"
-__all__ = ["PmmNamespace", "topk", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices",
+__all__ = ["PmmNamespace", "topk", "topk_maxsim", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices",
            "pack_sign", "topk_hamming"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
@@ -175,6 +180,28 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     if ids is not None:
         idx = ids[idx]
     return idx, sc.astype(np.float64, copy=False)
+
+
+def topk_maxsim(queries, docs, k: int, metric: Metric = "cosine", candidates=None):
+    """numpy-level late-interaction top-k (an extension): ``queries`` and
+    ``docs`` are pairs ``(tokens float32 [T, d], offsets [rows + 1])`` -- row i
+    holds the token vectors ``tokens[offsets[i]:offsets[i + 1]]`` (Arrow
+    columns of token lists work too).  Every query is searched among the
+    documents of its list (``candidates`` as in ``topk``; None: every
+    document, while rows x documents stays within 2^24) by MaxSim = the sum
+    over its tokens of the best cosine or dot pair score in the document.
+    Returns (indices uint32 [m, k'], scores float64 [m, k']), k' = min(k,
+    longest list); a shorter list ends in unused slots -- index 0xFFFFFFFF,
+    score NaN.  float32 only; euclidean raises ValueError."""
+    from polars_matmul._polars_matmul import _maxsim_search
+
+    r = _maxsim_search(queries, docs, k, metric, candidates, None)
+    if r is None:
+        return np.zeros((0, 0), dtype=np.uint32), np.zeros((0, 0), dtype=np.float64)
+    idx, sc, lens, kk = r
+    sc = sc.astype(np.float64)
+    sc[np.arange(kk)[None, :] >= lens[:, None].astype(np.int64)] = np.nan
+    return idx, sc
 
 
 def topk_hamming(queries_u8: np.ndarray, corpus_u8: np.ndarray, k: int):
@@ -463,6 +490,37 @@ if pl is not None:
             return self._expr.map_batches(
                 lambda s: _topk_self(s, k, metric),
                 is_elementwise=False,
+                return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def topk_maxsim(self, docs: "pl.Series", k: int, metric: Metric = "cosine",
+                        candidates: "pl.Expr | str | None" = None) -> "pl.Expr":
+            """Late-interaction top-k (an extension) of a column of token
+            lists -- List[Array[Float32, d]] -- against a documents column of
+            the same kind: List[Struct{index: u32, score: f64}], the documents
+            ranked by MaxSim (the sum over the row's tokens of the best cosine
+            or dot pair score in the document), exact f32.  candidates: an
+            expression or column name holding one List of document ids per
+            row, as in ``topk``; without it every row scores every document
+            (rows x documents up to 2^24)."""
+            if isinstance(docs, pl.Expr):
+                raise TypeError(
+                    "docs must be a Polars Series, not an Expression. "
+                    "Use docs['column_name'] or docs.get_column('column_name')."
+                )
+            if candidates is not None:
+                # the tokens and their list travel as one struct column, as topk's candidates= do
+                cand_expr = pl.col(candidates) if isinstance(candidates, str) else candidates
+                packed = pl.struct(self._expr.alias("tokens"), cand_expr.alias("candidates"))
+                return packed.map_batches(
+                    lambda s: _topk_maxsim(s.struct.field("tokens"), docs, k, metric,
+                                           candidates=s.struct.field("candidates")),
+                    is_elementwise=True,
+                    return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+                )
+            return self._expr.map_batches(
+                lambda s: _topk_maxsim(s, docs, k, metric),
+                is_elementwise=True,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
             )
 

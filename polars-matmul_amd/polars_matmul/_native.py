@@ -90,6 +90,9 @@ EXPORTED_SYMBOLS = (
     "pmm_topk_bf16_corpus",
     "pmm_range_f32_corpus",
     "pmm_topk_f32_candidates",
+    "pmm_corpus_create_f32_docs",
+    "pmm_corpus_docs",
+    "pmm_topk_f32_maxsim",
     "pmm_range_f32_self",
     "pmm_topk_f32_self",
     "pmm_range_self_plan",
@@ -214,6 +217,9 @@ _SIGS = {
     "pmm_range_f32_corpus": ([_vp, _vp, _i64, ctypes.c_float, _i32, _i64, _vp, _vp, _vp,
                               ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_candidates": ([_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
+    "pmm_corpus_create_f32_docs": ([_vp, _i64, _i64, _vp, _i64, _vp], _i32),
+    "pmm_corpus_docs": ([_vp, _vp, _vp, _i64], _i32),
+    "pmm_topk_f32_maxsim": ([_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_range_f32_self": ([_vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_self": ([_vp, _i64, _i32, _vp, _vp], _i32),
     "pmm_range_self_plan": ([_i64, _i32, _i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
@@ -801,6 +807,7 @@ class DeviceCorpus:
 
     is_bits = False  # a bit corpus (``bits`` / ``sign_bits``): ``d`` is the bytes of a row, ``topk`` takes no metric
     _mapped = False  # a derived handle: it holds a uint32 index map beside its rows
+    n_docs = 0       # a multi-vector handle (``multivector``): its documents; ``n`` stays the token rows
 
     def __init__(self, c: np.ndarray, compute: str = "f32"):
         self.compute = check_compute(compute)
@@ -832,6 +839,80 @@ class DeviceCorpus:
         h = ctypes.c_void_p()
         check(_lib.pmm_corpus_create_i8(ptr(c), c.shape[0], c.shape[1], ctypes.byref(h)))
         return cls._adopt(h, np.int8, c.shape[0], c.shape[1], corpus_device_bytes(c.shape[0], c.shape[1], np.int8))
+
+    @classmethod
+    def multivector(cls, tokens: np.ndarray, doc_offsets) -> "DeviceCorpus":
+        """A multi-vector corpus (pmm_corpus_create_f32_docs): the f32 handle
+        of the token rows -- every other method sees exactly that handle --
+        which also keeps the documents' bounds: document c is token rows
+        ``doc_offsets[c]:doc_offsets[c + 1]`` (from 0 to the token count,
+        strictly ascending: no empty document).  ``topk_maxsim`` searches it."""
+        tokens = np.asarray(tokens)
+        if tokens.dtype != np.float32 or tokens.ndim != 2:
+            raise TypeError(f"DeviceCorpus.multivector takes a 2-D float32 array, got {tokens.dtype} with shape "
+                            f"{tokens.shape}")
+        tokens = np.ascontiguousarray(tokens)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        if doc_offsets.size < 2:
+            raise ValueError("a multi-vector corpus needs at least one document (two offsets)")
+        h = ctypes.c_void_p()
+        check(_lib.pmm_corpus_create_f32_docs(ptr(tokens), tokens.shape[0], tokens.shape[1], ptr(doc_offsets),
+                                              doc_offsets.size - 1, ctypes.byref(h)))
+        self = cls._adopt(h, np.float32, tokens.shape[0], tokens.shape[1],
+                          corpus_device_bytes(tokens.shape[0], tokens.shape[1], np.float32) + 8 * doc_offsets.size)
+        self.n_docs = int(doc_offsets.size - 1)
+        return self
+
+    def doc_offsets(self) -> np.ndarray:
+        """The documents' bounds (pmm_corpus_docs): n_docs + 1 int64, or the
+        single offset [0] of a handle without documents."""
+        n = ctypes.c_int64(0)
+        self.acquire()
+        try:
+            check(_lib.pmm_corpus_docs(self._h, ctypes.byref(n), None, 0))
+            out = np.zeros(int(n.value) + 1, dtype=np.int64)
+            if n.value:
+                check(_lib.pmm_corpus_docs(self._h, ctypes.byref(n), ptr(out), out.size))
+        finally:
+            self.release()
+        return out
+
+    def topk_maxsim(self, q_tokens: np.ndarray, q_offsets, cand_offsets, cand_docs, k: int, metric: int):
+        """(idx uint32 (m, k), scores float32 (m, k), lens uint32 (m,)) of
+        pmm_topk_f32_maxsim: query row i holds the tokens
+        ``q_tokens[q_offsets[i]:q_offsets[i + 1]]`` and is searched among the
+        documents ``cand_docs[cand_offsets[i]:cand_offsets[i + 1]]`` (strictly
+        ascending document numbers of this multi-vector handle) by the MaxSim
+        score -- the sum over its tokens of the best pair score in the
+        document; its first ``lens[i]`` slots are the exact top-k there, the
+        rest hold index 0xFFFFFFFF and score 0.  Cosine or dot."""
+        q_tokens = np.ascontiguousarray(q_tokens, dtype=np.float32)
+        if q_tokens.ndim != 2 or q_tokens.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64).reshape(-1)
+        if q_offsets.size < 1:
+            raise ValueError("q_offsets needs m + 1 entries")
+        m = q_offsets.size - 1
+        if q_tokens.shape[0] < int(q_offsets[-1]):
+            raise ValueError(f"q_offsets end at {int(q_offsets[-1])}, the tokens hold {q_tokens.shape[0]} rows")
+        cand_offsets = np.ascontiguousarray(cand_offsets, dtype=np.int64)
+        if cand_offsets.shape != (m + 1,):
+            raise ValueError(f"one list per query row: {m} rows need {m + 1} offsets, got shape {cand_offsets.shape}")
+        cand_docs = np.ascontiguousarray(cand_docs, dtype=np.uint32).reshape(-1)
+        if cand_docs.size < int(cand_offsets[-1]):
+            raise ValueError(f"the offsets end at {int(cand_offsets[-1])}, the ids hold {cand_docs.size}")
+        k = int(k)
+        idx = np.empty((m, max(k, 0)), dtype=np.uint32)
+        sc = np.empty((m, max(k, 0)), dtype=np.float32)
+        lens = np.empty(m, dtype=np.uint32)
+        self.acquire()
+        try:
+            check(_lib.pmm_topk_f32_maxsim(self._h, ptr(q_tokens) if q_tokens.size else None, ptr(q_offsets), m,
+                                           ptr(cand_offsets), ptr(cand_docs) if cand_docs.size else None, k, metric,
+                                           ptr(idx), ptr(sc), ptr(lens)))
+        finally:
+            self.release()
+        return idx, sc, lens
 
     @classmethod
     def _adopt(cls, h, dtype, n: int, d: int, nbytes0: int) -> "DeviceCorpus":

@@ -271,15 +271,19 @@ def _persistent_key(original, arrow):
     return _arrow_key(arrow)
 
 
-def _handle_bytes(c: np.ndarray, compute: str) -> int:
+def _handle_bytes(c: np.ndarray, compute: str, doc_offsets=None) -> int:
     """HBM the cached handle of c holds; compute "bits" (the key mode of
-    ``_topk_hamming``, not a ``compute=`` value): c is packed bit rows."""
+    ``_topk_hamming``, not a ``compute=`` value): c is packed bit rows;
+    compute "maxsim" (the key mode of ``_topk_maxsim``): c is the token rows
+    of a multi-vector column and ``doc_offsets`` its documents' bounds."""
     if compute == "bits":
         return _native.bits_device_bytes(c.shape[0], c.shape[1])
+    if compute == "maxsim":
+        return _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, "f32") + 8 * int(doc_offsets.size)
     return _native.corpus_device_bytes(c.shape[0], c.shape[1], c.dtype, compute)
 
 
-def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = False):
+def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = False, doc_offsets=None):
     """The cache key of this corpus, or None when it is not cacheable.
     numpy_ok (the numpy-level ``within``): a numpy matrix that is searched as
     it is (C-contiguous, already of the compute dtype) is keyed by its address
@@ -294,19 +298,20 @@ def _corpus_key(original, rv, c: np.ndarray, compute: str, numpy_ok: bool = Fals
         # a handle is sharded over the device list of its creation; an f32
         # and a bf16 handle of one column are two entries
         key = key + (c.dtype.str, tuple(_native.get_devices()), compute)
-    dev_bytes = _handle_bytes(c, compute)
+    dev_bytes = _handle_bytes(c, compute, doc_offsets)
     if not _CACHE_ON or key is None or c.nbytes < _CACHE_MIN_BYTES or dev_bytes > _CACHE_BYTES:
         return None
     return key
 
 
-def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: bool = False):
+def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: bool = False, doc_offsets=None):
     """An ACQUIRED DeviceCorpus for this corpus (the caller releases it), or
-    None when the corpus is not cacheable."""
-    key = _corpus_key(original, rv, c, compute, numpy_ok)
+    None when the corpus is not cacheable.  compute "maxsim": the multi-vector
+    handle of the token rows c and their documents' bounds ``doc_offsets``."""
+    key = _corpus_key(original, rv, c, compute, numpy_ok, doc_offsets)
     if key is None:
         return None
-    dev_bytes = _handle_bytes(c, compute)
+    dev_bytes = _handle_bytes(c, compute, doc_offsets)
     with _cache_lock:
         hit = _cache.get(key)
         if hit is not None:
@@ -315,6 +320,7 @@ def _cached_corpus(original, rv, c: np.ndarray, compute: str = "f32", numpy_ok: 
         if not _fits_device(dev_bytes):
             return None
         dc = (_native.DeviceCorpus.bits(c) if compute == "bits" else
+              _native.DeviceCorpus.multivector(c, doc_offsets) if compute == "maxsim" else
               _native.DeviceCorpus.int8(c) if c.dtype == np.int8 and compute == "f32" else
               _native.DeviceCorpus(c) if compute == "f32" else _native.DeviceCorpus(c, compute=compute))
         _cache[key] = (rv, dc)
@@ -988,6 +994,201 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None, candi
         t = _lap("device", t)
         sc = sc.astype(np.float64, copy=False)  # src/matmul.rs:447 (f32 -> f64)
     out = _wrap(_topk_arrow(idx, sc, m, kk), "topk", polars_out)
+    _lap("assemble", t)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Late interaction (an extension; no reference counterpart): a row of either
+# column is a LIST of token vectors, and the score of a (query, document) pair
+# is MaxSim -- the sum over the query's tokens of the best pair score in the
+# document (DeviceCorpus.topk_maxsim).  The documents column is cached as a
+# multi-vector handle like any corpus; the lists go through ``candidates=``'s
+# normaliser as they are.
+# ---------------------------------------------------------------------------
+_MAXSIM_SYNTH_MAX = 1 << 24  # candidates=None: the full lists are written out up to m * n_docs of this
+
+
+def _maxsim_f32_only(what: str) -> TypeError:
+    return TypeError(
+        f"MaxSim search runs on Float32 token columns ({what}); cast the tokens first, e.g. "
+        "pl.col('tokens').cast(pl.List(pl.Array(pl.Float32, d))) or array.astype(numpy.float32)"
+    )
+
+
+def _maxsim_metric(metric) -> int:
+    """The metric id, without the library: cosine or dot."""
+    if not isinstance(metric, str):
+        raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
+    name = metric.lower()
+    if name in ("euclidean", "l2"):
+        raise ValueError("MaxSim takes metric 'cosine' or 'dot': a maximum over euclidean distances is not a similarity")
+    if name == "cosine":
+        return _native.METRIC_COSINE
+    if name == "dot":
+        return _native.METRIC_DOT
+    raise ValueError(f"Unknown metric: {metric}. Use 'cosine' or 'dot'")
+
+
+def _token_lists(obj, what: str, docs: bool):
+    """(tokens float32 [T, d], offsets int64 [rows + 1], arrow array or None)
+    of a multi-vector column: a pair ``(tokens, offsets)`` of numpy arrays, or
+    a Series / Arrow List whose rows are Array[Float32, d] or List[Float32]
+    lists of one width.  A null query row has no tokens; a null or empty
+    document raises ValueError (docs=True)."""
+    if isinstance(obj, (tuple, list)) and len(obj) == 2 and all(isinstance(x, np.ndarray) for x in obj):
+        tokens, offsets = obj
+        if tokens.ndim != 2:
+            raise TypeError(f"{what}: expected a 2-D array of token vectors, got shape {tokens.shape}")
+        if tokens.dtype != np.float32:
+            raise _maxsim_f32_only(f"{what} hold {tokens.dtype} tokens")
+        if offsets.dtype.kind not in "iu" or offsets.ndim != 1 or offsets.size < 1:
+            raise TypeError(f"{what}: the offsets must be a 1-D integer array of rows + 1 entries")
+        offsets = offsets.astype(np.int64)
+        if offsets[0] != 0 or np.any(np.diff(offsets) < 0) or offsets[-1] != tokens.shape[0]:
+            raise ValueError(f"{what}: the offsets must start at 0, not descend and end at len(tokens)")
+        arr = None
+    else:
+        arr = obj
+        if _is_polars_series(arr):
+            arr = arr.rechunk().to_arrow()
+        if isinstance(arr, pa.ChunkedArray):
+            arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
+        if not isinstance(arr, pa.Array):
+            raise TypeError(f"{what} must be a Series or Arrow List of token vectors, or a pair (tokens, offsets) of "
+                            f"numpy arrays, got {type(obj).__name__}")
+        t = arr.type
+        outer = pa.types.is_list(t) or pa.types.is_large_list(t)
+        it = t.value_type if outer else None
+        inner = outer and (pa.types.is_list(it) or pa.types.is_large_list(it) or pa.types.is_fixed_size_list(it))
+        if not inner:
+            raise TypeError(f"{what} must be a List of Array[Float32, d] or List[Float32] token vectors, got {t}")
+        if it.value_type != pa.float32():
+            raise _maxsim_f32_only(f"{what} hold {it.value_type} tokens")
+        n = len(arr)
+        raw = np.asarray(arr.offsets.to_numpy(zero_copy_only=False), dtype=np.int64)
+        lens = np.diff(raw)
+        if arr.null_count:
+            valid = np.asarray(arr.is_valid().to_numpy(zero_copy_only=False), dtype=bool)
+            if docs:
+                raise ValueError(f"{what}: document {int(np.argmin(valid))} is null")
+            lens = np.where(valid, lens, 0)
+        lo, hi = (int(raw[0]), int(raw[-1])) if n else (0, 0)
+        child = arr.values.slice(lo, hi - lo)  # the token vectors
+        if pa.types.is_fixed_size_list(it):
+            d = it.list_size
+            vals = _values_numpy(child.values.slice(child.offset * d, len(child) * d), np.float32)
+        else:
+            craw = np.asarray(child.offsets.to_numpy(zero_copy_only=False), dtype=np.int64)
+            widths = np.diff(craw)
+            if child.null_count:
+                raise ValueError(f"{what}: a token vector is null")
+            d = int(widths[0]) if widths.size else 0
+            if widths.size and np.any(widths != d):
+                bad = int(np.argmax(widths != d))
+                raise ValueError(f"{what}: token {bad} has width {int(widths[bad])}, the first token has {d}: "
+                                 "every token vector must have one width")
+            vals = _values_numpy(child.values.slice(int(craw[0]), int(craw[-1] - craw[0])), np.float32) if widths.size \
+                else np.zeros(0, dtype=np.float32)
+        tokens = np.ascontiguousarray(vals.reshape(len(child), d)) if d else np.zeros((0, 0), dtype=np.float32)
+        if int(lens.sum()) != len(child):  # null rows with an extent: the valid rows' tokens
+            pos = np.repeat(raw[:-1] - lo, lens) + (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens))
+            tokens = np.ascontiguousarray(tokens[pos])
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+    if docs:
+        lens = np.diff(offsets)
+        if lens.size and np.any(lens == 0):
+            raise ValueError(f"{what}: document {int(np.argmax(lens == 0))} is empty (a document needs a token)")
+    return tokens, offsets, arr
+
+
+def _maxsim_device(qt, qo, dt, do, original, rv, cand: _Candidates, kk: int, metric_id: int):
+    """(idx (m, kk), scores f32 (m, kk), lens (m,)), indices numbering the
+    documents.  On the cached multi-vector handle of the documents column when
+    it is cacheable and fits; else on a handle made for the call from the
+    documents some list names (their sorted union), the lists renumbered into
+    it and the result mapped back -- one search either way."""
+    dc = _cached_corpus(original, rv, dt, "maxsim", doc_offsets=do) if rv is not None else None
+    if dc is not None:
+        try:
+            out = dc.topk_maxsim(qt, qo, cand.offsets, cand.ids, kk, metric_id)
+            _reaccount_cache(dc)
+        finally:
+            dc.release()
+        return out
+    U, local = _candidates_union(cand)
+    lens = (do[1:] - do[:-1])[U]
+    uo = np.zeros(U.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=uo[1:])
+    rows = np.repeat(do[:-1][U], lens) + (np.arange(int(uo[-1])) - np.repeat(uo[:-1], lens))
+    tmp = _native.DeviceCorpus.multivector(np.ascontiguousarray(dt[rows]), uo)
+    tmp.acquire()
+    try:
+        idx, sc, ln = tmp.topk_maxsim(qt, qo, cand.offsets, local, kk, metric_id)
+    finally:
+        tmp.release()
+        tmp.close()
+    used = idx != 0xFFFFFFFF
+    idx[used] = U[idx[used]]
+    return idx, sc, ln
+
+
+def _maxsim_search(left, right, k, metric, candidates, compute):
+    """The checks (all before any library call) and the search behind
+    ``_topk_maxsim`` and ``polars_matmul.topk_maxsim``: (idx, f32 scores, lens,
+    kk), or None for a query column without rows."""
+    k = _as_usize(k)
+    if compute is not None and compute != "f32":
+        raise _maxsim_f32_only(f"compute={compute!r} has no MaxSim search")
+    metric_id = _maxsim_metric(metric)
+    qt, qo, _ = _token_lists(left, "the queries", False)
+    dt, do, rv = _token_lists(right, "the documents", True)
+    m, nd = qo.size - 1, do.size - 1
+    if candidates is not None:
+        cand = _check_candidates(candidates, m, nd)
+    else:
+        if m * nd > _MAXSIM_SYNTH_MAX:
+            raise ValueError(f"candidates=None scores every document for every row: {m} rows x {nd} documents is more "
+                             f"than {_MAXSIM_SYNTH_MAX} pairs; give candidates= (a first stage's hits per row)")
+        cand = _Candidates(np.arange(m + 1, dtype=np.int64) * nd, np.tile(np.arange(nd, dtype=np.uint32), m))
+    if m == 0:
+        return None
+    if nd == 0:
+        raise _compute_error("Empty series")
+    if qt.shape[0] and qt.shape[1] != dt.shape[1]:
+        raise _dim_mismatch(qt.shape[1], dt.shape[1])
+    if qt.shape[0] == 0:
+        qt = np.zeros((0, dt.shape[1]), dtype=np.float32)
+    kk = min(k, cand.maxlen)  # the clip-to-n rule on the longest list
+    if kk == 0:
+        return (np.zeros((m, 0), dtype=np.uint32), np.zeros((m, 0), dtype=np.float32), np.zeros(m, dtype=np.uint32), 0)
+    _apply_devices_env()
+    idx, sc, lens = _maxsim_device(qt, qo, dt, do, right, rv, cand, kk, metric_id)
+    return idx, sc, lens, kk
+
+
+def _topk_maxsim(left, right, k, metric="cosine", candidates=None, compute=None):
+    """Late-interaction top-k (an extension): ``left`` and ``right`` are
+    columns of token lists -- List[Array[Float32, d]] or List[List[Float32]]
+    of one width (Series or Arrow), or pairs ``(tokens [T, d], offsets)`` of
+    numpy arrays.  Row i of the result ranks the documents of its list
+    (``candidates``, as ``_topk``'s: sorted and de-duplicated here; None means
+    every document, while rows x documents stays within 2^24) by MaxSim(Q, D) =
+    sum over the query's tokens of the max over the document's tokens of the
+    cosine or dot pair score, exact f32: List[Struct{index: u32, score: f64}],
+    ragged, min(k, listed documents) long; a query without tokens has an empty
+    list.  Float32 only (Float64, Int8 and compute= raise TypeError); euclidean
+    raises ValueError, as do a null or empty document and token vectors of
+    more than one width -- all before any library call."""
+    polars_out = _is_polars_series(left)
+    t = time.perf_counter()
+    r = _maxsim_search(left, right, k, metric, candidates, compute)
+    if r is None:
+        return _wrap(pa.array([], type=pa.large_list(_TOPK_STRUCT)), "topk_maxsim", polars_out)
+    idx, sc, lens, _ = r
+    t = _lap("device", t)
+    out = _wrap(_ragged_topk_arrow(idx, sc, lens), "topk_maxsim", polars_out)
     _lap("assemble", t)
     return out
 
