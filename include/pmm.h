@@ -874,6 +874,57 @@ int pmm_range_f32_self(const pmm_corpus *corpus, float threshold, int metric, in
 int pmm_topk_f32_self(const pmm_corpus *corpus, int64_t k, int metric, uint32_t *out_idx /* n * k */,
                       float *out_score /* n * k */);
 
+/* k-means (Lloyd's iteration) on the rows of an f32 handle.  No reference
+ * counterpart.  The handle's n resident rows X are clustered around K
+ * centroids, from the K initial centroids `init` (K * d floats):
+ *
+ *   C = init; updates = 0; converged = 0
+ *   loop:
+ *     L, S = assign(X, C)
+ *     if updates > 0 and L == L_prev: converged = 1; break
+ *     if updates == max_iter: break
+ *     C = update(X, L, C); L_prev = L; updates += 1
+ *
+ * so the labels and scores returned are always the assignment against the
+ * centroids returned, and max_iter = 0 is a pure assignment against init.
+ *   assign.  L[i], S[i]: the exact f32 top-1 of row i among the K rows of C --
+ * the bits pmm_topk_f32 (rows as queries, C as the corpus, k = 1) returns:
+ * ties to the lower centroid, euclidean lower is better, the centroids' norms
+ * from the norm kernel of every corpus.  A row whose best score is NaN gets
+ * L[i] = PMM_NO_GROUP (what pmm_partition_plan reads as "dropped") and S[i] =
+ * the quiet NaN 0x7FC00000.
+ *   update.  Cluster c's members are the rows with label c in ascending row
+ * order, cut into pieces of PMM_KMEANS_PIECE consecutive members (the last one
+ * shorter).  Per column, each piece is summed in f64 sequentially from +0.0 in
+ * member order; the piece sums are added sequentially in piece order from
+ * +0.0; C[c][j] = (float)(sum / (double)count).  Euclidean: the term of row i
+ * is (double)x[i][j], count the members.  Cosine (spherical k-means): the
+ * term is (double)x[i][j] / (double)norm[i] with the handle's cached cosine
+ * norm; a member with norm[i] <= 1e-6f (the reference's zero-norm rule) keeps
+ * its place in its piece, adds no term and is not counted.  A cluster whose
+ * count is 0 keeps its centroid's bits.  Rows labelled PMM_NO_GROUP belong to
+ * no cluster.  The fixed two-level order makes the result independent of the
+ * launch geometry.
+ * Outputs: out_centroids (K * d), out_labels (n), out_score (n, may be NULL),
+ * *out_updates (the updates performed, <= max_iter), *out_converged.
+ * It serves an f32 handle of one shard -- plain, multi-vector (its tokens are
+ * clustered) or derived by pmm_corpus_subset_* (the labels are numbered by the
+ * handle's own rows).  A partitioned, f64, bf16, int8 or bit handle:
+ * PMM_ERR_ARG; a sharded handle: PMM_ERR_UNSUPPORTED.  A null argument, K < 1,
+ * K > n, K >= 2^32, a negative max_iter, dot (a mean does not maximise a dot
+ * product) or a bad metric: PMM_ERR_ARG before any device call.  Each
+ * iteration is the assignment (the fused f32 top-k), one launch that writes
+ * labels, scores and a changed flag, a stable radix sort of the row numbers by
+ * label on the device, and the gather-sum; the labels never visit the host
+ * between iterations.  Thread-safe like the other handle entries; waits once
+ * per iteration (the flag's read-back) and once at the end. */
+#define PMM_KMEANS_PIECE 256
+int pmm_kmeans_f32_corpus(const pmm_corpus *corpus, int64_t K, const float *init /* K * d */,
+                          int metric, int64_t max_iter,
+                          float *out_centroids /* K * d */, uint32_t *out_labels /* n */,
+                          float *out_score /* n, may be NULL */,
+                          int64_t *out_updates, int *out_converged);
+
 /* The triangular schedule of pmm_range_f32_self's emit pass for n rows on a
  * device of `cus` compute units (host only, no device is touched).
  * variant_in: 0 (128 x 128 tiles) or 3 (256 x 256), or -1 to choose as the

@@ -5111,6 +5111,152 @@ int pmm_topk_f32_maxsim(const pmm_corpus *h, const float *q_tokens, const int64_
   return PMM_OK;
 }
 
+// ---- k-means (DESIGN.md §4d "k-means") ----
+
+// Lloyd's iteration on the handle's resident rows: the assignment is the f32
+// executor's top-1 with the rows as the queries and the centroids as the
+// corpus, the update the ordered f64 gather-sum of pmm_kmeans.hip.  One arena
+// for the whole call; one read-back of the changed flag per iteration.
+int pmm_kmeans_f32_corpus(const pmm_corpus *h, int64_t K, const float *init, int metric, int64_t max_iter,
+                          float *out_centroids, uint32_t *out_labels, float *out_score, int64_t *out_updates,
+                          int *out_converged) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!init || !out_centroids || !out_labels || !out_updates || !out_converged)
+    return fail(PMM_ERR_ARG, "null argument");
+  if (K < 1) return fail(PMM_ERR_ARG, "k-means needs a cluster: K must be >= 1 (got %lld)", (long long)K);
+  if (K >= (int64_t(1) << 32)) return fail(PMM_ERR_ARG, "K out of range (%lld): labels are 32 bits wide", (long long)K);
+  if (max_iter < 0) return fail(PMM_ERR_ARG, "max_iter must be >= 0 (got %lld)", (long long)max_iter);
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (metric == kMetricDot)
+    return fail(PMM_ERR_ARG, "k-means takes euclidean or cosine: a mean does not maximise a dot product");
+  if (h->partitioned())
+    return fail(PMM_ERR_ARG, "k-means takes a plain f32 handle: this one is partitioned (pmm_corpus_partition); "
+                             "cluster its parent");
+  if (h->dtype != PMM_DTYPE_F32) {
+    static const char *const kRows[] = {"f32", "f64", "bf16", "int8", "bit"};
+    return fail(PMM_ERR_ARG, "k-means takes an f32 handle: this one holds %s rows", kRows[h->dtype]);
+  }
+  if (h->shards.size() != 1)
+    return fail(PMM_ERR_UNSUPPORTED, "a device-sharded corpus (%d shards) has no k-means: use a handle of one shard",
+                (int)h->shards.size());
+  const int64_t n = h->n, d = h->d, dp = h->dp;
+  if (K > n) return fail(PMM_ERR_ARG, "K (%lld) must be <= n (%lld): more clusters than rows", (long long)K, (long long)n);
+  if ((rc = validate_sizes(n, K, d, 1, true))) return rc;
+  static_assert(kKmeansPiece == PMM_KMEANS_PIECE, "pmm.h states the piece length");
+  const int64_t maxp = kmeans_max_pieces(n, K), units = kmeans_sort_units(n);
+  if (maxp * cdiv(dp, 256) > (int64_t)INT32_MAX * 4 || K * cdiv(dp, 256) > INT32_MAX)
+    return fail(PMM_ERR_UNSUPPORTED, "too many clusters for one k-means call (K=%lld at d=%lld)", (long long)K,
+                (long long)d);
+
+  const CorpusShard &x = h->shards[0];
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const hipStream_t s = f.s;
+  const TopkRoute route = route_topk(n, K, d, 1, metric, PMM_COMPUTE_F32, f.cus, false, false);
+  // arena: centroids | their norms and pre-filter factors | top-1 lists | labels
+  // | scores | flag | sort keys and rows (two each) | histograms | their scan |
+  // bounds | piece bases | piece sums | piece counts | the route's workspace
+  Layout L;
+  const size_t off_c = L.take((size_t)K * dp * 4);
+  const size_t off_cn = L.take((size_t)K * 2 * 4);
+  const size_t off_oi = L.take((size_t)n * 4), off_os = L.take((size_t)n * 4);
+  const size_t off_lab = L.take((size_t)n * 4), off_sc = L.take((size_t)n * 4);
+  const size_t off_flag = L.take(4);
+  size_t off_key[2], off_val[2];
+  for (int j = 0; j < 2; j++) off_key[j] = L.take((size_t)n * 4), off_val[j] = L.take((size_t)n * 4);
+  const size_t off_hist = L.take((size_t)units * 256 * 4), off_base = L.take((size_t)units * 256 * 4);
+  const size_t off_bounds = L.take((size_t)(K + 1) * 4), off_pbase = L.take((size_t)(K + 1) * 4);
+  const size_t off_psum = L.take((size_t)maxp * dp * 8), off_pcount = L.take((size_t)maxp * 4);
+  void *base;
+  if ((rc = arena(f.dev, s, L.off + route.total, &base))) return rc;
+  char *b = (char *)base;
+  float *C = (float *)(b + off_c), *cnrm = (float *)(b + off_cn);
+  if ((rc = upload_padded(C, init, K, d, dp, 4, s))) return rc;
+  uint32_t *oi = (uint32_t *)(b + off_oi), *labels = (uint32_t *)(b + off_lab);
+  float *os = (float *)(b + off_os), *scores = (float *)(b + off_sc);
+  unsigned *flag = (unsigned *)(b + off_flag);
+  KmeansOrder oa{};
+  oa.labels = labels;
+  oa.n = n;
+  oa.K = (uint32_t)K;
+  for (int j = 0; j < 2; j++) oa.key[j] = (uint32_t *)(b + off_key[j]), oa.val[j] = (uint32_t *)(b + off_val[j]);
+  oa.hist = (uint32_t *)(b + off_hist);
+  oa.base = (uint32_t *)(b + off_base);
+  oa.bounds = (uint32_t *)(b + off_bounds);
+  oa.pbase = (uint32_t *)(b + off_pbase);
+  KmeansUpdateArgs ua{};
+  ua.x = x.rows_as<float>();
+  ua.ldx = dp;
+  ua.cn = metric == kMetricCosine ? shard_norms<float>(h, x, kMetricCosine) : nullptr;
+  ua.rows = kmeans_sorted_rows(oa);
+  ua.bounds = oa.bounds;
+  ua.pbase = oa.pbase;
+  ua.K = (uint32_t)K;
+  ua.d = (int)d;
+  ua.dp = (int)dp;
+  ua.max_pieces = maxp;
+  ua.psum = (double *)(b + off_psum);
+  ua.pcount = (uint32_t *)(b + off_pcount);
+  ua.C = C;
+  int64_t updates = 0;
+  bool converged = false;
+  // (a failure waits for the stream: the read-back writes this frame's flag)
+  rc = f.run([&]() -> int {
+    for (;;) {
+      {
+        // the centroids' norms and pre-filter factors, by the kernel that made the handle's
+        Timed t("norms_f32", s);
+        HIP_TRY(launch_norms_f32(C, K, d, dp, metric == kMetricEuclidean, cnrm, cnrm + K, s));
+      }
+      if (int rc2 = topk_f32_device_impl(route, x.rows_as<float>(), dp, n, C, dp, K, d, 1, metric, 0u, oi, os,
+                                         b + L.off, route.total, s, f.dev, cnrm))
+        return rc2;
+      HIP_TRY(hipMemsetAsync(flag, 0, 4, s));
+      {
+        Timed t("kmeans_labels", s);
+        HIP_TRY(launch_kmeans_labels(oi, os, n, (uint32_t)K, labels, scores, updates > 0, flag, s));
+      }
+      if (updates > 0) {
+        // the iteration's one read-back and wait
+        unsigned changed = 0u;
+        HIP_TRY(hipMemcpyAsync(&changed, flag, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!changed) {
+          converged = true;
+          break;
+        }
+      }
+      if (updates == max_iter) break;
+      {
+        Timed t("kmeans_order", s);
+        HIP_TRY(launch_kmeans_order(oa, s));
+      }
+      {
+        Timed t("kmeans_update", s);
+        HIP_TRY(launch_kmeans_update(ua, s));
+      }
+      {
+        Timed t("kmeans_finish", s);
+        HIP_TRY(launch_kmeans_finish(ua, s));
+      }
+      updates++;
+    }
+    Timed t("d2h", s);
+    HIP_TRY(hipMemcpy2DAsync(out_centroids, (size_t)d * 4, C, (size_t)dp * 4, (size_t)d * 4, (size_t)K,
+                             hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_labels, labels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (out_score) HIP_TRY(hipMemcpyAsync(out_score, scores, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    return PMM_OK;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  *out_updates = updates;
+  *out_converged = converged ? 1 : 0;
+  return PMM_OK;
+}
+
 int pmm_screen_prepare_device(const float *a, int64_t ld, int64_t rows, int64_t d, uint16_t *out, int64_t ldo,
                               float *norm, float *inv_norm, float *rel, uint32_t *unsafe, uint32_t *scalars,
                               void *stream) {

@@ -277,6 +277,48 @@ struct MaxsimDecodeArgs {
   uint32_t *out_len;               // [m]
 };
 hipError_t launch_maxsim_decode(const MaxsimDecodeArgs &a, hipStream_t s);
+// ---- k-means on a resident f32 handle (pmm_kmeans.hip) ----
+// The update sums a cluster's members (ascending rows) in pieces of
+// kKmeansPiece consecutive members: each piece sequentially in f64 from +0.0,
+// then the pieces in order from +0.0 (PMM_KMEANS_PIECE in pmm.h).  This
+// constant is the one place the piece length is set.
+constexpr int kKmeansPiece = 256;
+// The ordering pass sorts runs of this many rows per wave.
+constexpr int kKmeansSortRows = 1024;
+// labels[i] = oi[i] and scores[i] = os[i] of the [n][1] top-1 lists; a NaN
+// score gives the label 0xFFFFFFFF and the canonical NaN.  have_prev: *changed
+// = 1 when a label differs from the one `labels` held (zeroed by the caller).
+hipError_t launch_kmeans_labels(const uint32_t *oi, const float *os, int64_t n, uint32_t K, uint32_t *labels,
+                                float *scores, bool have_prev, unsigned *changed, hipStream_t s);
+struct KmeansOrder {
+  const uint32_t *labels;      // [n]: a cluster below K or 0xFFFFFFFF
+  int64_t n;
+  uint32_t K;
+  uint32_t *key[2], *val[2];   // [n] each: the sort's two key and row buffers
+  uint32_t *hist, *base;       // [256 * kmeans_sort_units(n)] each
+  uint32_t *bounds;            // [K + 1]: cluster c's members are sorted rows [bounds[c], bounds[c + 1])
+  uint32_t *pbase;             // [K + 1]: cluster c's pieces are [pbase[c], pbase[c + 1])
+};
+int64_t kmeans_sort_units(int64_t n);
+int kmeans_sort_passes(uint32_t K);                 // 8-bit digits of the keys 0 .. K
+int64_t kmeans_max_pieces(int64_t n, int64_t K);    // an upper bound of pbase[K]
+// the rows by (label, row), the rows of no cluster last; then bounds and pbase
+hipError_t launch_kmeans_order(const KmeansOrder &a, hipStream_t s);
+const uint32_t *kmeans_sorted_rows(const KmeansOrder &a);  // the buffer the last pass wrote
+struct KmeansUpdateArgs {
+  const float *x;              // the handle's rows (row stride ldx), zero-padded to dp
+  int64_t ldx;
+  const float *cn;             // cosine: the rows' norms (term x / norm, a norm <= 1e-6f adds none); euclidean: null
+  const uint32_t *rows, *bounds, *pbase;  // launch_kmeans_order's
+  uint32_t K;
+  int d, dp;                   // dp % 32 == 0
+  int64_t max_pieces;          // kmeans_max_pieces(n, K): the rows of psum and pcount
+  double *psum;                // [max_pieces][dp] piece sums
+  uint32_t *pcount;            // [max_pieces] members that added a term
+  float *C;                    // [K][dp] centroids, updated in place
+};
+hipError_t launch_kmeans_update(const KmeansUpdateArgs &a, hipStream_t s);  // -> psum, pcount
+hipError_t launch_kmeans_finish(const KmeansUpdateArgs &a, hipStream_t s);  // psum, pcount -> C
 hipError_t launch_merge(const MergeArgs &a, int loader, hipStream_t s);
 // Threshold seeding: gthr[row] = (k-th best composite of the row's ns
 // materialised scores S[row][0..ns)) - 1, one wave per row; ns <= kSeedMaxNs.

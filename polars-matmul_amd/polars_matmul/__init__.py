@@ -28,7 +28,11 @@ its rows -- with the column's cached handle as its own query side.
 ``.pmm.topk_maxsim(docs, k, metric, candidates=)`` (an extension;
 ``topk_maxsim`` / ``_topk_maxsim`` without Polars) is late-interaction search:
 both columns hold lists of token vectors and a pair scores MaxSim, the sum
-over the query's tokens of the best pair score in the document.  The
+over the query's tokens of the best pair score in the document.
+``.pmm.kmeans(n_clusters, metric, max_iter, init=, seed=)`` (an extension;
+``kmeans`` / ``_kmeans`` without Polars) clusters one Float32 column on its
+cached handle -- Lloyd's iteration, euclidean or spherical -- into the labels
+that ``corpus_by=`` takes and the centroids that ``.pmm.topk`` probes.  The
 numerics run on MI355X through hand-written HIP
 kernels (``libpmm.so``, C ABI in ``include/pmm.h``); there is no CPU path.
 
@@ -57,6 +61,8 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     PanicException,
     _check_groups,
     _check_subset,
+    _kmeans,
+    _kmeans_labels,
     _matmul,
     _topk,
     _topk_self,
@@ -73,7 +79,7 @@ from polars_matmul import _native
 
 __version__ = "0.1.4"
 __all__ = ["PmmNamespace", "topk", "topk_maxsim", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices",
-           "pack_sign", "topk_hamming"]
+           "pack_sign", "topk_hamming", "kmeans"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
 Compute = Literal["f32", "bf16"]
@@ -334,6 +340,34 @@ def topk_self(corpus: np.ndarray, k: int, metric: Metric = "cosine", compute: Co
     return idx, sc.astype(np.float64)
 
 
+def kmeans(x: np.ndarray, n_clusters: int, metric: Metric = "euclidean", max_iter: int = 25, init=None, seed: int = 0,
+           compute=None):
+    """numpy-level k-means (an extension) of the rows of one float32 matrix:
+    Lloyd's iteration on the GPU from ``init`` -- a [n_clusters, d] matrix, an
+    array of n_clusters distinct row ids, or None for the rows
+    ``np.sort(np.random.RandomState(seed).choice(n, n_clusters, replace=False))``
+    -- for at most ``max_iter`` updates, stopped once an assignment repeats the
+    previous labels.  Returns (centroids float32 [K, d], labels uint32 [n],
+    scores float32 [n], updates, converged): labels and scores are the exact
+    f32 top-1 of every row among the returned centroids (ties to the lower
+    centroid; label 0xFFFFFFFF and a NaN score for a row whose best score is
+    NaN), the update an ordered f64 sum, so the result is reproducible bit for
+    bit.  metric "euclidean" or "cosine" (spherical k-means); "dot" raises
+    ValueError.  Float32 matrices only (Float64, Int8 and compute= raise
+    TypeError); the corpus cache as in ``within``.  The labels are what
+    ``topk(..., corpus_by=labels)`` takes, with ``by=`` from ``topk(queries,
+    centroids, 1)``."""
+    from polars_matmul._polars_matmul import _kmeans_f32_only, _kmeans_search
+
+    c = np.asarray(x)
+    if c.dtype != np.float32:
+        raise _kmeans_f32_only(f"got a {c.dtype} matrix")
+    if c.ndim != 2:
+        raise TypeError(f"expected a 2-D array of embeddings, got shape {c.shape}")
+    cc = np.ascontiguousarray(c)
+    return _kmeans_search(cc, cc, cc, n_clusters, metric, max_iter, init, seed, compute, numpy_ok=cc is x)
+
+
 def matmul(queries: np.ndarray, corpus: np.ndarray) -> np.ndarray:
     """numpy-level Q @ C^T on the GPU (f32 iff both inputs are float32)."""
     q = np.asarray(queries)
@@ -491,6 +525,25 @@ if pl is not None:
                 lambda s: _topk_self(s, k, metric),
                 is_elementwise=False,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def kmeans(self, n_clusters: int, metric: Metric = "euclidean", max_iter: int = 25, init=None,
+                   seed: int = 0, compute=None) -> "pl.Expr":
+            """k-means (an extension) of a Float32 embedding column: the UInt32
+            cluster label of every row after Lloyd's iteration (``init``,
+            ``seed`` and ``max_iter`` as ``polars_matmul.kmeans``), null for a
+            row in no cluster (its best score is NaN).  euclidean or cosine.
+            The labels depend on the whole column, so the expression is not
+            elementwise; ``polars_matmul.kmeans`` also returns the centroids."""
+            from polars_matmul._polars_matmul import _kmeans_f32_only, _kmeans_metric
+
+            if compute is not None and compute != "f32":
+                raise _kmeans_f32_only(f"compute={compute!r} has no k-means")
+            _kmeans_metric(metric)
+            return self._expr.map_batches(
+                lambda s: _kmeans_labels(s, n_clusters, metric, max_iter, init, seed),
+                is_elementwise=False,
+                return_dtype=pl.UInt32,
             )
 
         def topk_maxsim(self, docs: "pl.Series", k: int, metric: Metric = "cosine",

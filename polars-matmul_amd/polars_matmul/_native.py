@@ -93,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "pmm_corpus_create_f32_docs",
     "pmm_corpus_docs",
     "pmm_topk_f32_maxsim",
+    "pmm_kmeans_f32_corpus",
     "pmm_range_f32_self",
     "pmm_topk_f32_self",
     "pmm_range_self_plan",
@@ -220,6 +221,8 @@ _SIGS = {
     "pmm_corpus_create_f32_docs": ([_vp, _i64, _i64, _vp, _i64, _vp], _i32),
     "pmm_corpus_docs": ([_vp, _vp, _vp, _i64], _i32),
     "pmm_topk_f32_maxsim": ([_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
+    "pmm_kmeans_f32_corpus": ([_vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64),
+                               ctypes.POINTER(ctypes.c_int)], _i32),
     "pmm_range_f32_self": ([_vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_self": ([_vp, _i64, _i32, _vp, _vp], _i32),
     "pmm_range_self_plan": ([_i64, _i32, _i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
@@ -1112,6 +1115,31 @@ class DeviceCorpus:
         finally:
             self.release()
         return idx, sc
+
+    def kmeans(self, init: np.ndarray, metric: int, max_iter: int):
+        """(centroids float32 (K, d), labels uint32 (n,), scores float32 (n,),
+        updates, converged) of pmm_kmeans_f32_corpus: Lloyd's iteration on the
+        handle's resident rows from the K initial centroids ``init``, at most
+        ``max_iter`` updates.  The labels and scores are the exact f32 top-1
+        of every row among the returned centroids (``NO_GROUP`` and NaN for a
+        row whose best score is NaN); a derived handle's labels number its own
+        rows.  Euclidean or cosine.  No rows are uploaded."""
+        init = np.ascontiguousarray(init, dtype=np.float32)
+        if init.ndim != 2 or init.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        K, n = init.shape[0], self.n
+        cent = np.empty((K, self.d), dtype=np.float32)
+        labels = np.empty(n, dtype=np.uint32)
+        sc = np.empty(n, dtype=np.float32)
+        updates, conv = ctypes.c_int64(0), ctypes.c_int(0)
+        self.acquire()
+        try:
+            check(_lib.pmm_kmeans_f32_corpus(self._h, K, ptr(init) if init.size else None, metric, int(max_iter),
+                                             ptr(cent) if cent.size else None, ptr(labels), ptr(sc),
+                                             ctypes.byref(updates), ctypes.byref(conv)))
+        finally:
+            self.release()
+        return cent, labels, sc, int(updates.value), bool(conv.value)
 
     def topk_candidates(self, q: np.ndarray, offsets, ids, k: int, metric: int):
         """(idx uint32 (m, k), scores float32 (m, k), lens uint32 (m,)) of

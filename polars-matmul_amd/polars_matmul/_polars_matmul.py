@@ -1468,6 +1468,122 @@ def _topk_self(col, k, metric):
     return _wrap(_topk_arrow(idx, sc.astype(np.float64), n, idx.shape[1]), "topk_self", polars_out)
 
 
+# ---------------------------------------------------------------------------
+# k-means (an extension; no reference counterpart): Lloyd's iteration on one
+# Float32 column, on its cached f32 handle (include/pmm.h
+# pmm_kmeans_f32_corpus).  The labels feed ``corpus_by=`` and the centroids
+# ``.pmm.topk(centroids, nprobe)``: the coarse quantiser of a grouped search.
+# ---------------------------------------------------------------------------
+def _kmeans_f32_only(what: str) -> TypeError:
+    return TypeError(
+        f"k-means runs on Float32 columns ({what}); cast the embeddings first, e.g. "
+        "pl.col('embedding').cast(pl.List(pl.Float32)) or array.astype(numpy.float32)"
+    )
+
+
+def _kmeans_metric(metric) -> int:
+    """The metric id, without the library: euclidean or cosine."""
+    if not isinstance(metric, str):
+        raise TypeError(f"argument 'metric': '{type(metric).__name__}' object cannot be converted to 'PyString'")
+    name = metric.lower()
+    if name == "dot":
+        raise ValueError("k-means takes metric 'euclidean' or 'cosine': a mean does not maximise a dot product")
+    if name in ("euclidean", "l2"):
+        return _native.METRIC_EUCLIDEAN
+    if name == "cosine":
+        return _native.METRIC_COSINE
+    raise ValueError(f"Unknown metric: {metric}. Use 'euclidean' or 'cosine'")
+
+
+def _kmeans_init(c: np.ndarray, K: int, init, seed) -> np.ndarray:
+    """The K x d float32 initial centroids: ``init`` as a [K, d] matrix, as K
+    distinct row ids of c, or None -- the rows
+    ``np.sort(np.random.RandomState(seed).choice(n, K, replace=False))``."""
+    n, d = c.shape
+    if init is None:
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise TypeError(f"seed must be an integer, not {type(seed).__name__}")
+        ids = np.sort(np.random.RandomState(int(seed)).choice(n, K, replace=False))
+        return np.ascontiguousarray(c[ids])
+    a = np.asarray(init)
+    if a.ndim == 2:
+        if a.dtype.kind != "f":
+            raise TypeError(f"init as a matrix must hold floats, got {a.dtype}")
+        if a.shape != (K, d):
+            raise ValueError(f"init has shape {a.shape}, n_clusters={K} centroids of dimension {d} need ({K}, {d})")
+        return np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim == 1 and a.dtype.kind in "iu":
+        if a.shape[0] != K:
+            raise ValueError(f"init holds {a.shape[0]} row ids, n_clusters is {K}")
+        ids = a.astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            bad = int(ids[(ids < 0) | (ids >= n)][0])
+            raise ValueError(f"init holds the row id {bad}: not a row of the column ({n} rows)")
+        if np.unique(ids).size != K:
+            raise ValueError("init holds a row id twice: the initial centroids must be distinct rows")
+        return np.ascontiguousarray(c[ids])
+    raise TypeError("init must be a [n_clusters, d] float matrix, a 1-D integer array of n_clusters distinct row ids, "
+                    "or None")
+
+
+def _kmeans_search(c, original, rv, n_clusters, metric, max_iter, init, seed, compute, numpy_ok=False):
+    """The checks (all before any library call) and the call behind ``_kmeans``
+    and ``polars_matmul.kmeans`` on the (n, d) float32 matrix c: (centroids,
+    labels, scores float32, updates, converged)."""
+    if compute is not None and compute != "f32":
+        raise _kmeans_f32_only(f"compute={compute!r} has no k-means")
+    metric_id = _kmeans_metric(metric)
+    K = _as_usize(n_clusters)
+    max_iter = _as_usize(max_iter)
+    n = c.shape[0]
+    if K < 1:
+        raise ValueError("n_clusters must be >= 1")
+    if K > n:
+        raise ValueError(f"n_clusters ({K}) must be <= the rows of the column ({n})")
+    c0 = _kmeans_init(c, K, init, seed)
+    _apply_devices_env()
+    return _self_device(c, original, rv, lambda dc: dc.kmeans(c0, metric_id, max_iter), numpy_ok)
+
+
+def _kmeans_column(col):
+    """(polars_out, arrow column, matrix) of a k-means Float32 column."""
+    polars_out = _is_polars_series(col)
+    rv = _to_arrow(col)
+    if not _is_f32(rv):
+        raise _kmeans_f32_only("got a column of another type")
+    return polars_out, rv, _series_to_matrix(rv, np.float32)
+
+
+def _kmeans(col, n_clusters, metric="euclidean", max_iter=25, init=None, seed=0, compute=None):
+    """k-means (an extension) of a Float32 column (Series, Arrow or numpy
+    matrix): Lloyd's iteration from ``init`` -- a [n_clusters, d] matrix, an
+    array of n_clusters distinct row ids, or None for
+    ``np.sort(np.random.RandomState(seed).choice(n, n_clusters, replace=False))``
+    -- for at most ``max_iter`` updates, stopped early once an assignment
+    repeats the previous labels.  Returns (centroids float32 [K, d], labels
+    uint32 [n], scores float32 [n], updates, converged): the labels and scores
+    are the exact f32 top-1 of every row among the returned centroids, ties to
+    the lower centroid; a row whose best score is NaN has the label 0xFFFFFFFF.
+    The update is an ordered f64 sum (include/pmm.h), so the result is
+    reproducible bit for bit.  euclidean or cosine (spherical k-means: the mean
+    of the members' unit vectors); dot raises ValueError.  Float32 only
+    (Float64, Int8 and compute= raise TypeError).  The column's cached f32
+    handle is used, under ``_topk``'s key: a column that is already a cached
+    corpus is not uploaded again."""
+    _, rv, c = _kmeans_column(col)
+    return _kmeans_search(c, col, rv, n_clusters, metric, max_iter, init, seed, compute)
+
+
+def _kmeans_labels(col, n_clusters, metric="euclidean", max_iter=25, init=None, seed=0, compute=None):
+    """``_kmeans``'s labels as a UInt32 column named "kmeans"; a row in no
+    cluster (label 0xFFFFFFFF) is null."""
+    polars_out, rv, c = _kmeans_column(col)
+    labels = _kmeans_search(c, col, rv, n_clusters, metric, max_iter, init, seed, compute)[1]
+    none = labels == _native.NO_GROUP
+    arr = pa.array(labels, type=pa.uint32(), mask=none if none.any() else None)
+    return _wrap(arr, "kmeans", polars_out)
+
+
 def _matmul(left, right):
     """src/lib.rs:15-30 -> src/matmul.rs:295-417 matmul_impl."""
     polars_out = _is_polars_series(left)
