@@ -492,6 +492,53 @@ int pmm_topk_f32_grouped(const pmm_corpus *corpus, const float *q, int64_t m, co
 int pmm_topk_f64_grouped(const pmm_corpus *corpus, const double *q, int64_t m, const uint32_t *qlabels, int64_t k,
                          int metric, uint32_t *out_idx, double *out_score, uint32_t *out_len);
 
+/* The plan of a probed search: (query row, probe list) into work slots.  Host
+ * only -- it touches no device and runs without one.  Query row i carries the
+ * labels probe_labels[probe_offsets[i] .. probe_offsets[i + 1])
+ * (probe_offsets: m + 1 entries from 0, never decreasing); group_offsets
+ * (G + 1 entries) are the partition's segment bounds (pmm_corpus_groups).  A
+ * label is in [0, G) or PMM_NO_GROUP; any other value is PMM_ERR_ARG naming the
+ * position and the query row.  PMM_NO_GROUP entries and labels of empty
+ * segments are skipped and a repeated label counts once.  The kept
+ * (row, label) slots leave stably sorted by label -- ascending query row inside
+ * a label: slot s is query row slot_row[s] in group slot_label[s].  Row i's
+ * slot numbers, ascending by label, are row_slots[row_offsets[i] ..
+ * row_offsets[i + 1]) (row_offsets: m + 1 entries); *slots = row_offsets[m].
+ * out_len[i] = min(k, rows of row i's segments).  slot_row, slot_label and
+ * row_slots have room for probe_offsets[m] entries (row_slots is also the
+ * plan's scratch).  m, G < 2^32 - 1, 0 <= k < 2^31.  A plan whose slots x k
+ * would pass 2^31 list entries: PMM_ERR_UNSUPPORTED (split the call). */
+int pmm_probe_plan(const int64_t *probe_offsets, const uint32_t *probe_labels, int64_t m,
+                   const int64_t *group_offsets, int64_t G, int64_t k, uint32_t *slot_row, uint32_t *slot_label,
+                   int64_t *row_offsets, uint32_t *row_slots, uint32_t *out_len, int64_t *slots);
+
+/* Probed top-k against a partitioned f32 handle (host queries in, host
+ * results out; 0 <= k <= 128): query row i is searched in the union of the
+ * groups its probe list names (pmm_probe_plan's reading of probe_offsets /
+ * probe_labels) -- IVF with several probes, a row visible in several groups.
+ * With ids_i the ascending PARENT row numbers of every row of those groups,
+ * row i's list is pmm_topk_f32(q[i], parent rows ids_i, min(k, len(ids_i)))
+ * with its indices mapped through ids_i: the same indices, score bits and tie
+ * order (equal scores go to the lower parent row, also across groups).
+ * out_len[i] = min(k, len(ids_i)); the slots past it hold index 0xFFFFFFFF and
+ * score +0.0.  A row with one probe gets pmm_topk_f32_grouped's bits; probing
+ * every group of a partition that dropped no row gives pmm_topk_f32_corpus'
+ * bits on the parent.
+ * The queries are uploaded once and never copied per probe: the grouped
+ * kernel's row-table variant reads slot s's query row through slot_row[s],
+ * ONE launch for every (group, <= 16 slots) unit whose segment has at most
+ * PMM_GROUPED_SEG_MAX rows and roundup(d, 32) <= 1024; the other pairs gather
+ * their rows and run one after another through pmm_topk_f32_corpus' route
+ * (PMM_GROUPED=kernel | loop as in the grouped entry).  One launch of the merge
+ * kernel then keeps every row's best k of its per-group lists, keyed by score
+ * and parent row, and writes the caller's rows.
+ * A label that is no group: PMM_ERR_ARG before any device call.  A handle that
+ * is not partitioned: PMM_ERR_ARG; an f64 or bf16 handle, k > 128, or slots x
+ * k past 2^31: PMM_ERR_UNSUPPORTED. */
+int pmm_topk_f32_probed(const pmm_corpus *corpus, const float *q, int64_t m, const int64_t *probe_offsets,
+                        const uint32_t *probe_labels, int64_t k, int metric, uint32_t *out_idx, float *out_score,
+                        uint32_t *out_len);
+
 /* pmm_topk_f32 against a device-resident corpus (host queries in, host
  * results out; 0 <= k <= n).  Results are pmm_topk_f32's bit for bit.
  *

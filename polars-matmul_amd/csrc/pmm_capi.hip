@@ -3497,6 +3497,260 @@ static int topk_grouped(const pmm_corpus *h, const Score *q, int64_t m, const ui
   });
 }
 
+// ---------------------------------------------------------------------------
+// Probed search: every query row is searched inside the union
+// of several groups' segments -- IVF with nprobe lists, a document visible to
+// several tenants.  The plan turns (query row, probe list) into label-sorted
+// slots; the grouped kernel's row-table variant (or the loop's executors)
+// writes one exact list per slot; probe_merge_f32_kernel keeps each row's best
+// k under the parent's row order.
+// ---------------------------------------------------------------------------
+// The plan (host only, no device).  Row i's labels are probe_labels[
+// probe_offsets[i] .. probe_offsets[i + 1]); kNoGroup entries and labels of
+// empty segments are skipped and a repeated label counts once.  The kept
+// (row, label) slots leave stably sorted by label (ascending row inside a
+// label): slot_row / slot_label; row i's slot numbers, ascending by label (and
+// so ascending), are row_slots[row_offsets[i] .. row_offsets[i + 1]);
+// out_len[i] = min(k, rows of the row's segments); *slots = row_offsets[m].
+static int probe_plan(const int64_t *po, const uint32_t *pl, int64_t m, const int64_t *goff, int64_t G, int64_t k,
+                      uint32_t *slot_row, uint32_t *slot_label, int64_t *row_offsets, uint32_t *row_slots,
+                      uint32_t *out_len, int64_t *slots) {
+  if (m < 0 || G < 0 || m > (int64_t)UINT32_MAX - 1 || G > (int64_t)UINT32_MAX - 1)
+    return fail(PMM_ERR_ARG, "probe sizes out of range (m=%lld G=%lld)", (long long)m, (long long)G);
+  if (k < 0 || k > INT32_MAX) return fail(PMM_ERR_ARG, "k must be in [0, 2^31) (got %lld)", (long long)k);
+  if (!po || !goff || !row_offsets || !slots || (m > 0 && !out_len)) return fail(PMM_ERR_ARG, "null argument");
+  if (po[0] != 0) return fail(PMM_ERR_ARG, "probe_offsets[0] must be 0 (got %lld)", (long long)po[0]);
+  for (int64_t i = 0; i < m; i++)
+    if (po[i + 1] < po[i])
+      return fail(PMM_ERR_ARG, "probe_offsets must not decrease (row %lld: %lld after %lld)", (long long)i,
+                  (long long)po[i + 1], (long long)po[i]);
+  const int64_t cap = po[m];
+  if (cap > 0 && (!pl || !slot_row || !slot_label || !row_slots)) return fail(PMM_ERR_ARG, "null argument");
+  // pass one: every row's kept labels, ascending and distinct, packed into row_slots for now
+  row_offsets[0] = 0;
+  for (int64_t i = 0; i < m; i++) {
+    uint32_t *kept = row_slots + row_offsets[i];
+    int64_t nk = 0;
+    for (int64_t e = po[i]; e < po[i + 1]; e++) {
+      const uint32_t l = pl[e];
+      if (l == kNoGroup) continue;
+      if ((int64_t)l >= G)
+        return fail(PMM_ERR_ARG,
+                    "probe_labels[%lld] = %u (query row %lld) is not a group (G=%lld) and not the none label 0xFFFFFFFF",
+                    (long long)e, l, (long long)i, (long long)G);
+      if (goff[l + 1] > goff[l]) kept[nk++] = l;
+    }
+    std::sort(kept, kept + nk);
+    nk = std::unique(kept, kept + nk) - kept;
+    int64_t rows = 0;
+    for (int64_t j = 0; j < nk; j++) rows += goff[kept[j] + 1] - goff[kept[j]];
+    out_len[i] = (uint32_t)std::min(k, rows);
+    row_offsets[i + 1] = row_offsets[i] + nk;
+  }
+  const int64_t S = row_offsets[m];
+  *slots = S;
+  if (S > 0 && k > 0 && S > ((int64_t)1 << 31) / k)
+    return fail(PMM_ERR_UNSUPPORTED,
+                "%lld (query row, group) lists of k=%lld entries pass 2^31 entries: split the call into fewer query rows",
+                (long long)S, (long long)k);
+  // pass two: the stable counting sort of the slots by label
+  std::vector<int64_t> next((size_t)G + 1, 0);
+  for (int64_t e = 0; e < S; e++) next[row_slots[e] + 1]++;
+  for (int64_t g = 0; g < G; g++) next[g + 1] += next[g];
+  for (int64_t i = 0; i < m; i++)
+    for (int64_t e = row_offsets[i]; e < row_offsets[i + 1]; e++) {
+      const uint32_t l = row_slots[e];
+      const int64_t sl = next[l]++;
+      slot_row[sl] = (uint32_t)i;
+      slot_label[sl] = l;
+      row_slots[e] = (uint32_t)sl;
+    }
+  return PMM_OK;
+}
+
+static int topk_probed(const pmm_corpus *h, const float *q, int64_t m, const int64_t *po, const uint32_t *pl,
+                       int64_t k, int metric, uint32_t *out_idx, float *out_score, uint32_t *out_len) {
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!h->partitioned())
+    return fail(PMM_ERR_ARG, "the corpus handle is not partitioned: pmm_corpus_partition derives one");
+  if (h->dtype != PMM_DTYPE_F32)
+    return fail(PMM_ERR_UNSUPPORTED, "probed search runs on f32 handles: search a %s corpus per label and merge",
+                h->dtype == PMM_DTYPE_BF16 ? "bf16" : "f64");
+  int rc = validate_sizes(m, h->n, h->d, 0, false);
+  if (rc) return rc;
+  if (k < 0 || k > INT32_MAX) return fail(PMM_ERR_ARG, "k must be in [0, 2^31) (got %lld)", (long long)k);
+  if (k > kGroupedMaxK)
+    return fail(PMM_ERR_UNSUPPORTED, "probed search supports k <= %d (got %lld)", kGroupedMaxK, (long long)k);
+  if ((rc = check_metric(metric))) return rc;
+  if (m == 0) return PMM_OK;
+  if ((rc = need_buffers(q, po, out_len))) return rc;
+  if (k > 0 && (rc = need_buffers(out_idx, out_score))) return rc;
+  const int64_t G = (int64_t)h->offsets.size() - 1, d = h->d, dp = h->dp;
+  const std::vector<int64_t> &off = h->offsets;
+  if (po[0] != 0 || po[m] < 0) return fail(PMM_ERR_ARG, "probe_offsets must start at 0 and not decrease");
+  const size_t cap = (size_t)po[m];
+  std::vector<uint32_t> slot_row(cap), slot_label(cap), row_slots(cap);
+  std::vector<int64_t> roff((size_t)m + 1);
+  int64_t S = 0;
+  if ((rc = probe_plan(po, pl, m, off.data(), G, k, slot_row.data(), slot_label.data(), roff.data(),
+                       row_slots.data(), out_len, &S)))
+    return rc;
+  if (k == 0 || S == 0) {  // nothing to search: empty lists, no device work
+    for (int64_t t = 0; t < m * k; t++) {
+      out_idx[t] = kNoGroup;
+      out_score[t] = 0.0f;
+    }
+    return PMM_OK;
+  }
+  // Dispatch as the grouped entry's (PMM_GROUPED, PMM_GROUPED_SEG_MAX: read per call).
+  const char *ge = getenv("PMM_GROUPED");
+  const bool force_kernel = ge && !strcmp(ge, "kernel"), force_loop = ge && !strcmp(ge, "loop");
+  int64_t seg_max = kGroupedSegMax;
+  if (const char *se = getenv("PMM_GROUPED_SEG_MAX")) seg_max = atoll(se);
+  const bool kernel_ok = dp <= kGroupedMaxDp && !force_loop;
+  std::vector<GroupedPair> pairs;  // (q0, mq: a run of slots with one label)
+  std::vector<GroupedUnit> units;
+  for (int64_t s0 = 0; s0 < S;) {
+    const uint32_t g = slot_label[s0];
+    int64_t s1 = s0 + 1;
+    while (s1 < S && slot_label[s1] == g) s1++;
+    GroupedPair p{s0, s1 - s0, off[g], off[g + 1] - off[g], false};
+    p.kernel = kernel_ok && (force_kernel || p.ng <= seg_max);
+    pairs.push_back(p);
+    if (p.kernel)
+      for (int64_t r0 = 0; r0 < p.mq; r0 += kGroupedRows)
+        units.push_back(GroupedUnit{(uint32_t)p.c0, (uint32_t)p.ng, (uint32_t)(p.q0 + r0),
+                                    (uint32_t)std::min<int64_t>(kGroupedRows, p.mq - r0)});
+    s0 = s1;
+  }
+  const CorpusShard &x = h->shards[0];
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const int dev = f.dev, cus = f.cus;
+  const hipStream_t s = f.s;
+  // The loop pairs' routes, the largest workspace, query slice and short-list staging among them.
+  std::vector<TopkRoute> routes;
+  size_t ws_need = 0, tmp_entries = 0, loop_rows = 0;
+  for (const GroupedPair &p : pairs) {
+    if (p.kernel) continue;
+    const int64_t kg = std::min<int64_t>(k, p.ng);
+    routes.push_back(route_topk(p.mq, p.ng, d, kg, metric, PMM_COMPUTE_F32, cus, false, false));
+    ws_need = std::max(ws_need, routes.back().total);
+    loop_rows = std::max(loop_rows, (size_t)p.mq);
+    if (kg < k) tmp_entries = std::max(tmp_entries, (size_t)(p.mq * kg));
+  }
+  // The workspace (DESIGN.md §4d states this sum): no term in slots * dp.
+  const size_t tab_words = units.size() * 4 + (size_t)2 * S + (size_t)m + 1;
+  const size_t off_qu = 0, off_qn = al256((size_t)m * dp * 4), off_tab = off_qn + al256((size_t)m * 4);
+  const size_t off_gi = off_tab + al256(tab_words * 4), off_gs = off_gi + al256((size_t)S * k * 4);
+  const size_t off_oi = off_gs + al256((size_t)S * k * 4), off_os = off_oi + al256((size_t)m * k * 4);
+  const size_t off_ol = off_os + al256((size_t)m * k * 4), off_ql = off_ol + al256((size_t)m * 4);
+  const size_t off_ti = off_ql + al256(loop_rows * dp * 4), off_ts = off_ti + al256(tmp_entries * 4);
+  const size_t off_w = off_ts + al256(tmp_entries * 4);
+  void *base;
+  if ((rc = arena(dev, s, off_w + ws_need, &base))) return rc;
+  char *b = (char *)base;
+  const float *qu = (const float *)(b + off_qu);
+  float *qn = (float *)(b + off_qn), *ql = (float *)(b + off_ql);
+  uint32_t *tab = (uint32_t *)(b + off_tab);
+  const GroupedUnit *d_units = (const GroupedUnit *)tab;
+  const uint32_t *d_slot_row = tab + units.size() * 4, *d_row_off = d_slot_row + S, *d_row_slots = d_row_off + m + 1;
+  uint32_t *gi = (uint32_t *)(b + off_gi), *oi = (uint32_t *)(b + off_oi), *ol = (uint32_t *)(b + off_ol);
+  uint32_t *ti = (uint32_t *)(b + off_ti);
+  float *gs = (float *)(b + off_gs), *os = (float *)(b + off_os), *ts = (float *)(b + off_ts);
+  if ((rc = upload_padded(b + off_qu, q, m, d, dp, 4, s))) return rc;
+  std::vector<uint32_t> htab(tab_words);
+  {
+    uint32_t *t = htab.data();
+    if (!units.empty()) memcpy(t, units.data(), units.size() * sizeof(GroupedUnit));
+    t += units.size() * 4;
+    memcpy(t, slot_row.data(), (size_t)S * 4);
+    t += S;
+    for (int64_t i = 0; i <= m; i++) t[i] = (uint32_t)roff[i];
+    t += m + 1;
+    memcpy(t, row_slots.data(), (size_t)S * 4);
+  }
+  const float *cn = shard_norms<float>(h, x, metric);  // [norms n | pre-filter factors n]
+  // (from here on a failure waits for the stream: the upload reads this frame's vector)
+  return f.run([&]() -> int {
+    {
+      Timed t("h2d", s);
+      HIP_TRY(hipMemcpyAsync(tab, htab.data(), tab_words * 4, hipMemcpyHostToDevice, s));
+    }
+    // the query norms, once over the uploaded rows (the kernel's and the
+    // sign-of-zero pass's; the loop's executors compute their own, the same values)
+    if (metric != kMetricDot && (!units.empty() || metric == kMetricCosine)) {
+      Timed t("norms_f32", s);
+      HIP_TRY(launch_norms_f32(qu, m, d, dp, metric == kMetricEuclidean, qn, nullptr, s));
+    }
+    if (!units.empty()) {
+      GroupedArgs a{};
+      a.q = qu;
+      a.c = x.rows_as<float>();
+      a.qn = qn;
+      a.cn = cn;
+      a.ldq = dp;
+      a.ldc = dp;
+      a.dp = (int)dp;
+      a.k = (int)k;
+      a.units = d_units;
+      a.out_idx = gi;
+      a.out_score = gs;
+      a.qrow = d_slot_row;
+      Timed t("probed_topk_f32", s);
+      HIP_TRY(launch_grouped_topk_f32(a, (int)units.size(), metric, s));
+    }
+    // the loop path: one pair's query rows gathered into a dense slice, the
+    // existing executor on it, one pair after another
+    size_t ri = 0;
+    for (const GroupedPair &p : pairs) {
+      if (p.kernel) continue;
+      const int64_t kg = std::min<int64_t>(k, p.ng);
+      uint32_t *di = kg == k ? gi + p.q0 * k : ti;
+      float *ds = kg == k ? gs + p.q0 * k : ts;
+      {
+        Timed t("probed_gather_queries", s);
+        HIP_TRY(launch_gather_rows(qu, (int64_t)(dp / 4), (const int *)(d_slot_row + p.q0), (int)p.mq, (int)(dp / 4),
+                                   ql, s));
+      }
+      if (int r2 = topk_f32_device_impl(routes[ri++], ql, dp, p.mq, x.rows_as<float>() + p.c0 * dp, dp, p.ng, d, kg,
+                                        metric, (uint32_t)p.c0, di, ds, b + off_w, ws_need, s, dev,
+                                        cn ? cn + p.c0 : nullptr, false, nullptr, cn ? cn + h->n + p.c0 : nullptr))
+        return r2;
+      if (kg < k) {
+        Timed t("grouped_pad", s);
+        HIP_TRY(launch_grouped_pad(di, ds, (int)p.mq, (int)kg, (int)k, gi + p.q0 * k, gs + p.q0 * k, false, s));
+      }
+    }
+    // the sign of zero scores, while the lists still number the partition's
+    // rows: list s belongs to query row slot_row[s] (cosine and dot; the loop
+    // pairs' executors have restored theirs already)
+    HIP_TRY(launch_zero_sign_f32(qu, dp, x.rows_as<float>(), dp, qn, cn, (int)S, h->n, (int)d, (int)k, metric, 0u, gi,
+                                 gs, s, d_slot_row));
+    {
+      ProbeMergeArgs a{};
+      a.in_idx = gi;
+      a.in_score = gs;
+      a.row_off = d_row_off;
+      a.row_slots = d_row_slots;
+      a.map = h->map;
+      a.n = (uint32_t)h->n;
+      a.m = (int)m;
+      a.k = (int)k;
+      a.out_idx = oi;
+      a.out_score = os;
+      a.out_len = ol;
+      Timed t("probe_merge", s);
+      HIP_TRY(launch_probe_merge_f32(a, metric, s));
+    }
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_len, ol, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    }
+    return download_lists(out_idx, out_score, oi, os, m, k, s);
+  });
+}
+
 // ===========================================================================
 // C ABI
 // ===========================================================================
@@ -4210,6 +4464,19 @@ int pmm_topk_f32_grouped(const pmm_corpus *h, const float *q, int64_t m, const u
 int pmm_topk_f64_grouped(const pmm_corpus *h, const double *q, int64_t m, const uint32_t *qlabels, int64_t k,
                          int metric, uint32_t *out_idx, double *out_score, uint32_t *out_len) {
   return topk_grouped<double>(h, q, m, qlabels, k, metric, out_idx, out_score, out_len);
+}
+
+int pmm_probe_plan(const int64_t *probe_offsets, const uint32_t *probe_labels, int64_t m,
+                   const int64_t *group_offsets, int64_t G, int64_t k, uint32_t *slot_row, uint32_t *slot_label,
+                   int64_t *row_offsets, uint32_t *row_slots, uint32_t *out_len, int64_t *slots) {
+  return probe_plan(probe_offsets, probe_labels, m, group_offsets, G, k, slot_row, slot_label, row_offsets, row_slots,
+                    out_len, slots);
+}
+
+int pmm_topk_f32_probed(const pmm_corpus *h, const float *q, int64_t m, const int64_t *probe_offsets,
+                        const uint32_t *probe_labels, int64_t k, int metric, uint32_t *out_idx, float *out_score,
+                        uint32_t *out_len) {
+  return topk_probed(h, q, m, probe_offsets, probe_labels, k, metric, out_idx, out_score, out_len);
 }
 
 int pmm_corpus_create_f64(const double *c, int64_t n, int64_t d, pmm_corpus **out) {

@@ -426,10 +426,12 @@ hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m
                                  hipStream_t s);
 // cosine and dot lists: +0.0 scores whose reference value is -0.0 get their
 // sign back (the selection keys fold the two zeros); euclidean: nothing.  The
-// norms are read for cosine only.
+// norms are read for cosine only.  qrow (f32, may be NULL): list row i belongs
+// to row qrow[i] of q and qn (probed search: several lists per query row).
 hipError_t launch_zero_sign_f32(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
                                 const float *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
-                                const uint32_t *out_idx, float *out_score, hipStream_t s);
+                                const uint32_t *out_idx, float *out_score, hipStream_t s,
+                                const uint32_t *qrow = nullptr);
 hipError_t launch_zero_sign_f64(const double *q, int64_t ldq, const double *c, int64_t ldc, const double *qn,
                                 const double *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
                                 const uint32_t *out_idx, double *out_score, hipStream_t s);
@@ -492,8 +494,14 @@ struct GroupedArgs {
   const GroupedUnit *units;  // device table, one entry per workgroup
   uint32_t *out_idx;         // [grouped rows][k]: partition-row numbers, best first, padded
   float *out_score;
+  // The row table (probed search, the kernel's ROWTAB variant; NULL: the grouped
+  // entry's layout above).  A unit's rows [q0, q0 + mq) are then slots of the
+  // label-sorted (query row, label) slots: slot s reads row qrow[s] of q -- the
+  // uploaded queries as they are -- and norm qn[qrow[s]], and writes list s.
+  const uint32_t *qrow;
 };
 size_t grouped_lds_bytes(int dp);
+// (a.qrow set: one launch of the row-table variant, Timed as probed_topk_f32)
 hipError_t launch_grouped_topk_f32(const GroupedArgs &a, int units, int metric, hipStream_t s);
 // di / ds rows of k entries = the dense rows x kg lists si / ss, padded (index 0xFFFFFFFF, score 0)
 hipError_t launch_grouped_pad(const uint32_t *si, const void *ss, int rows, int kg, int k, uint32_t *di, void *ds,
@@ -503,6 +511,27 @@ hipError_t launch_grouped_pad(const uint32_t *si, const void *ss, int rows, int 
 hipError_t launch_grouped_scatter(const uint32_t *gi, const void *gs, const uint32_t *qrow, const uint32_t *glen,
                                   int64_t rows, int k, const uint32_t *map, uint32_t n, uint32_t *out_idx,
                                   void *out_score, uint32_t *out_len, bool f64, hipStream_t s);
+// ---- probed search (pmm_probed.hip) ----
+// The merge of a query row's per-slot lists (probe_merge_f32_kernel): row i's
+// lists are the slots row_slots[row_off[i] .. row_off[i + 1]) of in_idx /
+// in_score (k entries each, partition rows, best first, padded with index
+// 0xFFFFFFFF); out row i = the best k of them under okey32(rank value) << 32 |
+// ~map[partition row], in the parent's numbering, padded, with its length.
+struct ProbeMergeArgs {
+  const uint32_t *in_idx;     // [slots][k]
+  const float *in_score;      // [slots][k]
+  const uint32_t *row_off;    // [m + 1]
+  const uint32_t *row_slots;  // [slots]
+  const uint32_t *map;        // [n]: partition row -> parent row
+  uint32_t n;
+  int m, k;                   // 1 <= k <= kGroupedMaxK
+  uint32_t *out_idx;          // [m][k]
+  float *out_score;           // [m][k]
+  uint32_t *out_len;          // [m]
+};
+hipError_t launch_probe_merge_f32(const ProbeMergeArgs &a, int metric, hipStream_t s);
+// the grouped kernel's row-table variant (a.qrow set); launch_grouped_topk_f32 checks the arguments and calls it
+hipError_t launch_grouped_rowtab(const GroupedArgs &a, int units, int metric, hipStream_t s);
 hipError_t launch_gemm_f64_store(const double *q, int64_t ldq, const double *c, int64_t ldc,
                                  const double *qn, const double *cn, int M, int N, int D,
                                  int metric, int store_metric, double *out, int64_t ldo,

@@ -2756,7 +2756,8 @@ __global__ __launch_bounds__(256) void zero_sign_kernel(const T *__restrict__ q,
                                                         const T *__restrict__ qn, const T *__restrict__ cn,
                                                         int m, int64_t n, int d, int k, int metric,
                                                         uint32_t index_base, const uint32_t *__restrict__ out_idx,
-                                                        T *__restrict__ out_score) {
+                                                        T *__restrict__ out_score,
+                                                        const uint32_t *__restrict__ qrow) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)m * k) return;
   if (!is_pos_zero(out_score[t])) return;
@@ -2765,8 +2766,9 @@ __global__ __launch_bounds__(256) void zero_sign_kernel(const T *__restrict__ q,
   if (id == 0xFFFFFFFFu) return;
   const int64_t col = (int64_t)(uint32_t)(id - index_base);
   if (col >= n) return;
-  const int row = (int)(t / k);
-  const T *qr = q + (int64_t)row * ldq, *cr = c + col * ldc;
+  // (a row table: list t / k is one of several lists of query row qrow[t / k])
+  const int64_t row = qrow ? (int64_t)qrow[t / k] : t / k;
+  const T *qr = q + row * ldq, *cr = c + col * ldc;
   T acc = (T)0;
   for (int i = 0; i < d; i++) acc = fma_chain_step(qr[i], cr[i], acc);
   // (a dot product is its chain: no norms are read)
@@ -2778,10 +2780,10 @@ __global__ __launch_bounds__(256) void zero_sign_kernel(const T *__restrict__ q,
 // out_score is the dense m x k matrix of Q C^T over c's first k rows (k = n).
 hipError_t launch_zero_sign_f32(const float *q, int64_t ldq, const float *c, int64_t ldc, const float *qn,
                                 const float *cn, int m, int64_t n, int d, int k, int metric, uint32_t index_base,
-                                const uint32_t *out_idx, float *out_score, hipStream_t s) {
+                                const uint32_t *out_idx, float *out_score, hipStream_t s, const uint32_t *qrow) {
   if (m <= 0 || k <= 0 || metric == kMetricEuclidean) return hipSuccess;
   zero_sign_kernel<float><<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(
-      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score);
+      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score, qrow);
   return hipGetLastError();
 }
 hipError_t launch_zero_sign_f64(const double *q, int64_t ldq, const double *c, int64_t ldc, const double *qn,
@@ -2789,7 +2791,7 @@ hipError_t launch_zero_sign_f64(const double *q, int64_t ldq, const double *c, i
                                 const uint32_t *out_idx, double *out_score, hipStream_t s) {
   if (m <= 0 || k <= 0 || metric == kMetricEuclidean) return hipSuccess;
   zero_sign_kernel<double><<<(unsigned)(((int64_t)m * k + 255) / 256), 256, 0, s>>>(
-      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score);
+      q, ldq, c, ldc, qn, cn, m, n, d, k, metric, index_base, out_idx, out_score, nullptr);
   return hipGetLastError();
 }
 

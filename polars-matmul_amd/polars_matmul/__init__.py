@@ -107,7 +107,10 @@ def topk(queries: np.ndarray, corpus: np.ndarray, k: int, metric: Metric = "cosi
     (per label on the host rows: a numpy corpus has no cached handle).
     k' = min(k, largest searched segment); a row whose segment is shorter (or
     empty: a null or unseen label) ends in unused slots -- index 0xFFFFFFFF,
-    score NaN.  Not together with ``subset``.
+    score NaN.  Not together with ``subset``.  ``query_labels`` as a 2-D
+    integer matrix [m, P] or an Arrow List array gives every query a LIST of
+    labels (probed search): it is searched in the union of those labels' rows,
+    ties to the lower corpus row; k' = min(k, largest searched union).
     candidates (an extension): one list of corpus row ids per query row, as an
     Arrow List array or a pair ``(offsets, ids)`` of numpy arrays; every query
     is searched only among its own list, all rows in one call.  float32
@@ -403,6 +406,9 @@ if pl is not None:
             Series aligned with ``corpus``.  Every row is searched only among
             the corpus rows whose ``corpus_by`` equals its ``by`` (null matches
             nothing); the lists are ragged, min(k, rows of that label) long.
+            A ``by`` column of List type (one list of labels per row, e.g. the
+            nprobe nearest k-means clusters) searches the union of those
+            labels' rows -- probed search, ties to the lower corpus row.
             candidates (an extension): an expression or column name of the
             query frame holding one List of corpus row ids per row (any integer
             type; a null list is empty).  Every row is searched only among its

@@ -85,6 +85,8 @@ EXPORTED_SYMBOLS = (
     "pmm_corpus_groups",
     "pmm_topk_f32_grouped",
     "pmm_topk_f64_grouped",
+    "pmm_probe_plan",
+    "pmm_topk_f32_probed",
     "pmm_topk_f32_corpus",
     "pmm_topk_f64_corpus",
     "pmm_topk_bf16_corpus",
@@ -212,6 +214,9 @@ _SIGS = {
     "pmm_corpus_groups": ([_vp, ctypes.POINTER(ctypes.c_int64), _vp, _i64], _i32),
     "pmm_topk_f32_grouped": ([_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_topk_f64_grouped": ([_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
+    "pmm_probe_plan": ([_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
+                       _i32),
+    "pmm_topk_f32_probed": ([_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
     "pmm_topk_f32_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_f64_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
     "pmm_topk_bf16_corpus": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp], _i32),
@@ -782,6 +787,37 @@ def partition_plan(labels, G: int):
     return perm[:kept.value], offsets
 
 
+def _probe_lists(probe_offsets, probe_labels, m: int):
+    """(offsets int64 (m + 1,), labels uint32) as the probed entries take them."""
+    po = np.ascontiguousarray(probe_offsets, dtype=np.int64).reshape(-1)
+    pl = np.ascontiguousarray(probe_labels, dtype=np.uint32).reshape(-1)
+    if po.size != m + 1:
+        raise ValueError(f"probe_offsets has {po.size} entries for {m} query rows: one more than rows is needed")
+    if po[0] != 0 or np.any(np.diff(po) < 0) or po[-1] != pl.size:
+        raise ValueError(f"probe_offsets must rise from 0 to len(probe_labels) = {pl.size}")
+    return po, pl
+
+
+def probe_plan(probe_offsets, probe_labels, group_offsets, k: int):
+    """(slot_row uint32 [S], slot_label uint32 [S], row_offsets int64 [m + 1],
+    row_slots uint32 [S], out_len uint32 [m]) of pmm_probe_plan: the distinct
+    (query row, label) slots with a non-empty segment, stably sorted by label;
+    every row's slot numbers; every row's list length.  Host only: runs
+    without a GPU."""
+    po = np.ascontiguousarray(probe_offsets, dtype=np.int64).reshape(-1)
+    po, pl = _probe_lists(po, probe_labels, po.size - 1)
+    goff = np.ascontiguousarray(group_offsets, dtype=np.int64).reshape(-1)
+    m, cap = po.size - 1, int(po[-1])
+    slot_row, slot_label = np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.uint32)
+    row_slots, row_offsets = np.empty(cap, dtype=np.uint32), np.empty(m + 1, dtype=np.int64)
+    out_len = np.empty(m, dtype=np.uint32)
+    slots = ctypes.c_int64(0)
+    check(_lib.pmm_probe_plan(ptr(po), ptr(pl), m, ptr(goff), goff.size - 1, int(k), ptr(slot_row), ptr(slot_label),
+                              ptr(row_offsets), ptr(row_slots), ptr(out_len), ctypes.byref(slots)))
+    S = slots.value
+    return slot_row[:S], slot_label[:S], row_offsets, row_slots[:S], out_len
+
+
 def ascending_ids(ids, n: int) -> np.ndarray:
     """Row ids as the subset entries take them: uint32, ascending, unique.
     An id outside [0, n) raises ValueError."""
@@ -1288,6 +1324,30 @@ class DeviceCorpus:
         self.acquire()
         try:
             check(fn(self._h, ptr(q), m, ptr(qlabels), k, metric, ptr(idx), ptr(sc), ptr(lens)))
+        finally:
+            self.release()
+        return idx, sc, lens
+
+    def topk_probed(self, q: np.ndarray, probe_offsets, probe_labels, k: int, metric: int):
+        """(idx uint32 (m, k), scores float32 (m, k), lens uint32 (m,)) of
+        pmm_topk_f32_probed on a partitioned f32 handle: row i searched in the
+        union of the groups ``probe_labels[probe_offsets[i]:probe_offsets[i +
+        1]]`` (``NO_GROUP`` entries, labels of empty segments and repeats are
+        skipped); its first ``lens[i]`` slots are the exact top-k of that
+        union in the PARENT's numbering, ties to the lower parent row, the
+        rest hold index 0xFFFFFFFF and score 0.  k <= 128."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        m = q.shape[0]
+        po, pl = _probe_lists(probe_offsets, probe_labels, m)
+        idx = np.empty((m, k), dtype=np.uint32)
+        sc = np.empty((m, k), dtype=np.float32)
+        lens = np.empty(m, dtype=np.uint32)
+        self.acquire()
+        try:
+            check(_lib.pmm_topk_f32_probed(self._h, ptr(q), m, ptr(po), ptr(pl), k, metric, ptr(idx), ptr(sc),
+                                           ptr(lens)))
         finally:
             self.release()
         return idx, sc, lens

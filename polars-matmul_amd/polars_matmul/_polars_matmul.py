@@ -508,23 +508,72 @@ def _topk_subset(q, c, original, rv, sel: _Selection, kk: int, metric_id: int, c
 # group by group (DeviceCorpus.partition), cached beside it under the parent's
 # key plus the label array's buffers, and one call searches every query in its
 # group's segment (DeviceCorpus.topk_grouped).
+# Probed search: when the left side holds one LIST of labels per query row (an
+# Arrow List / LargeList / FixedSizeList, or a 2-D integer matrix), every row is
+# searched in the union of its labels' segments on the same partitioned handle
+# (DeviceCorpus.topk_probed) -- IVF with nprobe lists, rows visible in several
+# groups.
 # ---------------------------------------------------------------------------
 class _Groups:
     """A checked ``groups=`` argument: uint32 labels of the query rows and of
     the corpus rows in [0, G) (``_native.NO_GROUP``: matches nothing), the
     corpus rows per label, and -- when the corpus labels' buffers persist
-    across calls -- their ``_arrow_key`` with the array that keeps them alive."""
+    across calls -- their ``_arrow_key`` with the array that keeps them alive.
+    Probed search (a list of labels per query row): ``probe_offsets`` (int64,
+    m + 1) cuts ``qlabels``, the flattened labels, into the rows' lists."""
 
-    __slots__ = ("qlabels", "clabels", "G", "sizes", "key", "keep")
+    __slots__ = ("qlabels", "clabels", "G", "sizes", "key", "keep", "probe_offsets")
 
-    def __init__(self, qlabels, clabels, G, key, keep):
+    def __init__(self, qlabels, clabels, G, key, keep, probe_offsets=None):
         self.qlabels, self.clabels, self.G, self.key, self.keep = qlabels, clabels, G, key, keep
+        self.probe_offsets = probe_offsets
         self.sizes = np.bincount(clabels[clabels != _native.NO_GROUP], minlength=G).astype(np.int64)
 
+    def probe_pairs(self) -> np.ndarray:
+        """Probed search: the distinct (label, query row) pairs with a
+        non-empty segment, int64 (pairs, 2), sorted by label, then row."""
+        rows = np.repeat(np.arange(self.probe_offsets.size - 1, dtype=np.int64), np.diff(self.probe_offsets))
+        keep = self.qlabels != _native.NO_GROUP
+        keep[keep] = self.sizes[self.qlabels[keep]] > 0
+        pairs = np.stack([self.qlabels[keep].astype(np.int64), rows[keep]], axis=1)
+        return np.unique(pairs, axis=0) if pairs.size else pairs
+
     def searched_max(self) -> int:
-        """Rows of the largest segment some query searches (0: none does)."""
+        """Rows of the largest segment (probed search: union of segments)
+        some query searches (0: none does)."""
+        if self.probe_offsets is not None:
+            pairs = self.probe_pairs()
+            if not pairs.size:
+                return 0
+            return int(np.bincount(pairs[:, 1], weights=self.sizes[pairs[:, 0]]).max())
         ql = self.qlabels[self.qlabels != _native.NO_GROUP]
         return int(self.sizes[ql].max()) if ql.size else 0
+
+
+def _probe_lists(obj):
+    """(offsets int64 (m + 1,), the flattened labels) when ``obj`` holds one
+    list of labels per row -- an Arrow List / LargeList / FixedSizeList (a
+    null list is empty) or a 2-D integer matrix [m, P] -- else None."""
+    if isinstance(obj, np.ndarray) and obj.ndim == 2:
+        if obj.dtype.kind not in "iu":
+            raise TypeError(f"a matrix of probe labels must hold integers, got {obj.dtype}")
+        m, P = obj.shape
+        return np.arange(m + 1, dtype=np.int64) * P, np.ascontiguousarray(obj).reshape(-1)
+    if _is_polars_series(obj):
+        obj = obj.rechunk().to_arrow()
+    if isinstance(obj, pa.ChunkedArray):
+        obj = obj.combine_chunks() if obj.num_chunks != 1 else obj.chunk(0)
+    if not isinstance(obj, pa.Array):
+        return None
+    t = obj.type
+    if not (pa.types.is_list(t) or pa.types.is_large_list(t) or pa.types.is_fixed_size_list(t)):
+        return None
+    lens = pc.fill_null(pc.list_value_length(obj), 0).to_numpy(zero_copy_only=False).astype(np.int64)
+    if obj.null_count:  # (a null list's slots leave with it)
+        obj = obj.filter(obj.is_valid())
+    offsets = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    return offsets, obj.flatten()
 
 
 def _label_array(obj, what: str):
@@ -565,12 +614,14 @@ def _check_groups(groups, m: int, n: int) -> _Groups:
     if not isinstance(groups, (tuple, list)) or len(groups) != 2:
         raise TypeError("groups must be a pair (left_labels, right_labels)")
     right_original = groups[1]
-    left, _ = _label_array(groups[0], "left")
+    probes = _probe_lists(groups[0])  # a list of labels per row: probed search
+    left, _ = _label_array(groups[0] if probes is None else probes[1], "left")
     right, right_arrow = _label_array(groups[1], "right")
     if left.type != right.type:
         raise TypeError(f"groups labels must have one type, got {left.type} (left) and {right.type} (right)")
-    if len(left) != m:
-        raise ValueError(f"left labels have {len(left)} rows, the queries have {m}")
+    if (len(left) if probes is None else probes[0].size - 1) != m:
+        raise ValueError(f"left labels have {len(left) if probes is None else probes[0].size - 1} rows, "
+                         f"the queries have {m}")
     if len(right) != n:
         raise ValueError(f"right labels have {len(right)} rows, the corpus has {n}")
     enc = right.dictionary_encode()
@@ -579,7 +630,8 @@ def _check_groups(groups, m: int, n: int) -> _Groups:
     qlabels = pc.fill_null(pc.cast(pc.index_in(left, value_set=enc.dictionary), pa.uint32()), none)
     qlabels = qlabels.to_numpy(zero_copy_only=False)
     return _Groups(np.ascontiguousarray(qlabels, dtype=np.uint32), np.ascontiguousarray(clabels, dtype=np.uint32),
-                   len(enc.dictionary), _persistent_key(right_original, right_arrow), right_arrow)
+                   len(enc.dictionary), _persistent_key(right_original, right_arrow), right_arrow,
+                   None if probes is None else probes[0])
 
 
 def _cached_partition(parent, parent_key, grp: _Groups, c: np.ndarray, compute: str):
@@ -607,12 +659,10 @@ def _cached_partition(parent, parent_key, grp: _Groups, c: np.ndarray, compute: 
         return dc.acquire(), False
 
 
-def _topk_grouped(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, compute: str):
-    """(idx (m, kk), scores (m, kk), lens (m,)): row i's first lens[i] slots
-    are its top-kk among the corpus rows of its label, indices numbering c.  On
-    the device from a partitioned handle of the cached corpus when there is
-    one (one GPU, f32 or f64 rows); else the host fallback: one uncached
-    search per distinct label on that label's rows, mapped back."""
+def _partitioned_handle(c, original, rv, grp: _Groups, compute: str):
+    """(an ACQUIRED partitioned DeviceCorpus for ``grp``'s corpus labels,
+    transient), or (None, False): no cacheable parent, several devices, bf16
+    compute, a sharded parent, or a handle that does not fit."""
     dc, transient = None, False
     if len(_native.get_devices()) <= 1 and compute != "bf16" and grp.sizes.sum() > 0:
         parent_key = _corpus_key(original, rv, c, compute)
@@ -623,6 +673,81 @@ def _topk_grouped(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, com
                     dc, transient = _cached_partition(parent, parent_key, grp, c, compute)
             finally:
                 parent.release()
+    return dc, transient
+
+
+_PROBED_MAX_K = 128  # pmm_topk_f32_probed's list length (the grouped kernel's)
+
+
+def _merge_probed(cand_row, cand_id, cand_sc, m: int, kk: int, euclidean: bool, dtype):
+    """Per query row the best kk of its candidates (flat arrays: row, corpus
+    row, score) under the library's order -- best score first, NaN last, equal
+    scores to the lower corpus row -- as (idx (m, kk), scores, lens)."""
+    idx = np.full((m, kk), 0xFFFFFFFF, dtype=np.uint32)
+    sc = np.zeros((m, kk), dtype=dtype)
+    lens = np.zeros(m, dtype=np.uint32)
+    if cand_row.size == 0:
+        return idx, sc, lens
+    nan = np.isnan(cand_sc)
+    rank = np.where(nan, 0, cand_sc if euclidean else -cand_sc)  # ascending = best first; the zeros tie
+    order = np.lexsort((cand_id, rank, nan, cand_row))
+    rows = cand_row[order]
+    start = np.searchsorted(rows, np.arange(m))
+    pos = np.arange(rows.size) - start[rows]
+    take = pos < kk
+    idx[rows[take], pos[take]] = cand_id[order][take]
+    sc[rows[take], pos[take]] = cand_sc[order][take]
+    lens[:] = np.minimum(np.bincount(rows, minlength=m), kk)
+    return idx, sc, lens
+
+
+def _topk_probed(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, compute: str):
+    """(idx (m, kk), scores (m, kk), lens (m,)): row i's first lens[i] slots
+    are its top-kk among the corpus rows of ALL its labels, indices numbering
+    c, ties to the lower corpus row.  On the device in one call on the
+    partitioned handle ``groups=`` caches (f32 rows, kk <= 128); else on the
+    host: one uncached search per distinct label for the rows that probe it
+    and a per-row merge by (score, corpus row) -- the same bits for f32."""
+    dc, transient = None, False
+    if q.dtype == np.float32 and kk <= _PROBED_MAX_K:
+        dc, transient = _partitioned_handle(c, original, rv, grp, compute)
+    if dc is not None:
+        try:
+            idx, sc, lens = dc.topk_probed(q, grp.probe_offsets, grp.qlabels, kk, metric_id)
+            if not transient:
+                _reaccount_cache(dc)
+        finally:
+            dc.release()
+            if transient:
+                dc.close()
+        return idx, sc, lens
+    m = q.shape[0]
+    mode = _native.COMPUTE_BF16 if compute == "bf16" else _native.COMPUTE_F32
+    pairs = grp.probe_pairs()
+    cr, ci, cs = [np.zeros(0, np.int64)], [np.zeros(0, np.uint32)], [np.zeros(0, q.dtype)]
+    cuts = np.flatnonzero(np.diff(pairs[:, 0])) + 1 if pairs.size else np.zeros(0, np.int64)
+    for part in np.split(pairs, cuts) if pairs.size else []:
+        ids = np.flatnonzero(grp.clabels == part[0, 0]).astype(np.uint32)
+        rows = part[:, 1]
+        kg = min(kk, int(ids.size))
+        gi, gs = _native.topk_host(np.ascontiguousarray(q[rows]), np.ascontiguousarray(c[ids]), kg, metric_id,
+                                   compute=mode)
+        cr.append(np.repeat(rows, kg))
+        ci.append(ids[gi].reshape(-1))
+        cs.append(np.asarray(gs, dtype=q.dtype).reshape(-1))
+    return _merge_probed(np.concatenate(cr), np.concatenate(ci), np.concatenate(cs), m, kk,
+                         metric_id == _native.METRIC_EUCLIDEAN, q.dtype)
+
+
+def _topk_grouped(q, c, original, rv, grp: _Groups, kk: int, metric_id: int, compute: str):
+    """(idx (m, kk), scores (m, kk), lens (m,)): row i's first lens[i] slots
+    are its top-kk among the corpus rows of its label, indices numbering c.  On
+    the device from a partitioned handle of the cached corpus when there is
+    one (one GPU, f32 or f64 rows); else the host fallback: one uncached
+    search per distinct label on that label's rows, mapped back."""
+    if grp.probe_offsets is not None:
+        return _topk_probed(q, c, original, rv, grp, kk, metric_id, compute)
+    dc, transient = _partitioned_handle(c, original, rv, grp, compute)
     if dc is not None:
         try:
             idx, sc, lens = dc.topk_grouped(q, grp.qlabels, kk, metric_id)
@@ -885,7 +1010,12 @@ def _topk(left, right, k, metric, compute="f32", subset=None, groups=None, candi
     row is searched only among the corpus rows with its own label; a null label
     on either side matches nothing.  The lists are ragged: row i holds
     min(k, corpus rows of its label) entries, none when the corpus has no such
-    label.  Not together with ``subset``.
+    label.  Not together with ``subset``.  ``left_labels`` holding one LIST of
+    labels per row (an Arrow List / LargeList / FixedSizeList of the right
+    side's label type, or a 2-D integer matrix) runs probed search: the row is
+    searched in the union of its labels' corpus rows, ties to the lower corpus
+    row; a null element or an unseen label is skipped, a null or empty list
+    gives an empty result.
     candidates (an extension): one list of corpus row ids per row of ``left``
     -- a Series or Arrow List / LargeList of any integer type (a null list is
     empty), or a pair ``(offsets, ids)`` of numpy arrays.  Every query row is
