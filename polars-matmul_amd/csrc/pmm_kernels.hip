@@ -2494,13 +2494,18 @@ hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int
   return hipGetLastError();
 }
 
-// Exact finish, first half: one workgroup per query row (staged in LDS, read
-// as broadcasts).  A candidate's corpus row is gathered by one thread (16-byte
-// loads, 128 bytes in flight per lane) and scored by the f32 path's arithmetic
-// -- the fmaf chain over the padded K in natural order from 0, exact_score on
-// the reference-order norms: seed_lds_block's, bit for bit the fused kernel's
-// -- and its composite replaces the approximate one in place.  merge_kernel
-// then selects and orders the exact top-k as for the unscreened kernels.
+// Exact finish, first half: one one-wave workgroup per query row (staged in
+// LDS, read as broadcasts).  The wave gathers the listed candidates' corpus
+// rows together, kRescoreRows rows at a time and one 128-byte line of each
+// row per step: eight consecutive lanes load one line with 16-byte loads, so
+// a load instruction covers eight whole lines and every line is fetched once;
+// the loads of the next kRescoreAhead steps wait in registers while the
+// current step's lines lie in an LDS tile.  Lane r < kRescoreRows scores row
+// r of the group from the tile by the f32 path's arithmetic -- one fmaf chain
+// over the padded K in natural order from 0, exact_score on the
+// reference-order norms: seed_lds_block's, bit for bit the fused kernel's --
+// and its composite replaces the approximate one in place.  merge_kernel then
+// selects and orders the exact top-k as for the unscreened kernels.
 //
 // The kernel's time is the rows it gathers (whole rows from a buffer far
 // larger than the caches), so it gathers in two phases.  With T1 = (the row's
@@ -2523,18 +2528,32 @@ hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int
 // surviving entry gets the composite a single pass gives it, so the merged
 // lists are the same bits.
 //
-// Each phase first lists its entries in LDS and then scores the list with
-// consecutive threads, so the gathers run on full waves though the entries are
-// scattered over the segments.  A list that outgrows kRescoreList is scored in
-// several rounds (a crowded band; at most total / kRescoreList + 1 of them).
-// Until the end a scored entry is told from an approximate one by its index
-// part, written as col instead of ~col: columns are below N < 2^31, so bit 31
-// of an approximate entry's low word is set and a scored one's is clear; a
-// last walk over the entries restores ~col.  (A scored entry is never 0, the empty
-// mark: a kept row's exact score is not NaN.)  Rows whose result is discarded
-// (overflowed, unsafe, padding) take the same path: every index stays inside
-// the counted part of a segment and every loop has a bound fixed beforehand.
-constexpr int kRescoreList = 512;  // >= k (launch_screen_rescore checks)
+// Each phase first lists its entries in LDS (offset and column) and then
+// scores the list in groups, so the gathers run on full waves though the
+// entries are scattered over the segments.  A list that outgrows kRescoreList
+// is scored in several rounds (a crowded band; at most total / kRescoreList +
+// 1 of them).  While a later listing walk still has to pass over it, a scored
+// entry is told from an approximate one by its index part, written as col
+// instead of ~col: columns are below N < 2^31, so bit 31 of an approximate
+// entry's low word is set and a scored one's is clear.  That holds for phase
+// 1's k entries and for a round that another round follows; the last round
+// writes ~col at once.  Phase 1's entries get ~col back at the end from their
+// offsets, kept in registers (at most kRescoreP1 per lane); only a row that needed several
+// rounds walks over all its entries for that.  (A scored entry is never 0,
+// the empty mark: a kept row's exact score is not NaN.)  Rows whose result is
+// discarded (overflowed, unsafe, padding) take the same path: every index
+// stays inside the counted part of a segment and every loop has a bound fixed
+// beforehand.
+constexpr int kRescoreList = 256;   // >= k (launch_screen_rescore checks)
+constexpr int kRescoreThreads = 64; // one wave
+constexpr int kRescoreRows = 16;    // rows per group: lanes that run a chain
+constexpr int kRescoreChunk = 32;   // floats of a row per step: one 128-byte line
+constexpr int kRescoreStride = kRescoreChunk + 4;  // tile row, floats: + 16 bytes, the chains' 16-byte reads
+                                                   // of 16 rows then fall into different banks
+constexpr int kRescoreAhead = 2;    // steps loaded ahead: 2 x 2 KiB in flight per wave
+constexpr int kRescoreP1 = (kRescoreList + kRescoreThreads - 1) / kRescoreThreads;  // phase-1 offsets per lane
+static_assert(kRescoreRows * (kRescoreChunk / 4) == 2 * kRescoreThreads, "two 16-byte loads per lane and step");
+static_assert(2 * kRescoreList >= 256, "the selection's histogram lies in the lists' storage");
 
 // f(p, *p) for every counted entry of the row this thread owns (entry i of a
 // segment: thread i mod blockDim).  segs: the row's non-empty segments in LDS,
@@ -2561,15 +2580,24 @@ __device__ __forceinline__ void rescore_each_entry(const ScreenFinishArgs &a, u6
   }
 }
 
-// (8 waves per SIMD, 64 registers: the gathers need the waves in flight)
-__global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs a) {
+// One step's loads of a lane: 16 bytes of the step's line of rows lane >> 3
+// and (lane >> 3) + 8 of the group, piece lane & 7.
+struct RescoreLoads {
+  f32x4 v[2];
+};
+
+// (5 waves per SIMD: 88 registers without scratch -- at 8 waves, 64 registers, 58
+// are spilled -- and the 7.5 KB of LDS at D = 768 allow 21 workgroups per CU)
+__global__ __launch_bounds__(kRescoreThreads, 5) void screen_rescore_kernel(ScreenFinishArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ __attribute__((aligned(16))) unsigned hist[256];
-  __shared__ unsigned list[kRescoreList];
+  // phase 0's histogram, then the phases' lists (offset from base | column)
+  __shared__ __attribute__((aligned(16))) unsigned lbuf[2 * kRescoreList];
+  __shared__ __attribute__((aligned(16))) float tile[kRescoreRows * kRescoreStride];
   __shared__ unsigned res[4], ln, emin;
+  unsigned *hist = lbuf, *loff = lbuf, *lcol = lbuf + kRescoreList;
   float *qs = (float *)smem;
   unsigned *segs = (unsigned *)(qs + a.dp);  // S words
-  const int tid = threadIdx.x, nt = blockDim.x;
+  const int tid = threadIdx.x, nt = kRescoreThreads;
   const int row = (int)blockIdx.x;
   const float *qr = a.q + (int64_t)row * a.ldq;
   for (int i = 4 * tid; i < a.dp; i += 4 * nt) *(f32x4 *)(qs + i) = *(const f32x4 *)(qr + i);
@@ -2593,12 +2621,12 @@ __global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs
   };
   // Phase 0.  P, the k-th largest live composite, built from the top byte
   // down: per round a 256-bin histogram of the live entries that share the
-  // prefix so far, then the first wave finds the bin that holds the rank
-  // (bins 4 lane .. 4 lane + 3 per lane, a suffix sum across lanes).  `need`
-  // is the rank left inside the prefix; once the chosen bin holds exactly
-  // `need` entries the prefix (low bits zero) already has exactly k entries at
-  // or above it, and the rounds end -- for distinct score keys within the
-  // first four.  Fewer than k live entries: no bin is chosen (n_r tells).
+  // prefix so far, then the wave finds the bin that holds the rank (bins
+  // 4 lane .. 4 lane + 3 per lane, a suffix sum across lanes).  `need` is the
+  // rank left inside the prefix; once the chosen bin holds exactly `need`
+  // entries the prefix (low bits zero) already has exactly k entries at or
+  // above it, and the rounds end -- for distinct score keys within the first
+  // four.  Fewer than k live entries: no bin is chosen (n_r tells).
   u64 P = 0ull;
   unsigned n_r = 0u, need = (unsigned)a.k;
   for (int shift = 56; shift >= 0; shift -= 8) {
@@ -2607,7 +2635,7 @@ __global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs
         atomicAdd(&hist[(unsigned)(x >> shift) & 255u], 1u);
     });
     __syncthreads();
-    if (tid < 64) {
+    {
       const uint4 h = ((const uint4 *)hist)[tid];
       ((uint4 *)hist)[tid] = make_uint4(0u, 0u, 0u, 0u);
       const unsigned own = h.x + h.y + h.z + h.w;
@@ -2641,6 +2669,12 @@ __global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs
   // Phases 1 (x >= P) and 2 (x >= T2; it also empties the others): list the
   // approximate entries at or above the phase's bound, then score the list.
   const int max_rounds = (int)(((int64_t)a.S * a.capg + kRescoreList - 1) / kRescoreList) + 1;
+  const int nchunk = a.dp / kRescoreChunk;
+  const int lrow = tid >> 3, piece = (tid & 7) * 4;
+  unsigned p1off[kRescoreP1];  // phase 1's entries of this lane (~0: none)
+#pragma unroll
+  for (int j = 0; j < kRescoreP1; j++) p1off[j] = ~0u;
+  bool several = false;  // some list took several rounds
   unsigned done = 0u;
   for (int ph = n_r > (unsigned)a.k ? 1 : 2; ph <= 2; ph++) {
     const bool last = ph == 2;
@@ -2657,48 +2691,115 @@ __global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs
       rescore_each_entry(a, base, segs, nseg, [&](u64 *p, u64 x) __attribute__((always_inline)) {
         if (x == 0ull) return;
         const uint32_t lw = (uint32_t)x;
-        if (!(lw & 0x80000000u)) return;  // scored in an earlier round
+        if (!(lw & 0x80000000u)) return;  // scored in phase 1 or an earlier round
         if (x < thr || !live(x)) {
           if (last) *p = 0ull;
           return;
         }
         const unsigned pos = atomicAdd(&ln, 1u);
-        if (pos < (unsigned)kRescoreList) list[pos] = (unsigned)(p - base);
+        if (pos < (unsigned)kRescoreList) loff[pos] = (unsigned)(p - base), lcol[pos] = ~lw;
       });
       __syncthreads();
       const unsigned n = ln;
       const bool more = n > (unsigned)kRescoreList;
       const int cnt = more ? kRescoreList : (int)n;
-      for (int t = tid; t < cnt; t += nt) {
-        u64 *p = base + list[t];
-        const uint32_t col = ~(uint32_t)*p;
-        const float *cr = a.c + (int64_t)col * a.ldc;
-        float acc = 0.0f;
-        for (int k0 = 0; k0 < a.dp; k0 += 32) {
-          f32x4 v[8];
+      several = several || more;
+      // what a scored entry's index part says: only the last round of all
+      // writes the final form
+      const bool marked = !last || more;
+      if (!last) {
 #pragma unroll
-          for (int j = 0; j < 8; j++) v[j] = *(const f32x4 *)(cr + k0 + 4 * j);
+        for (int j = 0; j < kRescoreP1; j++) {
+          const int t = tid + j * kRescoreThreads;
+          p1off[j] = t < cnt ? loff[t] : ~0u;
+        }
+      }
+      // The list in groups of kRescoreRows rows, every group in nchunk steps
+      // of one line per row; the steps of all groups form one sequence, so the
+      // loads run kRescoreAhead steps ahead across the groups' ends too.
+      const int nsteps = ((cnt + kRescoreRows - 1) / kRescoreRows) * nchunk;
+      // loading side: group (its first list position), step within it, this
+      // lane's two rows
+      int lg = 0, lc = 0;
+      const float *rp0 = a.c, *rp1 = a.c;
+      bool lv0 = false, lv1 = false;
+      auto issue = [&](RescoreLoads &x, int s) __attribute__((always_inline)) {
+        if (s >= nsteps) return;  // (the same for every thread)
+        if (lc == 0) {
+          const int t0 = lg + lrow, t1 = t0 + 8;
+          lv0 = t0 < cnt;
+          lv1 = t1 < cnt;
+          if (lv0) rp0 = a.c + (int64_t)lcol[t0] * a.ldc + piece;
+          if (lv1) rp1 = a.c + (int64_t)lcol[t1] * a.ldc + piece;
+        }
+        if (lv0) x.v[0] = *(const f32x4 *)(rp0 + lc * kRescoreChunk);
+        if (lv1) x.v[1] = *(const f32x4 *)(rp1 + lc * kRescoreChunk);
+        if (++lc == nchunk) lc = 0, lg += kRescoreRows;
+      };
+      // scoring side: group, step within it, the chain of lane < kRescoreRows
+      int sg = 0, sc = 0;
+      float acc = 0.0f, cnv = 0.0f;
+      auto score = [&](const RescoreLoads &x) __attribute__((always_inline)) {
+        if (sg + lrow < cnt) *(f32x4 *)(tile + lrow * kRescoreStride + piece) = x.v[0];
+        if (sg + lrow + 8 < cnt) *(f32x4 *)(tile + (lrow + 8) * kRescoreStride + piece) = x.v[1];
+        __syncthreads();
+        const int t = sg + tid;
+        if (tid < kRescoreRows && t < cnt) {
+          if (sc == 0) acc = 0.0f, cnv = a.cn[lcol[t]];
+          const float *tr = tile + tid * kRescoreStride;
+          const float *qk = qs + sc * kRescoreChunk;
 #pragma unroll
-          for (int j = 0; j < 8; j++) {
-            const f32x4 q4 = *(const f32x4 *)(qs + k0 + 4 * j);
-            acc = fmaf(q4[0], v[j][0], acc);
-            acc = fmaf(q4[1], v[j][1], acc);
-            acc = fmaf(q4[2], v[j][2], acc);
-            acc = fmaf(q4[3], v[j][3], acc);
+          for (int j = 0; j < kRescoreChunk / 4; j++) {
+            const f32x4 v = *(const f32x4 *)(tr + 4 * j);
+            const f32x4 q4 = *(const f32x4 *)(qk + 4 * j);
+            acc = fmaf(q4[0], v[0], acc);
+            acc = fmaf(q4[1], v[1], acc);
+            acc = fmaf(q4[2], v[2], acc);
+            acc = fmaf(q4[3], v[3], acc);
+          }
+          if (sc == nchunk - 1) {
+            const uint32_t col = lcol[t];
+            const uint32_t key = okey32(exact_score<kMetricCosine>(acc, qv, cnv));
+            if (!last) atomicMin(&emin, key);
+            base[loff[t]] = ((u64)key << 32) | (u64)(marked ? col : ~col);
+            done++;
           }
         }
-        const uint32_t key = okey32(exact_score<kMetricCosine>(acc, qv, a.cn[col]));
-        if (!last) atomicMin(&emin, key);
-        *p = ((u64)key << 32) | (u64)col;
-        done++;
+        __syncthreads();  // (the tile is free again)
+        if (++sc == nchunk) sc = 0, sg += kRescoreRows;
+      };
+      RescoreLoads ring[kRescoreAhead] = {};
+#pragma unroll
+      for (int j = 0; j < kRescoreAhead; j++) issue(ring[j], j);
+      for (int s = 0; s < nsteps; s += kRescoreAhead) {
+#pragma unroll
+        for (int j = 0; j < kRescoreAhead; j++) {
+          if (s + j < nsteps) {  // (the same for every thread)
+            const RescoreLoads cur = ring[j];
+            issue(ring[j], s + j + kRescoreAhead);
+            score(cur);
+          }
+        }
       }
       if (!more) break;
     }
   }
+  // Phase 1's entries, and every entry of a row whose lists took several
+  // rounds, still carry col: back to ~col.
   __syncthreads();
-  rescore_each_entry(a, base, segs, nseg, [&](u64 *p, u64 x) __attribute__((always_inline)) {
+  auto restore = [&](u64 *p, u64 x) __attribute__((always_inline)) {
     if (x != 0ull && !((uint32_t)x & 0x80000000u)) *p = (x & 0xFFFFFFFF00000000ull) | (u64)(~(uint32_t)x);
-  });
+  };
+  if (several) {
+    rescore_each_entry(a, base, segs, nseg, restore);
+  } else {
+    u64 x[kRescoreP1];
+#pragma unroll
+    for (int j = 0; j < kRescoreP1; j++) x[j] = p1off[j] != ~0u ? base[p1off[j]] : 0ull;
+#pragma unroll
+    for (int j = 0; j < kRescoreP1; j++)
+      if (p1off[j] != ~0u) restore(base + p1off[j], x[j]);
+  }
   if (a.stat) {  // (diagnostics: PMM_SCREEN_DEBUG)
     __syncthreads();
     if (tid == 0) ln = 0u;
@@ -2714,19 +2815,11 @@ __global__ __launch_bounds__(256, 8) void screen_rescore_kernel(ScreenFinishArgs
 }
 hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;
-  if (a.dp % 32 != 0 || a.dp > 4096 || a.ldq % 4 != 0 || a.ldc % 4 != 0 || a.ldq < a.dp || a.ldc < a.dp ||
-      (((uintptr_t)a.q | (uintptr_t)a.c) & 15) || a.k < 1 || a.k > kRescoreList || a.capg > 1023 ||
+  if (a.dp % kRescoreChunk != 0 || a.dp > 4096 || a.ldq % 4 != 0 || a.ldc % 4 != 0 || a.ldq < a.dp ||
+      a.ldc < a.dp || (((uintptr_t)a.q | (uintptr_t)a.c) & 15) || a.k < 1 || a.k > kRescoreList || a.capg > 1023 ||
       ((int64_t)a.dp + a.S) * 4 > 64 * 1024)  // (the row and its segment list in LDS)
     return hipErrorInvalidValue;
-  // PMM_RESCORE_BLOCK (experiment knob, read per call): threads per row.  One
-  // wave measured best at c3 (re-score 19.5 ms against 21.4 at 128 and 21.5 at
-  // 256, profiles/rescore_band/README.md): more rows in flight per CU.
-  int nt = 64;
-  if (const char *e = getenv("PMM_RESCORE_BLOCK")) {
-    const int v = atoi(e);
-    if (v == 64 || v == 128 || v == 256) nt = v;
-  }
-  screen_rescore_kernel<<<(unsigned)a.M, nt, ((size_t)a.dp + a.S) * 4, s>>>(a);
+  screen_rescore_kernel<<<(unsigned)a.M, kRescoreThreads, ((size_t)a.dp + a.S) * 4, s>>>(a);
   return hipGetLastError();
 }
 
