@@ -149,8 +149,11 @@ int pmm_topk_f32_ex(const float *q, int64_t m, const float *c, int64_t n, int64_
 int pmm_topk_f64(const double *q, int64_t m, const double *c, int64_t n, int64_t d, int64_t k,
                  int metric, uint32_t *out_idx, double *out_score);
 
-/* The same f64 top-k on device rows (row strides >= roundup(d, 16), zero-
- * padded, 16-byte-aligned bases) on the caller's stream; out_idx / out_score
+/* The same f64 top-k on device rows (row strides >= roundup(d, 16) and
+ * multiples of 2 -- the GEMM stages rows with 16-byte loads; an odd stride is
+ * PMM_ERR_ARG -- zero-padded, 16-byte-aligned bases) on the caller's stream,
+ * in the thread's cached buffer (see "Device-resident entry points" for what
+ * that means for streams); out_idx / out_score
  * are device buffers of m*k entries, indices offset by index_base.  k <=
  * 1024 and an m x n score matrix of 256 MB or more: fused (f64 MFMA GEMM whose
  * epilogue appends each element that beats its row's running k-th to a
@@ -187,6 +190,44 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
  * caller's HIP stream (NULL = the HIP default stream, as in the HIP API), no
  * host synchronisation.
  * Used by the benchmark and the multi-GPU (corpus-sharded) path.
+ *
+ * The stream.  Every kernel, fill and copy of an entry goes to `stream` and
+ * nowhere else, so the entry reads what the stream produced before the call
+ * and its outputs are ready for whatever the caller enqueues behind it.  The
+ * entry returns with the work queued, except in the places below, where the
+ * host needs a word from the device and waits for the stream (the results are
+ * the same; only the host's progress differs):
+ *   - pmm_topk_f32_device on the screened route (f32 cosine with
+ *     PMM_F32_SCREEN in force): it reads back the screen's scalars -- the rows
+ *     to re-run, an unsafe corpus -- before it decides on the f32 re-run;
+ *   - pmm_topk_f64_device on the fused scan: its overflow flag;
+ *   - pmm_topk_i8_device and pmm_topk_bits_device: the count of rows whose
+ *     buffer overflowed, and again after a re-run, whose allocation is freed;
+ *   - workspace = NULL (and pmm_topk_f64_device, which has no workspace
+ *     argument) when the thread's cached buffer has to grow: the old buffer is
+ *     freed once its last use and the stream have finished.
+ * Not synchronising: the fused, materialised and global-sort routes of
+ * pmm_topk_f32_device, every route of pmm_topk_bf16_device (the widened one
+ * included), the materialised route of pmm_topk_f64_device, pmm_norms_*,
+ * pmm_round_bf16_device, pmm_screen_prepare_device, pmm_pack_sign_device and
+ * the three merge entries.  (pmm_timing_enable does not change this.)
+ *   The thread's cached buffer is shared by all streams the thread passes: a
+ * use on another stream than the last one waits, on the device, for an event
+ * recorded at the end of that use, and so does a host entry or a handle call
+ * of the same thread.  Two calls on two streams that both pass workspace =
+ * NULL therefore run one after the other; give each its own workspace to
+ * overlap them.
+ *
+ * Alignment.  Operand bases are 16-byte aligned and rows start 16-byte
+ * aligned: strides are multiples of 4 (f32), 8 (bf16), 2 (f64) or 16 (int8
+ * and bit rows) elements, at least the padded width.  The rows of the norms,
+ * rounding, preparing and sign-packing entries need their element's alignment
+ * only.  out_idx and out_score need their element's alignment.  A caller's
+ * workspace for the f32 and bf16 entries is 16-byte aligned (its regions
+ * start at multiples of 256 bytes from it and hold 64-bit keys, 16-byte fills
+ * and staged rows), for the int8 and bit entries 256-byte aligned.  What an
+ * entry cannot take it refuses with PMM_ERR_ARG before it enqueues anything,
+ * naming the value; it never runs a misaligned access.
  * ------------------------------------------------------------------------- */
 
 /* Scratch bytes pmm_topk_f32_device (compute F32) or pmm_topk_bf16_device
@@ -214,7 +255,9 @@ int pmm_topk_merge_bytes(const void *workspace, int64_t m, int64_t n, int64_t d,
  * returned corpus index (global index of corpus row 0 of this shard).  For
  * k <= 1024, k may exceed n (a small shard): slots past n are empty (index
  * 0xFFFFFFFF, score NaN).  workspace may be NULL (a per-thread cached buffer
- * is used). */
+ * is used); a caller's workspace holds at least pmm_topk_workspace_bytes at a
+ * 16-byte-aligned address (less of either: PMM_ERR_ARG; here and for
+ * pmm_topk_bf16_device). */
 int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, int64_t ldc,
                         int64_t n, int64_t d, int64_t k, int metric, int compute,
                         uint32_t index_base, uint32_t *out_idx, float *out_score,

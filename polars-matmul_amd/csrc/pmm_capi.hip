@@ -746,6 +746,11 @@ int acquire_workspace(void *ws, size_t ws_bytes, size_t need, int dev, hipStream
   out.s = s;
   if (!ws) {
     if (int rc = arena(dev, s, need, &ws)) return rc;
+  } else if ((uintptr_t)ws & 15) {
+    // (the regions start at multiples of 256 from ws and hold 64-bit keys that
+    // are updated atomically, 16-byte fills and the rows the kernels stage with
+    // 16-byte loads)
+    return fail(PMM_ERR_ARG, "the workspace needs a 16-byte-aligned address (got %p)", ws);
   } else if (ws_bytes < need) {
     return fail(PMM_ERR_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
   }
@@ -4064,10 +4069,11 @@ int pmm_topk_f64_device(const double *q, int64_t ldq, int64_t m, const double *c
   if (n == 0) return fail(PMM_ERR_ARG, "Empty series");
   if ((rc = need_buffers(q, c, out_idx, out_score))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_F64, d);
-  if (d == 0 || ldq < dp || ldc < dp || ((uintptr_t)q & 15) || ((uintptr_t)c & 15))
+  // (f64_tile stages the rows with 16-byte loads: every row must start 16-byte aligned)
+  if (d == 0 || ldq < dp || ldc < dp || ldq % 2 != 0 || ldc % 2 != 0 || ((uintptr_t)q & 15) || ((uintptr_t)c & 15))
     return fail(PMM_ERR_ARG,
-                "device f64 inputs need row strides >= roundup(d, 16) (zero-padded) and 16-byte-aligned "
-                "bases (d=%lld ldq=%lld ldc=%lld)",
+                "device f64 inputs need row strides >= roundup(d, 16) (zero-padded), multiples of 2, and "
+                "16-byte-aligned bases (d=%lld ldq=%lld ldc=%lld)",
                 (long long)d, (long long)ldq, (long long)ldc);
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
@@ -5621,8 +5627,8 @@ int pmm_topk_i8_device(const int8_t *q, int64_t ldq, int64_t m, const int8_t *c,
   void *w = workspace;
   if (w) {
     if (workspace_bytes < route.total || ((uintptr_t)w & 255))
-      return fail(PMM_ERR_ARG, "the int8 workspace needs %zu bytes at a 256-byte-aligned address (got %zu): size it "
-                               "with pmm_topk_i8_workspace_bytes", route.total, workspace_bytes);
+      return fail(PMM_ERR_ARG, "the int8 workspace needs %zu bytes at a 256-byte-aligned address (got %zu at %p): "
+                               "size it with pmm_topk_i8_workspace_bytes", route.total, workspace_bytes, w);
   } else if ((rc = arena(dev, s, route.total, &w))) {
     return rc;
   }
@@ -5720,8 +5726,8 @@ int pmm_topk_bits_device(const uint8_t *q, int64_t ldq, int64_t m, const uint8_t
   void *ws = workspace;
   if (ws) {
     if (workspace_bytes < route.total || ((uintptr_t)ws & 255))
-      return fail(PMM_ERR_ARG, "the bit-row workspace needs %zu bytes at a 256-byte-aligned address (got %zu): size it "
-                               "with pmm_topk_bits_workspace_bytes", route.total, workspace_bytes);
+      return fail(PMM_ERR_ARG, "the bit-row workspace needs %zu bytes at a 256-byte-aligned address (got %zu at %p): "
+                               "size it with pmm_topk_bits_workspace_bytes", route.total, workspace_bytes, ws);
   } else if ((rc = arena(dev, s, route.total, &ws))) {
     return rc;
   }
