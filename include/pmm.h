@@ -228,6 +228,21 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
  * and staged rows), for the int8 and bit entries 256-byte aligned.  What an
  * entry cannot take it refuses with PMM_ERR_ARG before it enqueues anything,
  * naming the value; it never runs a misaligned access.
+ *
+ * Largest row stride.  pmm_topk_f32_device and pmm_topk_bf16_device take ldq
+ * and ldc of at most 8388592 bytes (2097148 floats, 4194296 bf16 elements):
+ * their kernels read up to 256 rows (a corpus tile, a wave's query rows)
+ * through one buffer descriptor of 2^31 - 1 bytes with 32-bit offsets, and a
+ * read past a descriptor returns zeros.  A longer stride is PMM_ERR_ARG before
+ * anything is enqueued; the message names the stride and this limit.  A
+ * threshold seed reads its whole sample through one descriptor: where
+ * sample rows x ldc pass 2^31 - 1 bytes the call runs unseeded, with the same
+ * lists.  pmm_topk_workspace_bytes takes no stride and promises no route the
+ * entry then refuses.  The f64, int8 and bit top-k and the merges take any
+ * stride, and the norms, rounding, preparing and sign-packing entries any
+ * input stride, spans past 2^32 bytes included: they index with 64-bit
+ * products (tests/test_gpu_wide_strides.py; their output strides are not
+ * tested past 2^31 bytes).
  * ------------------------------------------------------------------------- */
 
 /* Scratch bytes pmm_topk_f32_device (compute F32) or pmm_topk_bf16_device

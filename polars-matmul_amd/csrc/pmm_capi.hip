@@ -43,6 +43,17 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
+// pmm_topk_f32_device / pmm_topk_bf16_device: a row stride of `ld` elements of `elem` bytes
+// against kMaxRowStrideBytes (pmm_internal.h), before anything is enqueued.
+int check_row_stride(const char *name, int64_t ld, int elem) {
+  if (ld <= kMaxRowStrideBytes / elem) return PMM_OK;
+  return fail(PMM_ERR_ARG,
+              "%s=%lld is a row stride above %lld bytes (%lld elements), the largest this entry takes: its "
+              "kernels address up to %d rows through one 2^31-byte buffer descriptor",
+              name, (long long)ld, (long long)kMaxRowStrideBytes, (long long)(kMaxRowStrideBytes / elem),
+              kDescRowsMax);
+}
+
 #define HIP_TRY(expr)                                                                   \
   do {                                                                                  \
     hipError_t e_ = (expr);                                                             \
@@ -785,6 +796,13 @@ hipError_t run_fused_f32(GemmF32Args a, const Plan &p, uint32_t index_base, uint
   }
 #endif
   {
+    // (a mark beside the launch's record: pmm_timing_read matches substrings,
+    // so the tile variant has a name of its own)
+    static const char *const kVariant[6] = {"f32_variant/0", "f32_variant/1", "f32_variant/2",
+                                            "f32_variant/3", "f32_variant/4", "f32_variant/5"};
+    if (p.variant >= 0 && p.variant < 6) Timed mark(kVariant[p.variant], s);
+  }
+  {
     Timed t("gemm_f32_topk", s);
     hipError_t e = launch_gemm_f32(a, p.variant, 0, p.grid, s);
     if (e != hipSuccess) return e;
@@ -1081,7 +1099,7 @@ int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const 
   const bool mostly_split = 2 * (int64_t)p.qb_full < (int64_t)p.QB;
   bool seed = (se ? atoi(se) != 0
                   : ((int64_t)p.tps * gemm_f32_bn(p.variant) < 8192 && n >= 4 * ns && mostly_split)) &&
-              ns >= k && ns < n && ns <= kSeedMaxNs && !keep_gthr &&
+              ns >= k && ns < n && ns <= kSeedMaxNs && !keep_gthr && seed_span_fits(ns, ldc, 4) &&
               (size_t)m * ns * 4 <= p.off_qn - p.off_cand;
   GemmF32Args a = fused_args(m, n, dp, k, metric, p, w);
   a.q = q;
@@ -1096,6 +1114,11 @@ int topk_f32_fused(const Plan &p, const float *q, int64_t ldq, int64_t m, const 
                             !(((uintptr_t)q | (uintptr_t)c | (uintptr_t)w) & 15) && p.off_gthr % 16 == 0 &&
                             p.off_cnt % 16 == 0 && p.off_cand % 16 == 0 && !getenv("PMM_SEED_GEMM");
   if (one_prologue) {
+    {
+      // (a mark: which form of seed blocks the prologue takes)
+      static const char *const kForm[3] = {"seed_form/fmaf", "seed_form/lds", "seed_form/mfma"};
+      Timed mark(kForm[seeded_prologue_form(n, (int)dp, (int)ns)], s);
+    }
     Timed t("gemm_f32_seed", s);
     HIP_TRY(launch_seeded_prologue(q, ldq, (int)m, c, ldc, n, (int)d, (int)dp, (int)ns, (int)k, metric, qn, cn,
                                    !c_norms, a.gthr, w, p.off_gthr, w + p.off_cnt, p.off_cand - p.off_cnt, s));
@@ -1438,8 +1461,8 @@ int topk_bf16_native(const Plan &p, const uint16_t *q, int64_t ldq, int64_t m, c
       // the row's final k-th best: the main pass starts from it.
       const int seed_env = getenv("PMM_BF16_SEED") ? atoi(getenv("PMM_BF16_SEED")) : 1;  // (read per call: tests toggle it)
       int64_t ns = kSeedMaxNs;
-      if (const char *ne = getenv("PMM_SEED_NS")) ns = std::max<int64_t>(32, std::min<int64_t>(atoll(ne), 4096) / 32 * 32);
-      if (seed_env && p.variant == -2 && 4 * k <= ns && n >= 8 * ns &&
+      if (const char *ne = getenv("PMM_SEED_NS")) ns = std::max<int64_t>(32, std::min<int64_t>(atoll(ne), kBf16SeedMaxNs) / 32 * 32);
+      if (seed_env && p.variant == -2 && 4 * k <= ns && n >= 8 * ns && seed_span_fits(ns, ldc, 2) &&
           (size_t)m * ns * 4 <= p.off_qn - p.off_cand) {
         float *sample = (float *)a.cand;
         Timed t("seed_bf16", s);
@@ -1454,6 +1477,10 @@ int topk_bf16_native(const Plan &p, const uint16_t *q, int64_t ldq, int64_t m, c
       // bucketing into the candidate lists; rows it cannot prove exact are
       // re-run below
       float *sample = (float *)a.cand;
+      // (its guessed threshold needs the sample: no unseeded form)
+      if (!seed_span_fits(p.ff_ns, ldc, 2))
+        return fail(PMM_ERR_ARG, "ldc=%lld: the fire-and-forget kernel's %d-row sample does not fit one descriptor",
+                    (long long)ldc, p.ff_ns);
       {
         Timed t("seed_bf16", s);
         HIP_TRY(launch_seed_bf16_ws(a, sample, p.ff_ns, s));
@@ -3931,6 +3958,7 @@ int pmm_topk_f32_device(const float *q, int64_t ldq, int64_t m, const float *c, 
                 "device inputs need row strides >= roundup(d, 32) (zero-padded), multiples of 4, "
                 "16-byte-aligned bases (d=%lld ldq=%lld ldc=%lld)",
                 (long long)d, (long long)ldq, (long long)ldc);
+  if ((rc = check_row_stride("ldq", ldq, 4)) || (rc = check_row_stride("ldc", ldc, 4))) return rc;
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream
@@ -4020,6 +4048,7 @@ int pmm_topk_bf16_device(const uint16_t *q, int64_t ldq, int64_t m, const uint16
                 "bf16 device inputs need row strides >= roundup(d, 128) (zero-padded), multiples "
                 "of 8, 16-byte-aligned bases (d=%lld ldq=%lld ldc=%lld)",
                 (long long)d, (long long)ldq, (long long)ldc);
+  if ((rc = check_row_stride("ldq", ldq, 2)) || (rc = check_row_stride("ldc", ldc, 2))) return rc;
   int dev;
   if ((rc = ensure_device(&dev))) return rc;
   hipStream_t s = (hipStream_t)stream;  // NULL = the HIP default stream

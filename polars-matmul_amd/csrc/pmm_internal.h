@@ -323,6 +323,26 @@ hipError_t launch_merge(const MergeArgs &a, int loader, hipStream_t s);
 // Threshold seeding: gthr[row] = (k-th best composite of the row's ns
 // materialised scores S[row][0..ns)) - 1, one wave per row; ns <= kSeedMaxNs.
 constexpr int kSeedMaxNs = 1024;
+// Row strides of pmm_topk_f32_device and pmm_topk_bf16_device.  Their GEMMs and
+// threshold seeds read rows through buffer descriptors with 32-bit byte
+// offsets, and a descriptor's size ends at kDescMaxBytes -- a load past it
+// returns zeros, it does not fault.
+//   GEMMs: one descriptor spans a corpus tile (BN rows) or a wave's query
+// rows (32; 64 in the fire-and-forget kernel): at most kDescRowsMax rows
+// (static_asserts below and at the kernels).  A stride of at most
+// kMaxRowStrideBytes keeps such a span inside the size field and every offset
+// below 2^31; the entries refuse a longer stride.
+//   Seeds: one descriptor spans the sample's ns rows, more than a tile.  A
+// seed only raises the starting thresholds, so a call whose sample does not
+// fit one descriptor (seed_span_fits) runs unseeded: the same lists.
+constexpr int64_t kDescMaxBytes = 0x7FFFFFFFll;
+constexpr int kDescRowsMax = 256;
+constexpr int64_t kMaxRowStrideBytes = (kDescMaxBytes / kDescRowsMax) & ~15ll;  // 8388592: whole 16-byte pieces
+constexpr int kBf16SeedMaxNs = 4096;  // the bf16 seed's sample (default kSeedMaxNs; PMM_SEED_NS up to this)
+inline bool seed_span_fits(int64_t ns, int64_t ld, int elem) { return ns * ld * elem <= kDescMaxBytes; }
+// f32 seeded prologue: the form of its seed blocks for this sample (the
+// environment read per call): 0 fmaf chains, 1 LDS-staged, 2 MFMA
+int seeded_prologue_form(int64_t n, int dp, int ns);
 // The fused top-k's prologue with threshold seeding in one launch: the seed
 // (the sample's scores as fmaf chains, bit-identical to the fused kernel's,
 // with its own norms; writes every row's gthr), the query norms (and the
@@ -359,6 +379,9 @@ hipError_t launch_seed_bf16_ws(const GemmF32Args &a, float *S, int ns, hipStream
 // fire-and-forget against a static guessed threshold (pmm_bf16_ff_kernel.h):
 // 64 rows x D per wave, 32-column corpus tiles.  N < 2^26.
 constexpr int kBf16FfBM = 256, kBf16FfBN = 32;
+static_assert(kBf16BN <= kDescRowsMax && kBf16WsBN <= kDescRowsMax && kBf16FfBN <= kDescRowsMax &&
+                  kBf16FfBM / 4 <= kDescRowsMax,
+              "a bf16 kernel's descriptor spans one corpus tile or one wave's query rows");
 size_t gemm_bf16_ff_lds_bytes(int D);  // D = padded dimension; 0 if unsupported
 hipError_t launch_gemm_bf16_ff(const GemmF32Args &a, int grid, hipStream_t s);
 // Exact re-score and bucketing of the ff kernel's survivor regions into the

@@ -107,6 +107,8 @@ struct GemmShape {
   static constexpr int NBW = CSP ? NB / 2 : NB;     // 32-column blocks per wave
   static constexpr int BN = 32 * NB;                // corpus columns per tile
   static constexpr int BM = 32 * RG;                // query rows per workgroup
+  static constexpr int WROWS = 32;                  // query rows per wave: one descriptor
+  static_assert(BN <= kDescRowsMax && WROWS <= kDescRowsMax, "one descriptor per corpus tile and per wave's rows");
   static constexpr int RS = 32 * NW;                // per-wave row-state slots
   static constexpr int A_BYTES = RG * 4096;         // RG row groups x 32 rows x 128 B
   static constexpr int B_BYTES = BN * 128;          // BN rows x 128 B
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
     const int wrow0 = qb * G::BM + rg * 32;
     const int seg = CSP ? 2 * s + half : s;  // this wave's candidate segment
     const __amdgpu_buffer_rsrc_t ra =
-        make_rsrc(a.q + (int64_t)wrow0 * a.ldq, (int64_t)min(32, a.M - wrow0) * a.ldq * 4);
+        make_rsrc(a.q + (int64_t)wrow0 * a.ldq, (int64_t)min(G::WROWS, a.M - wrow0) * a.ldq * 4);
 
     // Per-lane row constants for the 16 accumulator rows this lane holds.
     if (lane < 32) {
@@ -1583,7 +1585,8 @@ struct PrologueArgs {
 namespace seedk {
 constexpr int KC = 32;               // K floats per ring chunk
 constexpr int NB = 4;                // ring chunks (NB - 1 in flight)
-constexpr int CHUNK = 256 * KC * 4;  // 256 columns: 32 KiB
+constexpr int COLS = 256;            // sample columns per seed block
+constexpr int CHUNK = COLS * KC * 4;  // 256 columns: 32 KiB
 constexpr int kLdsMaxDp = 1024;
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {
@@ -2155,6 +2158,16 @@ static hipError_t launch_prologue_t(const PrologueArgs &a, unsigned grid, hipStr
 // 19-20 us (bench events), c2 0.096 vs 0.097 (profiles/r5_c1/seed_ab.txt)
 #define PMM_SEED_MFMA_DEFAULT 1
 #endif
+// PMM_SEED_LDS=1 takes the LDS-staged seed blocks where they apply; MFMA seed
+// blocks (prologue_mfma_kernel) for a 256-column sample otherwise, PMM_SEED_MFMA
+// 0 / 1 forces the fmaf-chain blocks / the MFMA blocks (both read per call)
+int seeded_prologue_form(int64_t n, int dp, int ns) {
+  const char *le = getenv("PMM_SEED_LDS");
+  if (ns <= seedk::COLS && dp <= seedk::kLdsMaxDp && le && atoi(le) == 1) return 1;
+  const char *me = getenv("PMM_SEED_MFMA");
+  const bool mfma_ok = ns == seedm::NSM && dp <= seedm::kMaxDp && n >= seedm::NSM;
+  return (mfma_ok && (me ? atoi(me) != 0 : PMM_SEED_MFMA_DEFAULT != 0)) ? 2 : 0;
+}
 hipError_t launch_seeded_prologue(const float *q, int64_t ldq, int m, const float *c, int64_t ldc, int64_t n,
                                   int d, int dp, int ns, int k, int metric, float *qn, float *cn, bool corpus_norms,
                                   unsigned long long *gthr, void *z0, size_t z0_bytes, void *z1, size_t z1_bytes,
@@ -2194,14 +2207,10 @@ hipError_t launch_seeded_prologue(const float *q, int64_t ldq, int m, const floa
 #ifdef PMM_LAB
   a.ablate = getenv("PMM_PROLOGUE_ABLATE") ? atoi(getenv("PMM_PROLOGUE_ABLATE")) : 0;
 #endif
-  const char *le = getenv("PMM_SEED_LDS");
-  a.lds_seed = (ns <= 256 && dp <= seedk::kLdsMaxDp && le && atoi(le) == 1) ? 1 : 0;
+  const int form = seeded_prologue_form(n, dp, ns);
+  a.lds_seed = form == 1;
   const bool xf = metric != kMetricDot;
-  // MFMA seed blocks (prologue_mfma_kernel) for a 256-column sample; PMM_SEED_MFMA
-  // (read per call) 0 / 1 forces the fmaf-chain blocks / the MFMA blocks
-  const char *me = getenv("PMM_SEED_MFMA");
-  const bool mfma_ok = ns == seedm::NSM && dp <= seedm::kMaxDp && !a.lds_seed && n >= seedm::NSM;
-  a.mfma_seed = (mfma_ok && (me ? atoi(me) != 0 : PMM_SEED_MFMA_DEFAULT != 0)) ? 1 : 0;
+  a.mfma_seed = form == 2;
   if (a.mfma_seed) {
     a.sblocks = (unsigned)((m + seedm::RM - 1) / seedm::RM);
     constexpr int T = seedm::NT;

@@ -152,6 +152,10 @@ def topk_case(name, kind, m, n, d, k, metric=COS, knobs=None, blocks=False):
             idx, sc = oracle.topk(q.astype(wide), c.astype(wide), k, metric)
         return {"idx": np.asarray(idx).astype(np.uint32), "score": np.asarray(sc).astype(sdt)}
 
+    def nat():
+        """The binding the case calls: the product's, or a second library's (case.native)."""
+        return case.native or _native
+
     def call(p, o, ws, stream):
         (pq, ldq), (pc, ldc) = p["q"], p["c"]
         if kind == "f64":
@@ -160,18 +164,18 @@ def topk_case(name, kind, m, n, d, k, metric=COS, knobs=None, blocks=False):
             _native.topk_bits_device(pq, ldq, m, pc, ldc, n, d, k, o["idx"], o["score"], workspace=ws[0],
                                      workspace_bytes=ws[1], stream=stream)
         else:
-            fn = {"f32": _native.topk_device, "bf16": _native.topk_bf16_device, "i8": _native.topk_i8_device}[kind]
+            fn = {"f32": nat().topk_device, "bf16": nat().topk_bf16_device, "i8": nat().topk_i8_device}[kind]
             fn(pq, ldq, m, pc, ldc, n, d, k, metric, o["idx"], o["score"], workspace=ws[0], workspace_bytes=ws[1],
                stream=stream)
 
-    workspace = {"f32": lambda: _native.workspace_bytes(m, n, d, k, metric, F32),
-                 "bf16": lambda: _native.workspace_bytes(m, n, d, k, metric, BF16),
+    workspace = {"f32": lambda: nat().workspace_bytes(m, n, d, k, metric, F32),
+                 "bf16": lambda: nat().workspace_bytes(m, n, d, k, metric, BF16),
                  "i8": lambda: _native.i8_workspace_bytes(m, n, d, k, metric),
                  "bits": lambda: _native.bits_workspace_bytes(m, n, d, k), "f64": None}[kind]
     case = Case(name, kind, make, [Output("idx", np.uint32, (m, k), 4), Output("score", sdt, (m, k), soff)], call, truth,
                 knobs, workspace, blocks or kind in ("i8", "bits"), arena=kind == "f64",
                 compute={"f32": F32, "bf16": BF16}.get(kind))
-    case.shape = (m, n, d, k, metric)
+    case.shape, case.native = (m, n, d, k, metric), None
     return case
 
 
@@ -398,13 +402,33 @@ def apply_knobs(env, case):
         env.setenv("PMM_F32_SCREEN", "1")
 
 
-def place_operands(case, weak, filled=True):
+def place_wide(op, ld, whole=False):
+    """The operand at a row stride whose image no host holds: one device allocation filled on the
+    device with the poison, then the rows with their zero padding written through a strided view
+    from the tight host rows.  The last row ends at its padded width (a column slice of a wide
+    matrix), so the guard band starts right behind it; whole: the last row has its stride too."""
+    import torch
+
+    width = roundup(op.d, op.pad) * op.elem
+    assert ld * op.elem >= width
+    pl = Placed((op.rows - 1) * ld * op.elem + (ld * op.elem if whole else width), 0, fill=op.poison)
+    tight = np.zeros((op.rows, width), np.uint8)
+    tight[:, :op.d * op.elem] = op.data.view(np.uint8).reshape(op.rows, op.d * op.elem)
+    torch.as_strided(pl.view, (op.rows, width), (ld * op.elem, 1)).copy_(torch.from_numpy(tight))
+    return pl
+
+
+def place_operands(case, weak, filled=True, wide=None):
     """Operand name -> (Placed, row stride).  filled: the rows are there (a synchronous upload);
-    else every byte is the poison and the caller produces the rows."""
+    else every byte is the poison and the caller produces the rows.  wide: operand name -> row
+    stride, placed by place_wide."""
     import torch
 
     out = {}
     for op in case.operands:
+        if wide and op.name in wide:
+            out[op.name] = (place_wide(op, wide[op.name], getattr(case, "whole_rows", False)), wide[op.name])
+            continue
         ld = op.weak_ld if weak else op.tight_ld
         pl = Placed(op.nbytes(ld), op.weak_off if weak else 0, fill=op.poison)
         if filled:
@@ -445,14 +469,15 @@ def check_bands(case, ops, outs, ws, label):
         ws.check(f"{label} workspace")
 
 
-def run_case(case, weak=False, weak_operands=None, ws_off=None, arena=False, stream=0):
+def run_case(case, weak=False, weak_operands=None, ws_off=None, arena=False, stream=0, wide=None):
     """One synchronous call.  weak: operands and outputs at the weakest layout (weak_operands
     overrides it for the operands alone); ws_off: the workspace's offset from a 256-byte boundary
-    (default 16 when weak, for the entries that take it there); arena: workspace = NULL."""
+    (default 16 when weak, for the entries that take it there); arena: workspace = NULL; wide:
+    operand name -> row stride of the operands placed on the device (place_wide)."""
     import torch
 
     weak_ops = weak if weak_operands is None else weak_operands
-    ops, outs = place_operands(case, weak_ops), place_outputs(case, weak)
+    ops, outs = place_operands(case, weak_ops, wide=wide), place_outputs(case, weak)
     if ws_off is None:
         ws_off = 16 if weak and case.kind in ("f32", "bf16") else 0
     ws = None if arena else place_workspace(case, ws_off)
