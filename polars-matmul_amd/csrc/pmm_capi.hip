@@ -31,6 +31,23 @@ namespace {
 constexpr const char *kVersion = "0.1.4+mi355x.r1";
 constexpr size_t kMaterialiseBudget = size_t(2) << 30;  // bytes of score chunk (f64/large-k/matmul)
 
+// The budget of one call's score or result chunk: kMaterialiseBudget, which
+// PMM_MATERIALISE_BUDGET (bytes, per call; a test knob) lowers so that a small
+// call runs its row-chunk loop past the first chunk.  A value outside
+// [1, kMaterialiseBudget] or with anything but decimal digits is ignored: the
+// knob can only shrink a chunk.  (Sizing and running read it separately: a
+// caller of pmm_topk_workspace_bytes sets it identically for both.)
+size_t materialise_budget() {
+  const char *e = getenv("PMM_MATERIALISE_BUDGET");
+  if (!e || !*e) return kMaterialiseBudget;
+  unsigned long long v = 0;
+  for (const char *p = e; *p; p++) {
+    if (*p < '0' || *p > '9' || v > kMaterialiseBudget) return kMaterialiseBudget;
+    v = v * 10 + (unsigned)(*p - '0');
+  }
+  return (v >= 1 && v <= kMaterialiseBudget) ? (size_t)v : kMaterialiseBudget;
+}
+
 thread_local std::string t_err;
 
 int fail(int code, const char *fmt, ...) {
@@ -570,7 +587,7 @@ void plan_materialise(int64_t m, int64_t n, int64_t k, size_t elem, MatPlan &p) 
   p.global_sort = (k > (kRowSelMaxP - 64) / 2) || p.P > kRowSelMaxP;
   p.P2 = p.global_sort ? next_pow2((int)n, 2) : 0;
   size_t per_row = (size_t)n * elem + (p.global_sort ? (size_t)p.P2 * 16 : 0);
-  p.rows = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kMaterialiseBudget / per_row)));
+  p.rows = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(materialise_budget() / per_row)));
   size_t off = 0;
   p.off_counter = off;
   off += 256;
@@ -1855,6 +1872,9 @@ size_t f64_workspace_bytes(int64_t m, int64_t n, int64_t k, bool fused) {
 int topk_f64_materialised(const double *dq, int64_t ldq, int64_t m, const double *dc, int64_t ldc, int64_t n,
                           int64_t d, int64_t k, int metric, uint32_t index_base, uint32_t *oi, double *os,
                           char *w, hipStream_t s, const double *cn_pre = nullptr) {
+  // (planned again here, after f64_workspace_bytes sized w: the same rule on
+  // the same sizes, and the budget the same thread read a moment before in the
+  // same entry call -- the environment does not change under a running call)
   MatPlan p;
   plan_materialise(m, n, k, 8, p);
   double *qn = (double *)(w + p.off_qn), *cn = (double *)(w + p.off_cn);
@@ -4127,7 +4147,7 @@ int pmm_matmul_f32(const float *q, int64_t m, const float *c, int64_t n, int64_t
   if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_F32, std::max<int64_t>(d, 1));
   const int64_t rows_chunk =
-      std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kMaterialiseBudget / ((size_t)n * 4))));
+      std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(materialise_budget() / ((size_t)n * 4))));
   size_t off_q = 0, off_c = al256((size_t)m * dp * 4), off_o = off_c + al256((size_t)n * dp * 4);
   size_t off_cnt = off_o + al256((size_t)rows_chunk * n * 4);
   void *base;
@@ -4167,7 +4187,7 @@ int pmm_matmul_f64(const double *q, int64_t m, const double *c, int64_t n, int64
   if ((rc = thread_stream(dev, &s))) return rc;
   const int64_t dp = padded_dim(PMM_DTYPE_F64, std::max<int64_t>(d, 1));
   const int64_t rows_chunk =
-      std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(kMaterialiseBudget / ((size_t)n * 8))));
+      std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(materialise_budget() / ((size_t)n * 8))));
   size_t off_q = 0, off_c = al256((size_t)m * dp * 8), off_o = off_c + al256((size_t)n * dp * 8);
   void *base;
   if ((rc = arena(dev, s, off_o + al256((size_t)rows_chunk * n * 8), &base))) return rc;

@@ -192,6 +192,10 @@ TOPK_CASES = [
     topk_case("f32 fused dot", "f32", 130, 5000, 256, 10, DOT),
     topk_case("f32 materialised k=1025", "f32", 64, 4099, 256, 1025, DOT),
     topk_case("f32 global sort k=3000", "f32", 33, 8192, 96, 3000, COS),
+    # the materialised row-chunk loop past its first chunk: three chunks of 24, 24 and 16 rows
+    # (PMM_MATERIALISE_BUDGET = 24 rows of 4099 f32 scores, tests/row_chunk_cases.py)
+    topk_case("f32 materialised k=1025 in row chunks", "f32", 64, 4099, 256, 1025, DOT,
+              {"PMM_MATERIALISE_BUDGET": str(24 * 4099 * 4)}),
     F32_SCREENED,
     BF16_WS,
     topk_case("bf16 one-wave k=500", "bf16", 70, 5000, 96, 500, EUC),

@@ -138,6 +138,7 @@ def poisoned_workspace(q, c, k, metric, compute, label, ld=None, exact=True):
 # The first twelve are tests/test_workspace_routes.py's RUNS; the rest are the knobs and
 # shapes that change which initialisation runs.
 SCREEN_ON, SCREEN_OFF = {"PMM_F32_SCREEN": "1"}, {"PMM_F32_SCREEN": "0"}
+BUDGET_KNOB = "PMM_MATERIALISE_BUDGET"
 WORKSPACE_CASES = [
     ("f32 fused cosine", 130, 5000, 96, 10, COS, F32, {}),
     ("f32 fused dot", 130, 5000, 256, 10, DOT, F32, {}),
@@ -182,6 +183,13 @@ WORKSPACE_CASES = [
     ("screened 33x1037x37", 33, 1037, 37, 10, COS, F32, SCREEN_ON),
     ("bf16 130x5003x37", 130, 5003, 37, 10, COS, BF16, {}),
     ("bf16 33x1037x37 k=500", 33, 1037, 37, 500, DOT, BF16, {}),
+    # the materialised paths' row-chunk loops past the first chunk (PMM_MATERIALISE_BUDGET = R rows of
+    # tests/row_chunk_cases.py's per_row): the score block, the sort keys and the tile counter are reused
+    ("f32 materialised k=1025, chunks of 24 rows", 64, 4099, 256, 1025, DOT, F32, {BUDGET_KNOB: str(24 * 4099 * 4)}),
+    ("f32 global sort k=3000, chunks of 13 rows", 33, 8192, 96, 3000, COS, F32,
+     {BUDGET_KNOB: str(13 * (8192 * 4 + 8192 * 16))}),
+    ("f64 materialised, chunks of 12 rows", 33, 1037, 37, 10, EUC, "f64",
+     {"PMM_F64_FUSED": "0", BUDGET_KNOB: str(12 * 1037 * 8)}),
 ]
 
 
@@ -197,7 +205,25 @@ def test_route_in_a_poisoned_workspace(env, case):
         assert here > _native.workspace_bytes(m, n, d, k, metric, compute), f"{label}: the call does not screen"
         env.setenv("PMM_F32_SCREEN", "1")
     rs = np.random.RandomState(m + n + d + k)
-    poisoned_workspace(randn(rs, m, d), randn(rs, n, d), k, metric, compute, label)
+    if BUDGET_KNOB not in knobs:
+        poisoned_workspace(randn(rs, m, d), randn(rs, n, d), k, metric, compute, label)
+        return
+    # a row-chunk case: the clean run and the three poisoned ones each launch the score GEMM once per chunk
+    _native.timing_reset()
+    _native.timing_enable(True)
+    try:
+        if compute == "f64":
+            # (the f64 entries take no workspace argument: the host entry on a poisoned arena)
+            q, c = randn(rs, m, d, np.float64), randn(rs, n, d, np.float64)
+            want = under_poison(env, lambda: _native.topk_host(q, c, k, metric), label)
+            assert_oracle(want, q, c, k, metric, label)
+        else:
+            poisoned_workspace(randn(rs, m, d), randn(rs, n, d), k, metric, compute, label)
+        launches = _native.timing_read("gemm_f64_scores" if compute == "f64" else "gemm_f32_scores")[1]
+    finally:
+        _native.timing_enable(False)
+        _native.timing_reset()
+    assert launches == 3 * (1 + len(POISONS)), f"{label}: {launches} score launches in four calls of three chunks"
 
 
 def test_screened_rerun_rows_in_poisoned_reserved_bytes(env, capfd):
