@@ -527,6 +527,13 @@ __global__ __launch_bounds__(ws::NTH, 1) void gemm_bf16_ws_kernel(GemmF32Args a)
                     : ~0ull;
         if (SCREEN) {
           eps_l = (grow < a.M) ? a.eps[grow] : 0.0f;
+          // a guessed bound (screen_guess_kernel) above the proven one: the
+          // row prunes with it from its first tile; gthr keeps proven bounds
+          // only, so the finish can tell whether a compaction confirmed it
+          if (a.guess && grow < a.M) {
+            const u64 g = (u64)a.guess[grow] << 32;
+            if (g > t) t = g;
+          }
           t = screen_lower(t, eps_l);
         }
         thr_w[lane] = t;

@@ -883,6 +883,22 @@ struct ScreenPlan {
   size_t off_qb = 0, off_cb = 0, off_rel = 0, off_eps = 0, off_bad = 0, off_ovf = 0, off_scal = 0, off_rows = 0,
          off_crel = 0, off_gq = 0, off_f32 = 0, f32_bytes = 0, total = 0;
 };
+// The guessed starting bound's slack t: a row's guess aims at rank t k of its
+// n scores (launch_screen_guess).  Measured at c3 (profiles/screen_guess/):
+// the screen kernel's time falls with t while the rows whose guess was too high
+// (re-run by the f32 kernel) grow; the fastest t that keeps those rows under a
+// tenth of one re-run launch.
+constexpr double kScreenGuessSlack = 4.0;
+// z with P(N(0,1) > z) = p, 0 < p < 0.5 (bisection on erfc; called once per call)
+double normal_upper_quantile(double p) {
+  double lo = 0.0, hi = 40.0;
+  for (int i = 0; i < 80; i++) {
+    const double mid = 0.5 * (lo + hi);
+    if (0.5 * std::erfc(mid / std::sqrt(2.0)) > p) lo = mid;
+    else hi = mid;
+  }
+  return 0.5 * (lo + hi);
+}
 // Whether a call's shape asks for the screen.  PMM_F32_SCREEN (read per call):
 // 0 = never, 1 = wherever the limits allow, unset = from kScreenMinWork.
 bool screen_wanted(int64_t m, int64_t n, int64_t d, int64_t k, int metric) {
@@ -1288,11 +1304,52 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
       HIP_TRY(launch_seed_select(sample, ns, (int)m, (int)ns, (int)k, metric, a.gthr, s));
     }
     HIP_TRY(launch_screen_prep(rel, scal, (int)m, (int)sp.dpb, eps, a.gthr, seeded ? 1 : 0, s));
+    // A guessed bound near each row's final k-th, extrapolated from the same
+    // sample (screen_guess_kernel): the target rank is t k of n, t the slack
+    // (PMM_SCREEN_GUESS_T, default kScreenGuessSlack).  PMM_SCREEN_GUESS=0:
+    // no guess, the rows start from the seed's proven bound alone.
+    const int guess_env = getenv("PMM_SCREEN_GUESS") ? atoi(getenv("PMM_SCREEN_GUESS")) : 1;  // (per call)
+    double slack = kScreenGuessSlack;
+    if (const char *te = getenv("PMM_SCREEN_GUESS_T")) slack = atof(te);
+    const double tail = slack * (double)k / (double)n;
+    if (seeded && guess_env && slack >= 1.0 && tail < (double)k / (double)ns) {
+      // (in the rows' residuals' place: screen_prep was their last reader)
+      uint32_t *guess = (uint32_t *)rel;
+      HIP_TRY(launch_screen_guess((const float *)a.cand, (int)m, (int)ns, (float)normal_upper_quantile(tail), eps,
+                                  guess, s));
+      a.guess = guess;
+    }
   }
+#ifdef PMM_SCREEN_CEILING
+  // Experiment build only (make ab AB=-DPMM_SCREEN_CEILING; tools/experiments/
+  // screen_ceiling.py): start every row from the bound an earlier call on the
+  // same inputs ended with -- a proven bound, so the results do not change --
+  // which is the best start any guessed threshold could give the screen kernel.
+  if (const char *f = getenv("PMM_SCREEN_GTHR_LOAD")) {
+    std::vector<uint64_t> hb((size_t)m);
+    FILE *fp = fopen(f, "rb");
+    const bool ok = fp && fread(hb.data(), 8, (size_t)m, fp) == (size_t)m;
+    if (fp) fclose(fp);
+    if (!ok) return fail(PMM_ERR_ARG, "PMM_SCREEN_GTHR_LOAD: cannot read %lld bounds from %s", (long long)m, f);
+    HIP_TRY(hipMemcpyAsync(a.gthr, hb.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+#endif
   {
     Timed t("gemm_f32_topk/screen", s);
     HIP_TRY(launch_gemm_bf16_ws(a, p.grid, s, true));
   }
+#ifdef PMM_SCREEN_CEILING
+  if (const char *f = getenv("PMM_SCREEN_GTHR_SAVE")) {
+    std::vector<uint64_t> hb((size_t)m);
+    HIP_TRY(hipMemcpyAsync(hb.data(), a.gthr, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    FILE *fp = fopen(f, "wb");
+    const bool ok = fp && fwrite(hb.data(), 8, (size_t)m, fp) == (size_t)m;
+    if (fp) fclose(fp);
+    if (!ok) return fail(PMM_ERR_ARG, "PMM_SCREEN_GTHR_SAVE: cannot write %s", f);
+  }
+#endif
   {
     Timed t("merge_topk/rescore", s);
     ScreenFinishArgs fa{};
@@ -1313,6 +1370,8 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     fa.cnt = a.cnt;
     fa.gthr = a.gthr;
     fa.stat = debug ? scal + 4 : nullptr;
+    fa.guess = a.guess;
+    fa.ovf = ovf;
     HIP_TRY(launch_screen_rescore(fa, s));
   }
   {
@@ -1337,9 +1396,10 @@ int topk_f32_screened(const TopkRoute &r, const float *q, int64_t ldq, int64_t m
     memcpy(&rc, &h[0], 4);
     fprintf(stderr,
             "[pmm screen] S=%d tps=%d qb_full=%d capg=%d ctrig=%d corpus_residual=%.6g corpus_unsafe=%u "
-            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u kept=%u m=%lld handle=%d\n",
+            "rerun_rows=%u overflowed=%u whole_call_f32=%d rescored=%u max_per_row=%u kept=%u m=%lld handle=%d "
+            "guess=%d guess_missed=%u\n",
             p.S, p.tps, p.qb_full, p.capg, p.ctrig, rc, h[1], h[2], h[3], whole ? 1 : 0, h[4], h[5], h[6],
-            (long long)m, img ? 1 : 0);
+            (long long)m, img ? 1 : 0, a.guess ? 1 : 0, h[7]);
   }
   // The f32 kernel's runs never screen (k <= kScreenMaxK: always its fused
   // route); plan_screen reserved their workspace at off_f32.

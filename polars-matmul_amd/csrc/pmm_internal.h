@@ -75,6 +75,12 @@ struct GemmF32Args {
   // flags set when a row's kept band outgrew its candidate segment
   const float *eps;
   unsigned *ovf;
+  // screened f32 path, optional: per-row guessed bounds of the exact k-th
+  // (launch_screen_guess).  A row starts from max(gthr, guess); gthr itself
+  // only ever holds proven bounds, so "gthr[row] < guess[row]" after the pass
+  // says the row's guess was never confirmed (screen_rescore_kernel decides).
+  // Stored as the composite's high word (the score key; the low word is 0).
+  const uint32_t *guess;
   // range mode (f32 kernel, mode 2): the threshold as a composite (okey32 of
   // its ranking value << 32; an element hits iff its composite is at or above
   // it), the record arena -- rcap records as key (okey32(rank value) << 32 |
@@ -438,13 +444,26 @@ struct ScreenFinishArgs {
   // optional: [0] += candidates re-scored (rows gathered), [1] = max per row,
   // [2] += entries at or above the published bound - eps (one pass's gathers)
   unsigned *stat;
+  // optional (with ovf): the rows' guessed starting bounds.  A row whose
+  // proven bound (gthr) stayed below its guess is finished only if the k best
+  // approximate entries' exact scores all reach the guess; otherwise ovf[row]
+  // = kScreenGuessMissed (unless already set) and the row is re-run.
+  const uint32_t *guess;
+  unsigned *ovf;
 };
+constexpr unsigned kScreenGuessMissed = 2u;  // ovf[row]: 1 = the band outgrew the segment
+// guess[row] = a bound of row's exact k-th extrapolated from its ns sample
+// scores S[row][0 .. ns) (mean + z standard deviations, lowered by eps[row]);
+// 0 = no guess; the score key (high word) of the composite.  ns <= 4096.
+hipError_t launch_screen_guess(const float *S, int m, int ns, float z, const float *eps, uint32_t *guess,
+                               hipStream_t s);
 // every kept candidate's approximate key replaced by its exact composite (the
 // f32 path's fmaf chain and epilogue); entries below the bound dropped -- the
 // published one lowered by eps, raised to (the exact k-th of the k best
 // approximate entries) - eps once those are scored
 hipError_t launch_screen_rescore(const ScreenFinishArgs &a, hipStream_t s);
-// rows[0 .. *count) = the rows with ovf[row] | bad[row] set; count[1] += the overflowed ones
+// rows[0 .. *count) = the rows with ovf[row] | bad[row] set; count[1] += the overflowed
+// ones, count[5] += those whose guessed bound was not confirmed (kScreenGuessMissed)
 hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,
                                  hipStream_t s);
 // cosine and dot lists: +0.0 scores whose reference value is -0.0 get their

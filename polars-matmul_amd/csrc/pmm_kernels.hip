@@ -2503,6 +2503,56 @@ hipError_t launch_screen_prep(const float *rel, const unsigned *scal, int m, int
   return hipGetLastError();
 }
 
+// A guessed starting bound per row.  The seed's bound is the k-th of ns sample
+// columns: about k n / ns of a row's n scores pass it, and the row's threshold
+// then climbs only at its compactions, so most 32 x 32 score groups of the
+// pass hold a survivor and take the queueing path.  A bound near the row's
+// *final* k-th from the first tile on avoids that, but the sample cannot
+// resolve that order statistic (rank k of n is rank k ns / n < 1 of the
+// sample), so it is extrapolated: the sample's mean plus z standard deviations,
+// z the standard normal quantile of rank t k of n (the caller's; t > 1 is the
+// slack: the row expects t k scores above the guess).  One wave per row, one
+// read of the sample, sums in f64.  The guess is not proven: the screen kernel
+// starts from max(proven bound, guess) and screen_rescore_kernel confirms it
+// or sends the row to the re-run, so a wrong guess costs time, never a result.
+// guess[row] lies in gthr's space (a bound of the exact k-th: the approximate
+// value less eps) as the composite's score key, its high word; 0 = none (a
+// sample that is not finite).
+__global__ __launch_bounds__(256) void screen_guess_kernel(const float *__restrict__ S, int m, int ns, float z,
+                                                           const float *__restrict__ eps,
+                                                           uint32_t *__restrict__ guess) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= m) return;
+  const float *src = S + (int64_t)row * ns;
+  double s1 = 0.0, s2 = 0.0;
+  for (int j = lane; j < ns; j += 64) {
+    const double v = (double)src[j];
+    s1 += v;
+    s2 += v * v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s1 += __shfl_xor(s1, o, 64);
+    s2 += __shfl_xor(s2, o, 64);
+  }
+  if (lane != 0) return;
+  const double mean = s1 / (double)ns;
+  const double var = fmax(0.0, s2 / (double)ns - mean * mean);
+  const float g = (float)(mean + (double)z * sqrt(var));
+  u64 out = 0ull;
+  // (no guess from a NaN or infinite sample, nor one above every cosine)
+  if (fabsf(g) <= 1.0f) out = screen_lower((u64)okey32(g) << 32, eps[row]);
+  guess[row] = (uint32_t)(out >> 32);
+}
+hipError_t launch_screen_guess(const float *S, int m, int ns, float z, const float *eps, uint32_t *guess,
+                               hipStream_t s) {
+  if (m <= 0) return hipSuccess;
+  if (ns < 2 || ns > 4096) return hipErrorInvalidValue;
+  screen_guess_kernel<<<(unsigned)((m + 3) / 4), 256, 0, s>>>(S, m, ns, z, eps, guess);
+  return hipGetLastError();
+}
+
 // Exact finish, first half: one one-wave workgroup per query row (staged in
 // LDS, read as broadcasts).  The wave gathers the listed candidates' corpus
 // rows together, kRescoreRows rows at a time and one 128-byte line of each
@@ -2690,6 +2740,17 @@ __global__ __launch_bounds__(kRescoreThreads, 5) void screen_rescore_kernel(Scre
     u64 thr = P;
     if (last) {
       __syncthreads();  // (phase 1's e_k is complete; none ran: ~0, which lowers to 0)
+      // A row that started from a guess no compaction confirmed (its proven
+      // bound is still below the guess): everything the screen dropped had an
+      // approximate score below guess - eps, so an exact score below the guess.
+      // With phase 1's k exact scores all at or above the guess those entries
+      // lie strictly below k held candidates and the row is complete; without
+      // (fewer than k live entries, or e_k below the guess) it is re-run.
+      if (a.guess && tid == 0) {
+        const u64 g = (u64)a.guess[row] << 32;
+        const bool confirmed = n_r > (unsigned)a.k && ((u64)emin << 32) >= g;
+        if (a.gthr[row] < g && !confirmed && a.ovf[row] == 0u) a.ovf[row] = kScreenGuessMissed;
+      }
       const u64 E = screen_lower((u64)emin << 32, eps);
       thr = E > T1 ? E : T1;
     }
@@ -2938,7 +2999,8 @@ __global__ __launch_bounds__(256) void screen_collect_kernel(const unsigned *__r
   const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (row < m && (ovf[row] | bad[row])) {
     rows[atomicAdd(count, 1u)] = row;
-    if (ovf[row]) atomicAdd(count + 1, 1u);
+    if (ovf[row] == kScreenGuessMissed) atomicAdd(count + 5, 1u);
+    else if (ovf[row]) atomicAdd(count + 1, 1u);
   }
 }
 hipError_t launch_screen_collect(const unsigned *ovf, const unsigned *bad, int m, unsigned *count, int *rows,
