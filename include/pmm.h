@@ -962,6 +962,36 @@ int pmm_topk_f32_maxsim(const pmm_corpus *corpus, const float *q_tokens, const i
 int pmm_range_f32_self(const pmm_corpus *corpus, float threshold, int metric, int64_t cap,
                        int64_t *out_offsets /* n + 1 */, uint32_t *out_idx, float *out_score, int64_t *total);
 
+/* pmm_components_f32_self: duplicate groups -- the connected components of the
+ * pairs pmm_range_f32_self lists.  Let E be the set of pairs (i, j), i < j,
+ * that pmm_range_f32_self(threshold, metric) lists for this handle: the same
+ * score bits, the same folding of the two zeros, a NaN score never an edge,
+ * the diagonal never present.  out_labels[i] is the smallest handle position
+ * in i's connected component of (rows, E), reported as a PARENT row number on
+ * a derived handle (the map ascends, so it is the smallest parent row too); a
+ * row with no edge labels itself.  The value does not depend on the order the
+ * hits are found in.  *components: the number of distinct labels; *pairs:
+ * |E|, pmm_range_f32_self's total.
+ * The pass is pmm_range_f32_self's emit pass -- the triangular schedule, the
+ * pre-filter, the exact score, the hit predicate -- except that a hit leaves no
+ * record: it is counted, and its two rows are united in a lock-free union-find
+ * over n words (the higher root linked under the lower by compare-and-swap),
+ * where it is found.  One more launch reads every row's root.  Device memory
+ * does NOT grow with the number of hits: the arena is the n parents, the n
+ * labels and the pass's survivor queues, whether the column has no pair or
+ * n (n - 1) / 2 of them, and there is no cap / total protocol and no second
+ * run.  One wait: the labels and the pair count come back together.
+ * Handles, refusals and their texts are pmm_range_f32_self's: an f32 handle of
+ * one shard, plain or derived; sharded and int8 handles PMM_ERR_UNSUPPORTED,
+ * partitioned, f64 and bf16 handles PMM_ERR_ARG; a NaN threshold, a bad
+ * metric, a null corpus, components or pairs: PMM_ERR_ARG, all before the
+ * handle is read or a device touched.  n = 0: PMM_OK, both counts 0, nothing
+ * else written (out_labels may be NULL); otherwise a null out_labels is
+ * PMM_ERR_ARG.  n = 1: the row's own number, 1 component, 0 pairs, no launch.
+ * Thread-safe like the other handle entries; no reference counterpart. */
+int pmm_components_f32_self(const pmm_corpus *corpus, float threshold, int metric,
+                            uint32_t *out_labels /* n */, int64_t *components, int64_t *pairs);
+
 /* pmm_topk_f32_self: row i's list is the ranked list of all n rows for query
  * row i (pmm_topk_f32_corpus' order: best first, NaN last, ties to the lower
  * index) with row i itself removed and then cut at k; 1 <= k <= n - 1 (else

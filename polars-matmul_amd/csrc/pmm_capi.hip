@@ -5073,6 +5073,131 @@ static int range_search(const pmm_corpus *h, bool self, const float *q, int64_t 
   return PMM_OK;
 }
 
+// Duplicate groups (DESIGN.md §4d "Duplicate groups"): the connected
+// components of the self range search's pairs.  The self path of range_search
+// with the components pass in place of the emit pass: a hit unites its two
+// rows where it is found, so the arena holds n parents and n labels whatever
+// the number of hits, and there is no second run, bin, sort or decode.
+int pmm_components_f32_self(const pmm_corpus *h, float threshold, int metric, uint32_t *out_labels,
+                            int64_t *components, int64_t *pairs) {
+  // every argument check before the handle is read or a device touched
+  if (!h) return fail(PMM_ERR_ARG, "null corpus");
+  if (!components || !pairs) return fail(PMM_ERR_ARG, "null argument");
+  int rc = check_metric(metric);
+  if (rc) return rc;
+  if (threshold != threshold) return fail(PMM_ERR_ARG, "the range threshold is NaN");
+  if ((rc = range_handle(h, "self search"))) return rc;
+  const int64_t n = h->n, dp = h->dp;
+  if ((rc = validate_sizes(n, n, h->d, 0, false))) return rc;
+  if (n > 0 && !out_labels) return fail(PMM_ERR_ARG, "null argument");
+  *components = 0;
+  *pairs = 0;
+  if (n == 0) return PMM_OK;
+
+  if (n == 1 && !h->map) {  // (one row has no pair: its own number, no device touched)
+    out_labels[0] = 0u;
+    *components = 1;
+    return PMM_OK;
+  }
+  const CorpusShard &x = h->shards[0];
+  ShardCall f;
+  if ((rc = f.open(h))) return rc;
+  const hipStream_t s = f.s;
+  if (n == 1) {  // (derived: the row's parent number is on the device; a copy, no launch)
+    rc = f.run([&]() -> int {
+      HIP_TRY(hipMemcpyAsync(out_labels, h->map, 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      return PMM_OK;
+    });
+    if (rc) return rc;
+    *components = 1;
+    return PMM_OK;
+  }
+  Plan p;
+  p.variant = range_variant(n, n, f.cus);
+  const int bn = gemm_f32_bn(p.variant);
+  plan_units(n, n, gemm_f32_bm(p.variant), bn, f.cus, 0.5, 1 << 20, p);
+
+  // arena: [work counter, cursor] | parent | labels | survivor queues --
+  // nothing in it depends on the number of hits
+  Layout L;
+  const size_t off_ctl = L.take(256);
+  const size_t off_parent = L.take((size_t)n * 4);
+  const size_t off_labels = L.take((size_t)n * 4);
+  const size_t off_wq = L.take((size_t)p.grid * gemm_f32_nw(p.variant) * 32 * bn * 8);
+  void *base;
+  if ((rc = arena(f.dev, s, L.off, &base))) return rc;
+  char *b = (char *)base;
+  HIP_TRY(hipMemsetAsync(b + off_ctl, 0, 256, s));
+  uint32_t *parent = (uint32_t *)(b + off_parent), *labels = (uint32_t *)(b + off_labels);
+  HIP_TRY(launch_components_init(parent, n, s));
+  // the threshold's composite, as range_search states it
+  const float rank = metric == kMetricEuclidean ? -threshold : threshold;
+  uint32_t tu;
+  memcpy(&tu, &rank, 4);
+  if ((tu << 1) == 0u) tu = 0u;
+  const uint32_t tkey = (tu & 0x80000000u) ? ~tu : (tu | 0x80000000u);
+
+  GemmF32Args a{};
+  a.q = x.rows_as<float>();
+  a.c = a.q;
+  a.qn = shard_norms<float>(h, x, metric);
+  a.cn = a.qn;
+  a.cpre = a.cn ? a.cn + n : nullptr;
+  a.ldq = dp;
+  a.ldc = dp;
+  a.M = (int)n;
+  a.N = (int)n;
+  a.D = (int)dp;
+  a.metric = metric;
+  a.QB = p.QB;
+  a.S = p.S;
+  a.tps = p.tps;
+  a.ntiles = p.T;
+  a.units = p.units;
+  a.counter = (unsigned *)(b + off_ctl);
+  a.wq = (unsigned long long *)(b + off_wq);
+  a.rthr = (unsigned long long)tkey << 32;
+  a.rcur = (unsigned long long *)(b + off_ctl + 8);
+  a.parent = parent;
+  {
+    Timed t("gemm_f32_components", s);
+    HIP_TRY(launch_gemm_f32_components(a, p.variant, p.grid, s));
+  }
+  {
+    Timed t("components_label", s);
+    HIP_TRY(launch_components_label(parent, h->map, n, labels, s));
+  }
+  // the call's one wait: the labels and the cursor together
+  unsigned long long cursor = 0;
+  rc = f.run([&]() -> int {
+    {
+      Timed t("d2h", s);
+      HIP_TRY(hipMemcpyAsync(out_labels, labels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&cursor, a.rcur, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return PMM_OK;
+  });
+  if (rc) return rc;
+  // The count leans on two facts, both stated here and nowhere else: unite
+  // always links the higher root under the lower, so a component's root is its
+  // smallest position; and a derived handle's map ascends, so labels keep the
+  // positions' order.  Then a root's label is above every label at a lower
+  // position, and a member's label (its root's) is not: the roots are the
+  // positions where the running maximum of the labels rises.
+  int64_t roots = 1;
+  uint32_t top = out_labels[0];
+  for (int64_t i = 1; i < n; i++)
+    if (out_labels[i] > top) {
+      top = out_labels[i];
+      roots++;
+    }
+  *components = roots;
+  *pairs = (int64_t)cursor;
+  return PMM_OK;
+}
+
 // Candidate search (DESIGN.md §4d "Candidate lists"): score every (row,
 // candidate) pair into the CSR key layout of the range search, sort each
 // row's segment with its kernels, cut at k and decode into the [m][k] planes.

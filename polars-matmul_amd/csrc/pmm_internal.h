@@ -92,6 +92,9 @@ struct GemmF32Args {
   unsigned long long *rkey;
   uint32_t *rrow;
   unsigned long long rcap;
+  // components mode (f32 kernel, mode 4): the union-find forest over the n
+  // rows, parent[i] = i before the pass (launch_components_init)
+  uint32_t *parent;
 };
 
 struct MergeArgs {
@@ -167,6 +170,17 @@ hipError_t launch_gemm_f32_self(const GemmF32Args &a, int variant, int grid, hip
 __host__ __device__ inline int self_first_tile(int n, int row0, int bn, int ntiles) {
   return n - 1 > row0 ? (row0 + 1) / bn : ntiles;
 }
+// mode 4 = components (pmm_components_f32_self): self mode's schedule, filter
+// and hit predicate; a hit is counted on *rcur and unites its two rows in
+// GemmF32Args::parent (lock-free union-find, the higher root under the lower)
+// -- no record, no per-row count.
+hipError_t launch_gemm_f32_components(const GemmF32Args &a, int variant, int grid, hipStream_t s);
+// ---- duplicate groups: the forest's two passes (pmm_range.hip) ----
+// parent[i] = i, i < n
+hipError_t launch_components_init(uint32_t *parent, int64_t n, hipStream_t s);
+// labels[i] = map ? map[root of i] : root of i, after the components pass
+hipError_t launch_components_label(const uint32_t *parent, const uint32_t *map, int64_t n, uint32_t *labels,
+                                   hipStream_t s);
 // ---- range search: records -> per-row best-first lists (pmm_range.hip) ----
 // Segments of up to kRangeWaveMax keys sort in one wave's registers, up to
 // kRangeSortMax in one workgroup's LDS (64 KiB of keys).

@@ -186,6 +186,52 @@ size_t gemm_f32_lds_bytes(int variant, int mode, int capg) { return gemm_f32_lds
 #define PMM_F32_KORDER_SMALL 3
 #endif
 
+// Components mode (MODE 4; pmm_components_f32_self): lock-free union-find over
+// parent[] (parent[i] = i at the start), the higher root always linked under
+// the lower.  The invariant: every write to parent[x] -- a link or a halving
+// store -- stores a strictly smaller id of x's own tree, and trees only merge.
+// So there is no cycle, every walk ends, whatever a lane reads -- however
+// stale -- is a node of the same tree, and a tree's root changes only by a
+// link.  A link re-points only a root (the CAS expects parent[hi] == hi); a
+// failed CAS costs a retry from the value it returned, never a wrong link.
+// The smallest row of a component can be linked under nothing: it is the
+// final root.  No lane holds a lock, so the divergent lanes of one wave cannot
+// block each other.  The loads are agent-scope atomics (the form the epilogue
+// reads gq with): a CU's vector L1 is not coherent with the other CUs' writes.
+// find halves the path as it goes: x, never a root again once it had a
+// parent, is re-pointed by an atomic store to the grandparent just read -- a
+// smaller node of x's tree, though a store that lands late may no longer be
+// the shortest way up (a link CAS on x expects parent[x] == x, which no longer
+// occurs, so the two never meet).
+__device__ __forceinline__ uint32_t components_find(uint32_t *parent, uint32_t x) {
+  for (;;) {
+    const uint32_t p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p == x) return x;
+    const uint32_t g = __hip_atomic_load(parent + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (g == p) return p;
+    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = g;
+  }
+}
+__device__ __forceinline__ void unite(uint32_t *parent, uint32_t x, uint32_t y) {
+  // (a shared parent is a node of both rows' trees: they are one already.  In a
+  // large group nearly every hit ends here, on two loads at the rows' own
+  // words instead of a walk that ends on the one root's)
+  if (__hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+      __hip_atomic_load(parent + y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    return;
+  for (;;) {
+    x = components_find(parent, x);
+    y = components_find(parent, y);
+    if (x == y) return;
+    const uint32_t hi = max(x, y), lo = min(x, y);
+    const uint32_t old = atomicCAS(parent + hi, hi, lo);  // (agent scope)
+    if (old == hi) return;
+    x = old;
+    y = lo;
+  }
+}
+
 template <int NB, int NW, int MODE, int METRIC, bool AK>
 __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a) {
   using G = GemmShape<NB, NW, AK>;
@@ -298,11 +344,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
       qb = (MODE == 0 ? a.qb_full : 0) + (u2 - s * qbb);
       // self mode: the splits last to first, so the units that every block
       // runs whole go out first and the ones the diagonal cuts short last
-      if (MODE == 3) s = a.S - 1 - s;
+      if (MODE == 3 || MODE == 4) s = a.S - 1 - s;
       t0 = s * a.tps;
       t1 = min(t0 + a.tps, a.ntiles);
     }
-    if (MODE == 3) {
+    if (MODE == 3 || MODE == 4) {
       // self mode (queries = corpus rows): only tiles with a column above the
       // block's first row, min(N, (t + 1) BN) - 1 > qb BM, hold a pair (row,
       // column > row); the rule is monotone in t, so it clamps t0
@@ -334,7 +380,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         const u64 t = (grow < a.M) ? a.rthr : ~0ull;
         thr_w[lane] = t;
         lo_w[lane] = prefilter_bound<METRIC>(t, qv);
-        cnt_w[lane] = 0u;
+        if (MODE != 4) cnt_w[lane] = 0u;
       }
     }
     wave_sync();
@@ -740,7 +786,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
           // Self mode: in a tile that reaches down to this wave's rows (a
           // wave-uniform test) a hit is also above the diagonal, column > row;
           // every other visited tile lies wholly above it.
-          const bool diag = MODE == 3 && col0 <= wrow0 + 31;
+          const bool diag = (MODE == 3 || MODE == 4) && col0 <= wrow0 + 31;
           if (qlen) {
             if (!G::CNL || qlen > a.qcap) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (G::CNL) wave_sync();
@@ -764,7 +810,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
                 if (diag) hit = hit && gcol > wrow0 + rl;
               }
               const u64 hm = __ballot(hit);
-              if (hm) {
+              if (MODE == 4) {
+                // components mode: nothing per pair is stored -- the cursor
+                // counts the pairs, every hit unites its two rows
+                if (hm) {
+                  if (lane == 0) atomicAdd(a.rcur, (u64)__popcll(hm));
+                  if (hit) unite(a.parent, (uint32_t)(wrow0 + rl), (uint32_t)(~(uint32_t)comp));
+                }
+              } else if (hm) {
                 u64 slot0 = 0ull;
                 if (lane == 0) slot0 = atomicAdd(a.rcur, (u64)__popcll(hm));
                 slot0 = wave_uniform_u64(slot0);
@@ -831,7 +884,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_f32_kernel(GemmF32Args a
         if (grow < a.M) a.cnt[(int64_t)grow * a.S + seg] = cnt_w[lane];
       }
     }
-    if (MODE >= 2) {
+    if (MODE == 2 || MODE == 3) {
       // one add per row this unit touched
       wave_sync();
       if (lane < 32) {
@@ -946,6 +999,12 @@ hipError_t launch_gemm_f32_range(const GemmF32Args &a, int variant, int grid, hi
 hipError_t launch_gemm_f32_self(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
   if (a.q != a.c || a.M != a.N || a.ldq != a.ldc) return hipErrorInvalidValue;
   return launch_gemm_f32_range_m<3>(a, variant, grid, s);
+}
+// Components mode (MODE 4; pmm_components_f32_self): self mode's schedule, a
+// hit unites its two rows in a.parent instead of leaving a record.
+hipError_t launch_gemm_f32_components(const GemmF32Args &a, int variant, int grid, hipStream_t s) {
+  if (a.q != a.c || a.M != a.N || a.ldq != a.ldc || !a.parent) return hipErrorInvalidValue;
+  return launch_gemm_f32_range_m<4>(a, variant, grid, s);
 }
 
 // ===========================================================================

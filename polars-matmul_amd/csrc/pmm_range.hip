@@ -136,6 +136,24 @@ __global__ __launch_bounds__(256) void drop_self_kernel(const uint32_t *__restri
   }
 }
 
+// Duplicate groups (pmm_components_f32_self): the union-find forest before
+// and after the components pass of the f32 GEMM (MODE 4).  The label pass
+// reads with plain loads: the kernel boundary orders them after every link.
+__global__ __launch_bounds__(256) void components_init_kernel(uint32_t *__restrict__ parent, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) parent[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(256) void components_label_kernel(const uint32_t *__restrict__ parent,
+                                                               const uint32_t *__restrict__ map, int64_t n,
+                                                               uint32_t *__restrict__ labels) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x = (uint32_t)i;
+  for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+  labels[i] = map ? map[x] : x;
+}
+
 static unsigned range_grid(int64_t count) {
   const int64_t blocks = (count + 255) / 256;
   return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));
@@ -173,6 +191,21 @@ hipError_t launch_drop_self(const uint32_t *in_idx, const float *in_score, int64
   if (m <= 0 || k <= 0) return hipSuccess;
   if (m > INT32_MAX || k >= INT32_MAX) return hipErrorInvalidValue;
   drop_self_kernel<<<(unsigned)((m + 3) / 4), 256, 0, s>>>(in_idx, in_score, (int)m, (int)k, out_idx, out_score);
+  return hipGetLastError();
+}
+
+hipError_t launch_components_init(uint32_t *parent, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+  components_init_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(parent, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_components_label(const uint32_t *parent, const uint32_t *map, int64_t n, uint32_t *labels,
+                                   hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+  components_label_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(parent, map, n, labels);
   return hipGetLastError();
 }
 

@@ -24,7 +24,10 @@ lists, on Float32 columns.  ``.pmm.within_self(threshold, metric)`` and
 ``.pmm.topk_self(k, metric)`` (extensions; ``within_self`` / ``topk_self`` and
 ``_within_self`` / ``_topk_self`` without Polars) search one column against
 itself -- every near-duplicate pair once, and the k-nearest-neighbour graph of
-its rows -- with the column's cached handle as its own query side.
+its rows -- with the column's cached handle as its own query side;
+``.pmm.duplicate_groups(threshold, metric)`` (``duplicate_groups`` /
+``_duplicate_groups`` without Polars) labels every row with the first row of
+its near-duplicate group, the pairs united on the device, none stored.
 ``.pmm.topk_maxsim(docs, k, metric, candidates=)`` (an extension;
 ``topk_maxsim`` / ``_topk_maxsim`` without Polars) is late-interaction search:
 both columns hold lists of token vectors and a pair scores MaxSim, the sum
@@ -69,6 +72,7 @@ from polars_matmul._polars_matmul import (  # noqa: F401
     _topk_maxsim,
     _within,
     _within_self,
+    _duplicate_groups,
     _sign_bits,
     _topk_hamming,
     pack_sign,
@@ -78,8 +82,8 @@ from polars_matmul._polars_matmul import (  # noqa: F401
 from polars_matmul import _native
 
 __version__ = "0.1.4"
-__all__ = ["PmmNamespace", "topk", "topk_maxsim", "within", "within_self", "topk_self", "matmul", "set_devices", "get_devices",
-           "pack_sign", "topk_hamming", "kmeans"]
+__all__ = ["PmmNamespace", "topk", "topk_maxsim", "within", "within_self", "topk_self", "duplicate_groups", "matmul",
+           "set_devices", "get_devices", "pack_sign", "topk_hamming", "kmeans"]
 
 Metric = Literal["cosine", "dot", "euclidean"]
 Compute = Literal["f32", "bf16"]
@@ -323,6 +327,30 @@ def within_self(corpus: np.ndarray, threshold: float, metric: Metric = "cosine",
     return offsets, idx, sc.astype(np.float64)
 
 
+def duplicate_groups(corpus: np.ndarray, threshold: float, metric: Metric = "cosine", compute: Compute = "f32"):
+    """numpy-level duplicate groups (an extension): labels uint32 [n], the
+    connected components of ``within_self(corpus, threshold, metric)``'s pairs.
+    ``labels[i]`` is the smallest row number in row i's group; a row with no
+    near-duplicate labels itself, so ``labels == arange(n)`` marks the one row
+    to keep of every group.  The pairs are united on the device where they are
+    found: no pair list is built, and the memory of the call does not grow
+    with the number of duplicates.  Float32 matrices only (Float64 input and
+    compute="bf16" raise TypeError); the corpus cache as in ``within``."""
+    from polars_matmul._polars_matmul import _self_device, _self_f32_only
+
+    if _native.check_compute(compute) == "bf16":
+        raise _self_f32_only('compute="bf16" has no self search')
+    c = _self_matrix(corpus)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    metric_id = _native.metric_from_str(metric)
+    if c.shape[0] == 0:
+        return np.zeros(0, dtype=np.uint32)
+    cc = np.ascontiguousarray(c)
+    return _self_device(cc, cc, cc, lambda dc: dc.components_self(threshold, metric_id), numpy_ok=cc is corpus)[0]
+
+
 def topk_self(corpus: np.ndarray, k: int, metric: Metric = "cosine", compute: Compute = "f32"):
     """numpy-level self top-k (an extension): the k-nearest-neighbour graph of
     one matrix.  Returns (indices uint32 [n, k'], scores float64 [n, k']) with
@@ -514,6 +542,25 @@ if pl is not None:
                 lambda s: _within_self(s, threshold, metric),
                 is_elementwise=False,
                 return_dtype=pl.List(pl.Struct({"index": pl.UInt32, "score": pl.Float64})),
+            )
+
+        def duplicate_groups(self, threshold: float, metric: Metric = "cosine",
+                             compute: Compute = "f32") -> "pl.Expr":
+            """Duplicate groups (an extension): for every embedding the number
+            of the first row of its near-duplicate group -- the connected
+            components of ``within_self(threshold, metric)``'s pairs -- as
+            UInt32; a row with no near-duplicate carries its own number, so
+            comparing with the row index keeps one row per group.  No pair
+            list is built: memory does not grow with the number of duplicates.
+            Not elementwise; Float32 columns only."""
+            if _native.check_compute(compute) == "bf16":
+                from polars_matmul._polars_matmul import _self_f32_only
+
+                raise _self_f32_only('compute="bf16" has no self search')
+            return self._expr.map_batches(
+                lambda s: _duplicate_groups(s, threshold, metric),
+                is_elementwise=False,
+                return_dtype=pl.UInt32,
             )
 
         def topk_self(self, k: int, metric: Metric = "cosine", compute: Compute = "f32") -> "pl.Expr":

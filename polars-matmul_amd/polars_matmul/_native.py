@@ -98,6 +98,7 @@ EXPORTED_SYMBOLS = (
     "pmm_kmeans_f32_corpus",
     "pmm_range_f32_self",
     "pmm_topk_f32_self",
+    "pmm_components_f32_self",
     "pmm_range_self_plan",
     "pmm_sort_plan",
     "pmm_topk_i8",
@@ -230,6 +231,8 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_int)], _i32),
     "pmm_range_f32_self": ([_vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_topk_f32_self": ([_vp, _i64, _i32, _vp, _vp], _i32),
+    "pmm_components_f32_self": ([_vp, ctypes.c_float, _i32, _vp, ctypes.POINTER(ctypes.c_int64),
+                                 ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_range_self_plan": ([_i64, _i32, _i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
                              ctypes.POINTER(ctypes.c_int64)], _i32),
     "pmm_sort_plan": ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
@@ -1133,6 +1136,25 @@ class DeviceCorpus:
         n = self.n
         return self._range(n, n * (n - 1) // 2, cap, lambda *out: _lib.pmm_range_f32_self(
             self._h, float(threshold), metric, *out))
+
+    def components_self(self, threshold: float, metric: int):
+        """(labels uint32 (n,), components, pairs) of pmm_components_f32_self:
+        the duplicate groups of the handle's rows -- the connected components
+        of the pairs ``range_self(threshold, metric)`` lists.  ``labels[i]`` is
+        the smallest position in row i's group (a derived handle returns its
+        parent's row numbers), ``components`` the number of groups, ``pairs``
+        the number of pairs (``range_self``'s total).  No pair is stored: the
+        device memory of the call is a few words per row whatever the number of
+        hits, and there is no cap and no second run."""
+        labels = np.empty(self.n, dtype=np.uint32)
+        components, pairs = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.acquire()
+        try:
+            check(_lib.pmm_components_f32_self(self._h, float(threshold), metric, ptr(labels),
+                                               ctypes.byref(components), ctypes.byref(pairs)))
+        finally:
+            self.release()
+        return labels, components.value, pairs.value
 
     def topk_self(self, k: int, metric: int):
         """(idx uint32 (n, k'), scores float32 (n, k')) of pmm_topk_f32_self:

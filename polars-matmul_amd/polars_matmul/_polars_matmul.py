@@ -1579,6 +1579,29 @@ def _within_self(col, threshold, metric):
     return _wrap(_csr_arrow(offsets, idx, sc), "within_self", polars_out)
 
 
+def _duplicate_groups(col, threshold, metric):
+    """Duplicate groups (an extension): the connected components of
+    ``_within_self(col, threshold, metric)``'s pairs, as a UInt32 column named
+    "duplicate_groups": every row carries the number of the first row of its
+    group, and a row with no near-duplicate its own.  The pairs are united on
+    the device where they are found, so no pair list is built: the memory of
+    the call does not grow with the number of duplicates.  Float32 columns
+    only."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise TypeError(f"threshold must be a number, not {type(threshold).__name__}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    polars_out, rv = _self_column(col, metric)
+    if _nrows(rv) == 0:
+        return _wrap(pa.array([], type=pa.uint32()), "duplicate_groups", polars_out)
+    metric_id = _self_metric(metric)
+    c = _series_to_matrix(rv, np.float32)
+    _apply_devices_env()
+    labels = _self_device(c, col, rv, lambda dc: dc.components_self(threshold, metric_id))[0]
+    return _wrap(pa.array(labels, type=pa.uint32()), "duplicate_groups", polars_out)
+
+
 def _topk_self(col, k, metric):
     """Self top-k (an extension): for every row of ``col`` its min(k, n - 1)
     best OTHER rows, as List[Struct{index: UInt32, score: Float64}] named
